@@ -7,7 +7,7 @@ resident in HBM.  N=1 runs BASELINE.json configs[1] (single 512x512 patch, 20 st
 mode); with N>1 every rank runs the same per-GPU workload on its own stamps (weak scaling) and the
 decoded u8 patches are gathered to rank 0 over RCCL inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--res R] [--ddim-steps S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--res R] [--ddim-steps S] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts its N ranks itself (launch_ranks: rank r -> GPU r, a free rendezvous port on
@@ -291,6 +291,39 @@ def emit(line):
     return text
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together, as float32
+
+
+def sample_output(x, max_values, seed=0):
+    """`x` as float32 on the host, or -- when it holds more than `max_values` values -- a fixed, seeded sample of it: whole stamps (rows
+    of the first axis) drawn at random and kept in order, and, if even one stamp is larger than the budget, the same random subset of
+    values from each kept stamp."""
+    x = x.detach().cpu()
+    if x.numel() <= max_values:
+        return x.to(torch.float32)
+    g = torch.Generator().manual_seed(seed)
+    rows = x.reshape(x.shape[0], -1)
+    keep = max(1, min(rows.shape[0], max_values // rows.shape[1]))
+    rows = rows[torch.randperm(rows.shape[0], generator=g)[:keep].sort().values]
+    if rows.numel() > max_values:
+        rows = rows[:, torch.randperm(rows.shape[1], generator=g)[:max_values // keep].sort().values]
+    return rows.to(torch.float32)
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy in float32, at most `limit_bytes` in all (the budget is split evenly between the
+    arrays; a larger array is replaced by sample_output's seeded sample).  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    per_array = limit_bytes // 4 // max(1, len(arrays))
+    shapes = {}
+    for name, x in arrays.items():
+        v = sample_output(x, per_array).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        shapes[name] = list(v.shape)
+    return shapes
+
+
 def write_detail(path, detail):
     """Per-kernel / per-class tables of the profiled pass go to a side file (default gpurun_out/bench_detail.json: it travels back from the
     GPU box), never into the line."""
@@ -446,7 +479,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the extra configurations (batch 8, 256 px, oracle pixel error)")
     ap.add_argument("--dump-launches", default="", help="CSV with one line per profiled kernel launch")
     ap.add_argument("--detail", default="", help="side file for the per-kernel tables (default gpurun_out/bench_detail.json)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (the u8 RGB patches, as float32) to DIR/patches.npy, at most 64 MB")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.cpu_config0:
         print(json.dumps(cpu_config0()))
         return
@@ -510,12 +547,16 @@ def main():
     t0 = time.perf_counter()
     for _ in range(a.steps):
         s0 = time.perf_counter()
-        one_step()
+        last = one_step()
         torch.cuda.synchronize()
         lat_ms.append((time.perf_counter() - s0) * 1e3)
     D.barrier()
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
+    if a.dump_outputs and rank == 0:  # before any other pass reuses the output / gather buffers
+        shapes = dump_outputs(a.dump_outputs, {"patches": last})
+        print(f"[bench] outputs of the last timed step -> {a.dump_outputs}: {shapes}", file=sys.stderr, flush=True)
+    del last
     stage = model.stage_times_ms()
     info = model.stamp_info()
 

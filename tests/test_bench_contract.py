@@ -154,3 +154,27 @@ def test_plain_multi_gpu_command_starts_its_own_ranks():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'if "RANK" not in os.environ and (a.gpus > 1 or os.environ.get("DTP_BENCH_FORCE_DIST")):' in src
     assert src.index("launch_ranks(a, sys.argv[1:])") < src.index("D.init_from_env(")
+
+
+def test_dump_outputs_writes_float32_within_the_budget_and_samples_the_same_way_every_time(tmp_path):
+    """--dump-outputs: the last timed step's patches as DIR/<name>.npy in float32; a tensor larger than the budget becomes a fixed,
+    seeded sample (whole stamps first, then the same values of each kept stamp), so two runs write identical files."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    g = torch.Generator().manual_seed(1)
+    small = torch.randint(0, 256, (2, 8, 8, 3), dtype=torch.uint8, generator=g)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"patches": small})
+    got = np.load(tmp_path / "a" / "patches.npy")
+    assert shapes == {"patches": [2, 8, 8, 3]} and got.dtype == np.float32 and np.array_equal(got, small.numpy().astype(np.float32))
+    big = torch.randint(0, 256, (16, 32, 32, 3), dtype=torch.uint8, generator=g)
+    limit = 4 * 32 * 32 * 3 * 5 + 100  # room for 5 stamps
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"patches": big}, limit_bytes=limit)
+    b, c = np.load(tmp_path / "b" / "patches.npy"), np.load(tmp_path / "c" / "patches.npy")
+    assert b.dtype == np.float32 and b.shape == (5, 32 * 32 * 3) and b.nbytes <= limit and np.array_equal(b, c)
+    rows = big.reshape(16, -1).numpy().astype(np.float32)
+    assert all(any(np.array_equal(r, s) for s in rows) for r in b)  # whole stamps, unchanged
+    huge = bench.sample_output(big, 1000)
+    assert huge.dtype == torch.float32 and huge.numel() <= 1000 and torch.equal(huge, bench.sample_output(big, 1000))
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
