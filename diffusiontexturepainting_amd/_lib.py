@@ -34,7 +34,7 @@ PROF_KINDS = [f"gemm_kernel<{_SHAPES[i & 3][0]}, {_SHAPES[i & 3][1]}, {2 + i // 
     [f"gemm_kernel<{_SHAPES[i & 3][0]}, {_SHAPES[i & 3][1]}, 3, 1, {(4, 8)[i // 4]}>" for i in range(8)] + \
     ["xattn_kernel (cross-attention GEMM pair)", "conv_halo_kernel<8, 8, 64, 3 images>", "conv_halo_kernel<8, 8, 128, 3 images>",
      "lnlin_kernel (activation-stationary LayerNorm-folded Linear / GEGLU)", "convws_kernel<8, 8, 3 images>", "convws_kernel<16, 16>", "convws_kernel<8, 16, 2 n-tiles>", "convws_kernel<8, 16, 2 n-tiles, 2 workgroups per CU>",
-     "gemmws_kernel (weight-streaming dense GEMM)"]
+     "gemmws_kernel (weight-streaming dense GEMM)", "gemm_f8f8_kernel (two-operand e4m3 GEMM)", "quant8_kernel (e4m3 quantise pass)"]
 
 
 class GemmDesc(C.Structure):
@@ -48,7 +48,9 @@ class GemmDesc(C.Structure):
                 ("batch", C.c_int), ("a_bs", C.c_int64), ("w_bs", C.c_int64), ("c_bs", C.c_int64), ("r_bs", C.c_int64),
                 ("bias_bs", C.c_int), ("lns_bs", C.c_int), ("sm_valid", C.c_int),
                 ("st_out", C.c_void_p), ("st_in", C.c_void_p), ("st_parts", C.c_int), ("st_parts_out", C.c_int),
-                ("W8", C.c_void_p), ("ldw8", C.c_int), ("a_scale", C.c_float), ("w_scale", C.c_float), ("gn_cpg", C.c_int), ("Wfr", C.c_void_p)]
+                ("W8", C.c_void_p), ("ldw8", C.c_int), ("a_scale", C.c_float), ("w_scale", C.c_float), ("gn_cpg", C.c_int), ("Wfr", C.c_void_p),
+                ("A8", C.c_void_p), ("lda8", C.c_int), ("A2_8", C.c_void_p), ("lda2_8", C.c_int), ("C8", C.c_void_p), ("ldc8", C.c_int),
+                ("c_scale", C.c_float), ("a2_scale", C.c_float)]
 
 
 GF_BIAS, GF_BIAS_M, GF_RESID, GF_GEGLU, GF_GELU, GF_QUICKGELU, GF_OUT_F32, GF_SILU, GF_LNFOLD = 1, 2, 4, 8, 64, 128, 256, 512, 1024
@@ -85,6 +87,8 @@ SYMBOLS = {
     "dtp_set_option": (_i, [_vp, C.c_char_p, _i]),
     "dtp_last_stamp_finite": (_i, [_vp, C.POINTER(_i)]),
     "dtp_op_gemm": (_i, [C.POINTER(GemmDesc), _vp]),
+    "dtp_op_gemm_f8f8": (_i, [C.POINTER(GemmDesc), _vp]),
+    "dtp_op_quant_e4m3": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _vp, _i, _vp, _i, _i, _f, _i, _i, _vp, _i, _f, _vp]),
     "dtp_op_pack_linear": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "dtp_op_pack_conv": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dtp_op_rowsum": (_i, [_vp, _i, _i, _vp, _i, _vp]),

@@ -118,6 +118,39 @@ int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s) {
   return dtp_launch_gemm(p, tile, (hipStream_t)s);
 }
 
+int dtp_op_gemm_f8f8(dtp_gemm_desc* d, dtp_stream s) {
+  std::lock_guard<std::mutex> lk(g_ops_mu);
+  int rc = ops_init();
+  if (rc) return rc;
+  static bool f8f8_init = false;
+  if (!f8f8_init) { dtp_gemm_f8f8_init(); f8f8_init = true; }
+  GemmParams p = {};
+  p.A8 = (const unsigned char*)d->A8; p.lda8 = d->lda8;
+  p.A2_8 = (const unsigned char*)d->A2_8; p.lda2_8 = d->lda2_8; p.Cin2 = d->A2_8 ? d->Cin2 : 0;
+  p.W8 = (const unsigned char*)d->W8; p.ldw8 = d->ldw8;
+  p.C = d->C; p.ldc = d->ldc; p.C8 = (unsigned char*)d->C8; p.ldc8 = d->ldc8;
+  p.bias = d->bias; p.R = (const f16*)d->R; p.ldr = d->ldr;
+  p.zero = g_ops.zero;
+  p.M = d->M; p.N = d->N; p.K = d->K;
+  p.flags = d->flags;
+  p.st_out = d->st_out;
+  p.a_scale = d->a_scale; p.w_scale = d->w_scale; p.c_scale = d->c_scale; p.a2_scale = d->a2_scale;
+  p.splits = 1;
+  const int tile = d->tile >= 0 ? d->tile : dtp_gemm_f8f8_pick(p, g_ops.num_cu);
+  if (p.flags & GF_ROWSTATS) d->st_parts_out = (p.N + 127) / 128;
+  return dtp_launch_gemm_f8f8(p, tile, (hipStream_t)s);
+}
+
+int dtp_op_quant_e4m3(const void* x, int ldx, void* y, int ldy, int K, float scale, int ln, const void* x2, int ldx2, void* y2, int ldy2,
+                      int K2, float scale2, int ln2, int M, const float* st_in, int st_parts, float eps, dtp_stream s) {
+  Quant8Params q = {};
+  q.M = M; q.njobs = x2 ? 2 : 1;
+  q.job[0] = Quant8Job{(const f16*)x, ldx, K, (unsigned char*)y, ldy, scale, ln};
+  if (x2) q.job[1] = Quant8Job{(const f16*)x2, ldx2, K2, (unsigned char*)y2, ldy2, scale2, ln2};
+  q.st_in = st_in; q.st_parts = st_parts; q.st_rows = M; q.eps = eps;
+  return dtp_launch_quant8(q, (hipStream_t)s);
+}
+
 int dtp_op_pack_linear(const float* w, void* out, int N, int K, int ldw, int geglu, dtp_stream s) {
   std::lock_guard<std::mutex> lk(g_ops_mu);
   int rc = ops_init();

@@ -304,7 +304,41 @@ struct GemmParams {
   // enqueue time, i.e. before graph capture); amax_slot1 - 1 = its slot in the context's amax table (0: none)
   const float* a_scale_host;
   int amax_slot1;
+  // two-operand e4m3 GEMM (gemm_f8f8.hip): A8 = e4m3(A / a_scale) [M][lda8] bytes, A2_8 the same for the A2 columns (one scale for
+  // both unless a2_scale is set); C8 (or null) = e4m3(out / c_scale) [M][ldc8] next to / instead of the fp16 C
+  const unsigned char* A8;
+  int lda8;
+  const unsigned char* A2_8;
+  int lda2_8;
+  unsigned char* C8;
+  int ldc8;
+  float c_scale;
+  float a2_scale;  // scale of A2_8 (0 = a_scale); another power of two needs (K - Cin2) % 128 == 0: applied as the MFMA's E8M0 block scale
 };
+
+// ---------------------------------------------------------------- e4m3 activation operands (gemm_f8f8.hip)
+// quantise pass: up to two row-parallel jobs over the same M rows; job j writes y = e4m3(x / scale) or, with ln, e4m3(LN(x) / scale)
+// where LN(x) = (x - mean) * rstd (no gamma / beta) from the producer's row-statistic partials st_in [st_parts][st_rows][2] (null:
+// computed here).  Values beyond +-448 * scale saturate.
+struct Quant8Job {
+  const f16* x; int ld, K;
+  unsigned char* y; int ldy;
+  float scale;
+  int ln;
+};
+struct Quant8Params {
+  int M, njobs;
+  Quant8Job job[2];
+  const float* st_in; int st_parts, st_rows;
+  float eps;
+};
+bool dtp_quant8_supported(const Quant8Params& q);
+int dtp_launch_quant8(const Quant8Params& q, hipStream_t s);
+// tile: 0 = 128x128, 1 = 64x128 (M x N), four waves each; -1 = heuristic (dtp_gemm_f8f8_pick)
+bool dtp_gemm_f8f8_supported(const GemmParams& p);
+int dtp_gemm_f8f8_pick(const GemmParams& p, int num_cu);
+int dtp_launch_gemm_f8f8(const GemmParams& p, int tile, hipStream_t s);
+void dtp_gemm_f8f8_init();
 
 // K-slices pinned to XCDs.  Block b of a launch runs on XCD b % 8 and every XCD has its own L2: with the split index on grid.z the
 // tiles of one K-slice are spread over all XCDs, so each slice's operand panels are fetched from the Infinity Cache / HBM into up to

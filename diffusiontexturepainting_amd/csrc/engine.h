@@ -48,12 +48,24 @@ struct T {
   long long rows() const { return (long long)B * H * W; }
 };
 
+// e4m3 view [rows][ld] bytes (option fp8_operands): value = byte * scale, scale = *scale_host when calibrated (read at enqueue time,
+// like every fp8 scale), `scale` otherwise; amax_slot1 - 1 = the calibration slot its producer measures into (0: fixed scale)
+struct T8 {
+  unsigned char* p = nullptr;
+  int B = 0, H = 0, W = 0, C = 0, ld = 0;
+  const float* scale_host = nullptr;
+  float scale = 1.f;
+  int amax_slot1 = 0;
+  long long rows() const { return (long long)B * H * W; }
+  float now() const { return scale_host ? *scale_host : scale; }
+};
+
 struct Ctx;
 
 // A launch program: a flat list of closures bound to statically planned buffers.
 using Op = std::function<int(hipStream_t, int /*step*/)>;
 // profiling classes (dtp_profile_rows): 0-11 = gemm_kernel<BM,BN,NS> variants (id = shape + 4*(NS-2)), then the rest
-enum { PK_GEMM0 = 0, PK_ATTN = 12, PK_GN = 13, PK_LN = 14, PK_ELEM = 15, PK_SOFTMAX = 16, PK_HALO0 = 17, PK_BIG0 = 21, PK_WIDE0 = 25, PK_FP8 = 27, PK_KH2 = 28, PK_LW = 36, PK_XATTN = 44, PK_HALO3 = 45, PK_LNLIN = 47, PK_WS0 = 48, PK_GEMMWS = 52, PK_COUNT = 53 };
+enum { PK_GEMM0 = 0, PK_ATTN = 12, PK_GN = 13, PK_LN = 14, PK_ELEM = 15, PK_SOFTMAX = 16, PK_HALO0 = 17, PK_BIG0 = 21, PK_WIDE0 = 25, PK_FP8 = 27, PK_KH2 = 28, PK_LW = 36, PK_XATTN = 44, PK_HALO3 = 45, PK_LNLIN = 47, PK_WS0 = 48, PK_GEMMWS = 52, PK_F8F8 = 53, PK_QUANT8 = 54, PK_COUNT = 55 };
 struct ProfRec {
   int kind;
   double flops, bytes;
@@ -154,6 +166,7 @@ struct Fp8Cal {
 constexpr int DTP_FP8_SLOTS = 2048;
 constexpr float DTP_FP8_LN_A_SCALE = 0.125f;  // LayerNorm'd operands: |x| <= sqrt(K - 1) < 36 -> x * 8 < 448 never clips, three more octaves above the subnormals
 constexpr float DTP_FP8_MARGIN = 2.0f;        // head-room over the calibration evaluation's absolute maximum
+constexpr int DTP_FP8_OPERANDS_MIN_K = 1280;  // option fp8_operands: transformer Linears with K >= this contract two e4m3 operands (gemm_f8f8.hip)
 
 struct UNetProg {
   int N = 0;          // UNet batch (3B or 2B)
@@ -267,6 +280,7 @@ struct Ctx {
   bool pack_ws = false;           // load_conv also builds the fragment-order packing (set while the UNet's weights load; $DTP_NO_WS=1: never)
   bool fp8_linear = false;        // UNet transformer Linears / 1x1 convs on the fp8 MX MFMA (configs[4]); fixed once a UNet program exists
   bool fp8_attention = false;     // UNet self-attention on the fp8 MX MFMA (BASELINE configs[4]); fixed once a UNet program exists
+  bool fp8_operands = false;      // transformer Linears with K >= DTP_FP8_OPERANDS_MIN_K on e4m3 activations in memory (gemm_f8f8.hip); fixed once a UNet program exists
   std::deque<float> fp8_scales;   // host copies of the calibrated scales (stable addresses: the ops read them at enqueue time)
   std::deque<Fp8Cal> fp8_cals;
   unsigned int* fp8_amax = nullptr;  // device: DTP_FP8_SLOTS float bit patterns
@@ -326,6 +340,7 @@ struct Builder {
   Ctx* c;
   Prog* prog;
   bool fp8 = false;  // dense Linears pushed through linear() / the transformer tail run on gemm_fp8_kernel when they can
+  bool f8ops = false;  // option fp8_operands: transformer() routes its K >= DTP_FP8_OPERANDS_MIN_K Linears through quant8 / linear8
   // append an op; when profiling is on, every launch is bracketed by HIP events on its own stream
   void push(int kind, double flops, double bytes, Op fn, const std::string& label = std::string());
   T alloc(int B, int H, int W, int C);
@@ -345,6 +360,12 @@ struct Builder {
             const T* dst = nullptr);  // dst: write into this (possibly strided) view instead of a fresh buffer
   int linear(const T& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit = nullptr, const RowStats* use = nullptr,
              const T* dst = nullptr);
+  // option fp8_operands: an e4m3 tensor from the pool shaped like `like` with C columns and a calibrated (a new calibration slot) or
+  // fixed scale; the quantise pass x -> y (ln: (x - mean) * rstd with the statistics `st` when they cover x); a Linear over the e4m3 x
+  T8 alloc8(const T& like, int C, bool calibrated, float fixed_scale = 1.f);
+  void release8(const T8& t);
+  int quant8(const T& x, const T8& y, bool ln, const RowStats* st);
+  int linear8(const T8& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit);
   int alloc_stats(long long rows, int C, RowStats& st);  // room for one partial per 64-column tile
   void release_stats(RowStats& st);
   int attention(const T& q, const T& k, const T& v, int heads, int Sq, int Skv, int Bn, T& o);

@@ -1179,6 +1179,75 @@ int Builder::linear(const T& x, const ConvW& w, const T* resid, int flags, T& y,
   return push_gemm(c, prog, p, -1, (double)w.K, (emit && emit->buf) ? emit : nullptr);
 }
 
+// ---------------------------------------------------------------- option fp8_operands: e4m3 activations in memory (gemm_f8f8.hip)
+T8 Builder::alloc8(const T& like, int C, bool calibrated, float fixed_scale) {
+  T8 t;
+  t.B = like.B; t.H = like.H; t.W = like.W; t.C = C; t.ld = (C + 15) & ~15;
+  void* p = nullptr;
+  if (ctx_pool_get(c, (size_t)t.rows() * t.ld, &p) != DTP_OK) p = nullptr;
+  t.p = (unsigned char*)p;
+  t.scale = fixed_scale;
+  if (calibrated) {
+    t.scale_host = fp8_new_linear_scale(c, &t.amax_slot1);
+    if (!t.scale_host) t.scale = DTP_FP8_LN_A_SCALE * 8.0f;  // calibration slots used up: the default scale of fp8_linear
+  }
+  return t;
+}
+void Builder::release8(const T8& t) { ctx_pool_put(c, t.p); }
+
+int Builder::quant8(const T& x, const T8& y, bool ln, const RowStats* st) {
+  if (!y.p) return DTP_ERR_HIP;
+  if (x.C != y.C || x.rows() != y.rows()) { dtp_set_error("quant8: shape mismatch"); return DTP_ERR_ARG; }
+  Quant8Params q = {};
+  q.M = (int)x.rows(); q.njobs = 1; q.eps = 1e-5f;
+  q.job[0] = Quant8Job{x.p, x.ld, x.C, y.p, y.ld, y.scale, ln ? 1 : 0};
+  if (ln && st && st->buf && st->parts > 0 && st->M == q.M) { q.st_in = st->buf; q.st_parts = st->parts; q.st_rows = q.M; }
+  if (!dtp_quant8_supported(q)) { dtp_set_error("quant8: unsupported problem (M %d, K %d)", q.M, x.C); return DTP_ERR_ARG; }
+  const T8 ya = y;
+  Ctx* cc = c;
+  push(PK_QUANT8, 0.0, 3.0 * q.M * x.C, [=](hipStream_t s, int) -> int {
+    Quant8Params r = q;
+    r.job[0].scale = ya.now();
+    if (cc->calibrating && ya.amax_slot1 > 0 && !ln)  // a raw operand with a calibrated scale: measure it once
+      RC(dtp_launch_amax_f16(r.job[0].x, r.M, r.job[0].K, r.job[0].ld, cc->fp8_amax + ya.amax_slot1 - 1, s));
+    return dtp_launch_quant8(r, s);
+  }, "quant8 M=" + std::to_string(q.M) + " K=" + std::to_string(x.C) + (ln ? " ln" : ""));
+  return DTP_OK;
+}
+
+int Builder::linear8(const T8& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit) {
+  if (x.C != w.K || w.taps != 1 || !w.w8) { dtp_set_error("linear8: operand mismatch (K %d vs %d)", x.C, w.K); return DTP_ERR_ARG; }
+  const int n_out = (flags & GF_GEGLU) ? w.cout / 2 : w.cout;
+  GemmParams p = {};
+  p.A8 = x.p; p.lda8 = x.ld;
+  p.W8 = w.w8; p.ldw8 = w.ldw8; p.w_scale = w.w8_scale;
+  p.M = (int)x.rows(); p.N = w.cout; p.K = x.C;
+  p.flags = flags;
+  p.zero = c->zero; p.splits = 1;
+  p.a_scale = x.scale; p.a_scale_host = x.scale_host;  // (the producer of x measured its range: no amax slot here)
+  y = alloc(x.B, x.H, x.W, n_out);
+  if (!y.p) return DTP_ERR_HIP;
+  p.C = y.p; p.ldc = y.ld;
+  if (w.b) { p.flags |= GF_BIAS; p.bias = w.b; }
+  if (resid) { p.flags |= GF_RESID; p.R = resid->p; p.ldr = resid->ld; }
+  if (emit && emit->buf) {
+    p.flags |= GF_ROWSTATS; p.st_out = emit->buf;
+    emit->parts = (p.N + 127) / 128; emit->M = p.M;
+  }
+  if (!dtp_gemm_f8f8_supported(p)) { dtp_set_error("linear8: unsupported problem (M %d N %d K %d)", p.M, p.N, p.K); return DTP_ERR_ARG; }
+  const int tile = dtp_gemm_f8f8_pick(p, c->num_cu);
+  char lab[160];
+  snprintf(lab, sizeof(lab), "f8f8 M=%d N=%d K=%d tile=%d%s", p.M, p.N, p.K, tile, (flags & GF_GEGLU) ? " geglu" : "");
+  // algorithmic work: 2*M*N*K; bytes = both e4m3 operands once + the fp16 output once
+  const double bytes = (double)p.M * p.K + (double)p.N * p.K + 2.0 * p.M * n_out;
+  push(PK_F8F8, 2.0 * p.M * (double)p.N * p.K, bytes, [=](hipStream_t s, int) -> int {
+    GemmParams q = p;
+    if (p.a_scale_host) q.a_scale = *p.a_scale_host;
+    return dtp_launch_gemm_f8f8(q, tile, s);
+  }, lab);
+  return DTP_OK;
+}
+
 int Builder::attention(const T& q, const T& k, const T& v, int heads, int Sq, int Skv, int Bn, T& o) {
   o = alloc(Bn, 1, Sq, q.C);
   if (!o.p) return DTP_ERR_HIP;

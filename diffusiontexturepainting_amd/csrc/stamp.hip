@@ -336,6 +336,7 @@ int dtp_finalize_weights(dtp_ctx* ctx) {
   dtp_conv_halo_init();
   dtp_gemm_wide_init();
   dtp_gemm_fp8_init();
+  dtp_gemm_f8f8_init();
   dtp_xattn_init();
   dtp_lnlin_init();
   dtp_xchain_init();
@@ -494,7 +495,7 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   }
   HIP_CHECK(hipEventRecord(c->ev[1], s));
   // fp8 (configs[4]): the first stamp of a program measures its activation ranges once, before the loop is captured
-  if ((c->fp8_linear || c->fp8_attention)) {
+  if ((c->fp8_linear || c->fp8_attention || c->fp8_operands)) {
     if (u3 && !u3->fp8_calibrated) RC(fp8_calibrate(c, u3, s, 0));
     if (u2 && !u2->fp8_calibrated) {
       if (tg_evals > 0)  // (u2 is not the first program:) its input is normally assembled where the loop switches programs: do it now, from the initial latents
@@ -639,6 +640,14 @@ int dtp_set_option(dtp_ctx* ctx, const char* name, int value) {
       return DTP_ERR_STATE;
     }
     c->fp8_linear = value != 0;
+    return DTP_OK;
+  }
+  if (!strcmp(name, "fp8_operands")) {
+    if (!c->unet_progs.empty() && c->fp8_operands != (value != 0)) {
+      dtp_set_error("dtp_set_option: fp8_operands must be chosen before the first UNet program is built");
+      return DTP_ERR_STATE;
+    }
+    c->fp8_operands = value != 0;
     return DTP_OK;
   }
   if (!strcmp(name, "fp8_attention")) {

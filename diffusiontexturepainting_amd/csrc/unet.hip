@@ -202,7 +202,18 @@ static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up,
     RC(b.linear(t, w.proj_in, nullptr, 0, y, &st1));
     b.release(t);
   }
-  RC(b.linear(y, w.qkv, nullptr, 0, qkv, nullptr, &st1));  // LN1 folded
+  // option fp8_operands: q/k/v, to_out and FF1 with K >= DTP_FP8_OPERANDS_MIN_K (the C = 1280 blocks; no de-duplicated prefix reaches them)
+  // contract two e4m3 operands (gemm_f8f8.hip).  A LayerNorm'd operand is quantised AFTER the normalisation (fixed scale; gamma / beta stay
+  // folded into the packed weights / bias, so its consumer is a plain GF_BIAS GEMM); the attention output gets a calibrated scale.
+  const bool f8 = b.f8ops;
+  if (f8 && w.qkv.K >= DTP_FP8_OPERANDS_MIN_K && w.qkv.w8) {
+    T8 y8 = b.alloc8(y, C, false, DTP_FP8_LN_A_SCALE);
+    RC(b.quant8(y, y8, true, &st1));
+    RC(b.linear8(y8, w.qkv, nullptr, 0, qkv, nullptr));
+    b.release8(y8);
+  } else {
+    RC(b.linear(y, w.qkv, nullptr, 0, qkv, nullptr, &st1));  // LN1 folded
+  }
   b.release_stats(st1);
   T q = qkv, k = qkv, v = qkv;
   q.C = k.C = v.C = C;
@@ -279,6 +290,11 @@ static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up,
     for (int i = 0; i < cs.n; ++i) bytes += 2.0 * cs.rows[i] * cs.row_bytes[i];
     b.push(PK_ELEM, 0.0, bytes, [=](hipStream_t s, int) { return dtp_launch_copy_rows(cs, s); }, "dup uncond<-cond rows=" + std::to_string(rB));
     xin = dup->x_full;
+  } else if (f8 && w.out1.K >= DTP_FP8_OPERANDS_MIN_K && w.out1.w8) {
+    T8 a8 = b.alloc8(a, C, true);  // the attention output: calibrated
+    RC(b.quant8(a, a8, false, nullptr));
+    RC(b.linear8(a8, w.out1, &y, 0, y2, &st2));
+    b.release8(a8);
   } else {
     RC(b.linear(a, w.out1, &y, 0, y2, &st2));
   }
@@ -375,8 +391,18 @@ static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up,
       return DTP_OK;
     }
   }
-  RC(b.linear(y3, w.ff1, nullptr, GF_GEGLU, f, nullptr, &st3));  // LN3 folded
-  b.release_stats(st3);
+  if (f8 && w.ff1.K >= DTP_FP8_OPERANDS_MIN_K && w.ff1.w8) {  // FF1 (C = 1280) on the LayerNorm-3'd e4m3 copy of y3
+    const T8 y3n = b.alloc8(y3, C, false, DTP_FP8_LN_A_SCALE);
+    RC(b.quant8(y3, y3n, true, &st3));
+    b.release_stats(st3);
+    RC(b.linear8(y3n, w.ff1, nullptr, GF_GEGLU, f, nullptr));
+    b.release8(y3n);
+  } else {
+    RC(b.linear(y3, w.ff1, nullptr, GF_GEGLU, f, nullptr, &st3));  // LN3 folded
+    b.release_stats(st3);
+  }
+  // (fp8_operands leaves the merged GEMM below in fp16 although its K is 1600 .. 6400: its A2 operand y3 is the residual stream, and
+  // rounding THAT to e4m3 costs 2.6e-2 of pixel error on its own -- measured by emulation in the fp32 oracle)
   // ff.net.2 (+ y3) and proj_out (+ x) are two Linears with only a residual add between them: one GEMM over [f | y3]
   // with the merged weights [Wp W2 | Wp] (load_linear_pair) -- no y4 tensor, one launch fewer per block
   {
@@ -482,9 +508,21 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
     // the quantise kernels run on the null stream, the program on the caller's (non-blocking) stream: order them once, here
     HIP_CHECK(hipDeviceSynchronize());
   }
+  if (c->fp8_operands) {  // e4m3 copies of the Linears fp8_operands covers (transformer(): q/k/v, to_out, FF1 with K >= DTP_FP8_OPERANDS_MIN_K)
+    UNetW& uw = c->unet;
+    std::vector<XfW*> all;
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j) all.push_back(&uw.down_xf[i][j]);
+    all.push_back(&uw.mid_xf);
+    for (int i = 1; i < 4; ++i) for (int j = 0; j < 3; ++j) all.push_back(&uw.up_xf[i][j]);
+    for (XfW* x : all)
+      for (ConvW* w : {&x->qkv, &x->out1, &x->ff1})
+        if (w->K >= DTP_FP8_OPERANDS_MIN_K) RC(ensure_w8(c, *w));
+    HIP_CHECK(hipDeviceSynchronize());  // (null-stream quantise kernels before the caller's stream, as above)
+  }
   up.cal_begin = c->fp8_cals.size();
   Builder b{c, &up.main};
   b.fp8 = c->fp8_linear;
+  b.f8ops = c->fp8_operands;
   T x0;
   x0.p = up.in16; x0.B = N; x0.H = h; x0.W = h; x0.C = 16; x0.ld = 16;
   // Zero-copy skip connections: every up-path ResBlock consumes cat([x, skip], C).  The 12 concat buffers are

@@ -20,7 +20,8 @@ DEFAULT_SETTINGS = dict(steps=20, context_pad=150, tg_steps=20, cfg_weight=2.0, 
 
 
 class MI355ConditionalInpainter(ConditionalInpainterBase):
-    def __init__(self, resolution, device=0, weights="synthetic", max_batch=1, seed=42, use_graph=True, fp8_attention=None, fp8_linear=None):
+    def __init__(self, resolution, device=0, weights="synthetic", max_batch=1, seed=42, use_graph=True, fp8_attention=None, fp8_linear=None,
+                 fp8_operands=None):
         """weights: "synthetic" (seeded random tensors with the real shapes -- no checkpoints can be
         downloaded in this environment) or a dict {unet, vae, [lora], [clip], [penc]} of
         {diffusers key: tensor} state dicts (see weights.load_checkpoint_file)."""
@@ -63,6 +64,11 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.fp8_linear = bool(fp8_linear)
         if self.fp8_linear:  # ... and its transformer Linears / 1x1 convs
             check(self._lib.dtp_set_option(self._h, b"fp8_linear", 1), "dtp_set_option(fp8_linear)")
+        if fp8_operands is None:
+            fp8_operands = os.environ.get("DTP_FP8_OPERANDS", "0") not in ("", "0")
+        self.fp8_operands = bool(fp8_operands)
+        if self.fp8_operands:  # PARITY-ONLY: transformer Linears with K >= 1280 on e4m3 activations in memory (before any program is built)
+            check(self._lib.dtp_set_option(self._h, b"fp8_operands", 1), "dtp_set_option(fp8_operands)")
         # noise: seeded once, never reseeded (trt_model.py:54, stable_diffusion_pipeline.py:154-156)
         self.generator = torch.Generator(device=self._device).manual_seed(seed)
         self.stream = torch.cuda.Stream(device=self._device)

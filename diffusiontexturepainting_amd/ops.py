@@ -89,6 +89,64 @@ def quantize_w8(wp, k):
     return out, sc.value
 
 
+def quant_e4m3(x, scale, ln=False, stats_in=None, eps=1e-5, k=None, x2=None, scale2=1.0, ln2=False, k2=None):
+    """fp16 rows x [M, >=k] -> e4m3 bytes (torch.uint8) [M, k] = e4m3(x / scale), saturating at +-448; ln=True first applies the
+    LayerNorm (x - mean) * rstd (no gamma / beta) with the producer's per-row partials stats_in f32 [parts, M, 2] (None: computed
+    in-kernel).  x2 (or None): a second job over the same rows in the same launch; then returns both outputs."""
+    lib = _lib.load()
+    m = x.shape[0]
+    k = k or x.shape[1]
+    y = torch.empty(m, k, dtype=torch.uint8, device=x.device)
+    y2 = None
+    if x2 is not None:
+        k2 = k2 or x2.shape[1]
+        y2 = torch.empty(m, k2, dtype=torch.uint8, device=x.device)
+    st = stats_in.contiguous() if stats_in is not None else None
+    check(lib.dtp_op_quant_e4m3(ptr(x), x.stride(0), ptr(y), y.stride(0), k, float(scale), int(ln),
+                                ptr(x2), x2.stride(0) if x2 is not None else 0, ptr(y2), y2.stride(0) if y2 is not None else 0,
+                                k2 or 0, float(scale2), int(ln2), m, ptr(st), st.shape[0] if st is not None else 0, eps, _stream()),
+          "quant_e4m3")
+    return (y, y2) if x2 is not None else y
+
+
+def gemm_f8f8(a8, w8, n, a_scale, w_scale, k=None, bias=None, resid=None, flags=0, tile=-1, tail8=None, row_stats=False,
+              out8_scale=None, out16=True, tail_scale=None):
+    """Both operands e4m3 (torch.uint8): a8 [M, >=k] = e4m3(A / a_scale), w8 [rows, ldw8] from quantize_w8 (scale w_scale);
+    tail8 (or None): e4m3 [M, K2] supplying the last K2 columns (scale tail_scale, default a_scale).  Returns the f16 output [M, N] (or [M, N/2] with
+    GEGLU; None with out16=False), the e4m3 output (out8_scale given: e4m3(out / out8_scale)) and, with row_stats, the partials."""
+    lib = _lib.load()
+    m = a8.shape[0]
+    k = k or a8.shape[1]
+    n_out = n // 2 if flags & GF_GEGLU else n
+    d = GemmDesc()
+    out = torch.empty(m, n_out, dtype=torch.float16, device=a8.device) if out16 else None
+    out8 = torch.empty(m, n_out, dtype=torch.uint8, device=a8.device) if out8_scale is not None else None
+    d.A8, d.lda8 = a8.data_ptr(), a8.stride(0)
+    d.W8, d.ldw8, d.a_scale, d.w_scale = w8.data_ptr(), w8.stride(0), a_scale, w_scale
+    d.C, d.ldc = (out.data_ptr(), out.stride(0)) if out is not None else (None, 0)
+    if out8 is not None:
+        d.C8, d.ldc8, d.c_scale = out8.data_ptr(), out8.stride(0), out8_scale
+    d.bias = bias.data_ptr() if bias is not None else None
+    d.R = resid.data_ptr() if resid is not None else None
+    d.ldr = resid.stride(0) if resid is not None else 0
+    d.M, d.N, d.K = m, n, k
+    d.flags = flags | (GF_BIAS if bias is not None else 0) | (GF_RESID if resid is not None else 0)
+    d.tile = tile
+    if tail8 is not None:
+        d.A2_8, d.lda2_8, d.Cin2 = tail8.data_ptr(), tail8.stride(0), tail8.shape[1]
+        d.a2_scale = tail_scale or 0.0
+        d.K = k + tail8.shape[1]
+    st = None
+    if row_stats:
+        st = torch.zeros((n + 127) // 128, m, 2, dtype=torch.float32, device=a8.device)
+        d.st_out = st.data_ptr()
+        d.flags |= _lib.GF_ROWSTATS
+    check(lib.dtp_op_gemm_f8f8(C.byref(d), _stream()), "gemm_f8f8")
+    if row_stats:
+        st = st[:d.st_parts_out]
+    return out, out8, st
+
+
 def gemm(a, wp, n, k=None, bias=None, resid=None, flags=0, tile=-1, splits=0, out=None, lda=None, lns=None, ln_eps=1e-5, batch=0,
          sm_valid=0, bias_shared=False, tail=None, row_stats=False, stats_in=None, w8=None, w_scale=1.0, a_scale=1.0, layernorm=False,
          wfr=None):

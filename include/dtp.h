@@ -129,7 +129,8 @@ int dtp_last_stamp_info(dtp_ctx* ctx, int* unet_evals, int* graph_nodes);
  * waves), 44 = xattn_kernel (fused cross-attention GEMM pair), 45-46 = conv_halo_kernel<8,8,64|128> with three images per workgroup,
  * 47 = lnlin_kernel (activation-stationary LayerNorm-folded Linear / GEGLU), 48-51 = convws_kernel (weight-streaming 3x3 conv:
  * three 8x8 images / one 16x16 image / an 8x16 pixel tile x 64 channels per workgroup / the same for two workgroups per CU),
- * 52 = gemmws_kernel (weight-streaming dense GEMM; DTP_EXPERIMENTAL=1 builds only).  flops/bytes are ALGORITHMIC (unpadded 2*M*N*K; each operand once in fp16).
+ * 52 = gemmws_kernel (weight-streaming dense GEMM; DTP_EXPERIMENTAL=1 builds only), 53 = gemm_f8f8_kernel (two-operand e4m3 GEMM, option
+ * "fp8_operands"; labels "f8f8 M=.. N=.. K=.."), 54 = quant8_kernel (its e4m3 quantise pass; labels "quant8 M=.. K=..").  flops/bytes are ALGORITHMIC (unpadded 2*M*N*K; each operand once in fp16).
  * dtp_profile(ctx, 0) switches back to graph replay.  The nvtx/cudaEvent hooks of
  * stable_diffusion_pipeline.py:146-149,486-503 are the reference counterpart. */
 typedef struct { int kind; int launches; double ms; double flops; double bytes; } dtp_prof_row;
@@ -146,7 +147,12 @@ int dtp_profile_dump(dtp_ctx* ctx, const char* path);
  * performance path: every fp8 operand carries a calibrated power-of-two scale (an amax pass over the first evaluation of a launch
  * program, before it is captured; weights per tensor at load time) and the 256^2 / 8-step stamp stays inside the 1e-2 pixel gate on
  * both synthetic weight sets, but in three rounds of measurements it was never faster than fp16 on this chip: the
- * activations arrive in fp16 and are converted on the way into LDS.  "fuse_gn_conv" exists only in DTP_EXPERIMENTAL=1 builds. */
+ * activations arrive in fp16 and are converted on the way into LDS.  "fp8_operands" (default 0; choose before the first UNet program is
+ * built, DTP_ERR_STATE after): q/k/v, attn1.to_out and the GEGLU ff.net.0 of the C = 1280 transformer blocks (every Linear with K >= 1280
+ * except proj_in and the merged ff.net.2 / proj_out) contract two e4m3 operands on gemm_f8f8_kernel: the activation is written as e4m3 by
+ * a quantise pass (LayerNorm'd first, fixed scale; to_out's input with a calibrated scale); takes precedence over "fp8_linear" there.
+ * PARITY-ONLY as well: inside the 1e-2 pixel gate (6.4e-3 at 64^2 x 8), but 0.9 % SLOWER at batch 8 and 1.8 % at batch 1 than fp16
+ * (profiles/fp8_operands_ab.txt).  "fuse_gn_conv" exists only in DTP_EXPERIMENTAL=1 builds. */
 int dtp_set_option(dtp_ctx* ctx, const char* name, int value);
 /* *finite = 1 if the last stamp (run with "check_finite" on) produced only finite values, 0 otherwise.  Blocks until that
  * stamp has finished; DTP_ERR_STATE if the option was off. */
@@ -206,12 +212,35 @@ typedef struct {
                         receives f32 [images][2 * (Ho/8) * (Wo/16)][N / gn_cpg][2] partial (sum, sum of squares) of the rounded outputs,
                         the input of dtp_op_groupnorm_apply */
   const void* Wfr;   /* 3x3 conv, tiles 51 .. 54: the weights in MFMA fragment order (dtp_op_pack_conv_ws); dense, tile 55: dtp_op_pack_linear_ws */
+  /* dtp_op_gemm_f8f8 only (both operands e4m3 in memory): */
+  const void* A8;    /* e4m3 activations [M][lda8] bytes = e4m3(A / a_scale) (dtp_op_quant_e4m3) */
+  int lda8;
+  const void* A2_8;  /* or NULL: e4m3 [M][lda2_8] supplying the LAST Cin2 columns of the contraction (same a_scale) */
+  int lda2_8;
+  void* C8;          /* or NULL: e4m3 output [M][ldc8] = e4m3(out / c_scale), quantised from the fp16-rounded output; C may then be NULL */
+  int ldc8;
+  float c_scale;
+  float a2_scale;    /* scale of A2_8 (0 = a_scale); a different power of two needs (K - Cin2) % 128 == 0 */
 } dtp_gemm_desc;
 enum { DTP_GF_BIAS = 1, DTP_GF_BIAS_M = 2, DTP_GF_RESID = 4, DTP_GF_GEGLU = 8, DTP_GF_GELU = 64, DTP_GF_QUICKGELU = 128,
        DTP_GF_OUT_F32 = 256, DTP_GF_SILU = 512, DTP_GF_LNFOLD = 1024, DTP_GF_ROWSTATS = 2048, DTP_GF_SOFTMAX16 = 4096,
        DTP_GF_GNSTATS = 1 << 24 };
 
 int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s);
+/* Two-operand e4m3 GEMM (gemm_f8f8_kernel; option "fp8_operands" runs it): C = epilogue(a_scale * w_scale * A8 . W8^T) with A8 / A2_8 / W8
+ * (d->W8, d->ldw8, d->w_scale from dtp_op_quantize_w8) all e4m3 bytes moved by LDS-DMA, on the MX MFMA.  Epilogues (d->flags): DTP_GF_BIAS,
+ * DTP_GF_RESID (f16 R), DTP_GF_GEGLU (N % 128 == 0), DTP_GF_ROWSTATS (st_out: ceil(N / 128) partials per row, d->st_parts_out), and the
+ * e4m3 output C8.  M arbitrary, N % 64 == 0, K % 16 == 0 (Cin2 % 16 == 0), rows 16-byte aligned.  W8 must hold roundup(N, 128) rows and
+ * ldw8 >= roundup(K, 128) columns, zero beyond N / K (dtp_op_quantize_w8 on dtp_op_pack_linear output is).  Every scale is a power of two
+ * (other values: DTP_ERR_ARG).  d->tile: 0 = 128x128, 1 = 64x128, -1 = heuristic.  Values beyond +-448 * c_scale saturate; NaN stays NaN. */
+int dtp_op_gemm_f8f8(dtp_gemm_desc* d, dtp_stream s);
+/* The e4m3 quantise pass of option "fp8_operands" (gemm_f8f8_kernel's activation operand): y u8 [M][ldy] = e4m3(x / scale) of x f16 [M][ldx] (K columns, K % 8 == 0), with ln = 1
+ * of the LayerNorm (x - mean) * rstd (no gamma / beta; mean / rstd from st_in f32 [st_parts][M][2] per-row (sum, sumsq) partials as a
+ * DTP_GF_ROWSTATS producer writes them, or computed here when st_in is NULL; eps).  x2 (or NULL): a second job over the same M rows in
+ * the same launch (e.g. the raw and the normalised copy of one tensor).  Saturating (+-448; NaN stays NaN), round to nearest even;
+ * scales are powers of two. */
+int dtp_op_quant_e4m3(const void* x, int ldx, void* y, int ldy, int K, float scale, int ln, const void* x2, int ldx2, void* y2, int ldy2,
+                      int K2, float scale2, int ln2, int M, const float* st_in, int st_parts, float eps, dtp_stream s);
 /* w f32 [N][K] -> out f16 [rows][ldw] (caller zero-fills out); geglu=1 applies the [a|gate] tile packing */
 int dtp_op_pack_linear(const float* w, void* out, int N, int K, int ldw, int geglu, dtp_stream s);
 /* w f32 [Cout][Cin][3][3] (or 1x1) -> out f16 [rows][ldw], k = tap*Cin_pad + ci (caller zero-fills out) */
