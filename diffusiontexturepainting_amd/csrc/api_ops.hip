@@ -89,33 +89,20 @@ int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s) {
   int tile = 0;
   dtp_gemm_pick(p, &tile, g_ops.num_cu);
   if (d->tile >= 0) tile = d->tile;
-  if (d->splits >= 1 && d->batch <= 1) {
-    p.kb_per_split = (p.nkb + d->splits - 1) / d->splits;
-    p.splits = (p.nkb + p.kb_per_split - 1) / p.kb_per_split;
-  }
-  if ((tile >= 20 && tile < 32) || tile == DTP_TILE_LNLIN) { p.splits = 1; p.kb_per_split = p.nkb; }  // the wide, fp8 and lnlin tiles do not split K
-  if ((tile >= 24 && tile < 32) != (p.W8 != nullptr)) { dtp_set_error("gemm: tiles 24..27 and W8 go together"); return DTP_ERR_ARG; }
-  if (dtp_is_halo_tile(tile)) {  // halo-tiled 3x3 conv: split-K counts 64-channel blocks
-    if (!d->Wcb) { dtp_set_error("conv_halo: Wcb missing"); return DTP_ERR_ARG; }
-    p.W = (const f16*)d->Wcb;
-    dtp_split_k(p.nkb, tile, d->splits >= 1 ? d->splits : 1, &p.kb_per_split, &p.splits);
-  }
-  if (dtp_is_ws_tile(tile) || tile == DTP_TILE_GEMMWS) dtp_split_k(p.nkb, tile, d->splits >= 1 ? d->splits : 1, &p.kb_per_split, &p.splits);
+  const DtpTile t = dtp_tile(tile);
+  // the caller's splits; without them: the pick's K-slices for gemm_kernel tiles (batched problems always take those), four
+  // column ranges for lnlin, unsplit for the rest
+  int sp = t.split == SPLIT_COLS ? 4 : t.split == SPLIT_K ? p.splits : 1;
+  if (d->splits >= 1 && (d->batch <= 1 || t.split != SPLIT_K)) sp = d->splits;
+  if ((t.fam == TF_FP8) != (p.W8 != nullptr)) { dtp_set_error("gemm: tiles 24..28 and W8 go together"); return DTP_ERR_ARG; }
+  if (t.fam == TF_HALO && !d->Wcb) { dtp_set_error("conv_halo: Wcb missing"); return DTP_ERR_ARG; }
+  p.Wcb = (const f16*)d->Wcb;
+  (void)dtp_tile_apply(p, tile, sp);  // an unrealisable split takes the nearest the tile has; wide and fp8 tiles stay unsplit
   rc = ops_ws(dtp_gemm_workspace_bytes(p));
   if (rc) return rc;
   p.part = g_ops.ws;
-  if (dtp_is_ws_tile(tile)) return dtp_launch_conv_ws(p, tile - DTP_TILE_WS0, (hipStream_t)s);
-  if (p.flags & GF_ROWSTATS) {
-    int bm = 0, bn = 64, ns = 0;
-    (void)dtp_gemm_tile_dims(tile, &bm, &bn, &ns);
-    d->st_parts_out = p.splits > 1 ? 1 : (p.N + bn - 1) / bn;
-    if (tile == DTP_TILE_LNLIN) d->st_parts_out = d->splits >= 1 ? d->splits : 4;  // one partial per column range
-    if (tile == DTP_TILE_GEMMWS) d->st_parts_out = p.splits > 1 ? 1 : (p.N + 63) / 64;
-  }
-  if (tile == DTP_TILE_GEMMWS) return dtp_launch_gemm_ws(p, (hipStream_t)s);
-  if (tile == DTP_TILE_LNLIN) return dtp_launch_lnlin(p, d->splits >= 1 ? d->splits : 4, (hipStream_t)s);
-  if (dtp_is_halo_tile(tile)) return dtp_launch_conv_halo(p, dtp_halo_variant(tile), (hipStream_t)s);
-  return dtp_launch_gemm(p, tile, (hipStream_t)s);
+  if (p.flags & GF_ROWSTATS) d->st_parts_out = dtp_tile_row_parts(p, tile);
+  return dtp_launch_tile(p, tile, (hipStream_t)s);
 }
 
 int dtp_op_gemm_f8f8(dtp_gemm_desc* d, dtp_stream s) {

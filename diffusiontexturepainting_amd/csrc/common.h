@@ -355,10 +355,10 @@ static __device__ __forceinline__ void dtp_xcd_split(int id, int tiles, int spli
   else { const int g = 8 / splits; z = xcd % splits; tile = idx * g + xcd / splits; }
 }
 
-// tile: shape + 4 * (stages - 2); shape 0 = 128x128, 1 = 128(M)x64(N), 2 = 64x64, 3 = 64(M)x128(N); stages 2..4
+// gemm_kernel tile ids only (dtp_tile(tile).fam == TF_GEMM); dtp_launch_tile takes every family
 int dtp_launch_gemm(const GemmParams& p, int tile, hipStream_t s);
+int dtp_launch_tile(const GemmParams& p, int tile, hipStream_t s);
 int dtp_launch_splitk_reduce(const GemmParams& p, hipStream_t s);
-bool dtp_gemm_tile_dims(int tile, int* bm, int* bn, int* ns);
 size_t dtp_gemm_workspace_bytes(const GemmParams& p);
 void dtp_gemm_pick(GemmParams& p, int* tile, int num_cu);  // sets splits/kb_per_split
 
@@ -505,24 +505,81 @@ bool dtp_gemm_wide_supported(const GemmParams& p, int variant);
 int dtp_launch_gemm_wide(const GemmParams& p, int variant, hipStream_t s);
 void dtp_gemm_wide_init();
 // conv_halo.hip: variant 0..3 = (8x16|8x8 pixel tile) x (64|128 output channels); kb_per_split counts 64-channel blocks
-inline bool dtp_is_halo_tile(int tile) { return (tile >= 12 && tile < 16) || tile == 48 || tile == 49; }
-inline int dtp_halo_variant(int tile) { return tile >= 48 ? tile - 44 : tile - 12; }
 constexpr int DTP_TILE_LNLIN = 50;  // lnlin_kernel (lnlin.hip): the "splits" of a tune entry are its column ranges, K is not split
 constexpr int DTP_TILE_WS0 = 51;    // convws_kernel (conv_ws.hip): 51 = three 8 x 8 images, 52 = one 16 x 16 image, 53 = an 8 x 16 pixel tile x 64 channels per workgroup, 54 = the same for two co-resident workgroups per CU; splits = K-slices
 constexpr int DTP_WS_VARIANTS = 4;
 constexpr int DTP_TILE_GEMMWS = 55; // gemmws_kernel (gemm_ws.hip): dense problems with the fragment-order packing; splits = K-slices
 constexpr int DTP_TILE_IDS = 56;    // tile ids are 0 .. DTP_TILE_IDS - 1
-inline bool dtp_is_ws_tile(int tile) { return tile >= DTP_TILE_WS0 && tile < DTP_TILE_WS0 + DTP_WS_VARIANTS; }
-// Split-K of a problem of nkb 64-wide k-blocks into (at most) sp slices.  conv_halo_kernel unrolls the nine taps of a channel block:
-// its slices are multiples of 9 k-blocks (the 9 * Cin/64 conv blocks come first, so no channel block is cut).
-inline void dtp_split_k(int nkb, int tile, int sp, int* kb_per_split, int* splits) {
+
+// profiling classes (dtp_profile_rows): 0-11 = gemm_kernel<BM,BN,NS> variants (id = shape + 4*(NS-2)), then the rest
+enum { PK_GEMM0 = 0, PK_ATTN = 12, PK_GN = 13, PK_LN = 14, PK_ELEM = 15, PK_SOFTMAX = 16, PK_HALO0 = 17, PK_BIG0 = 21, PK_WIDE0 = 25, PK_FP8 = 27, PK_KH2 = 28, PK_LW = 36, PK_XATTN = 44, PK_HALO3 = 45, PK_LNLIN = 47, PK_WS0 = 48, PK_GEMMWS = 52, PK_F8F8 = 53, PK_QUANT8 = 54, PK_COUNT = 55 };
+
+// ---- tile ids.  Every GEMM / conv launch of the engine is named by one id: the value of a tune table entry, of dtp_gemm_desc.tile
+// and of LastGemm.  dtp_tile(id) is the only decoder: which kernel family runs the id, the variant that family's launcher takes,
+// the tile shape, the profiling class, and what the "splits" of a configuration (tile, splits) mean.
+enum DtpFamily : unsigned char { TF_NONE, TF_GEMM, TF_HALO, TF_WIDE, TF_FP8, TF_LNLIN, TF_CONVWS, TF_GEMMWS };
+enum DtpSplit : unsigned char {
+  SPLIT_K,       // K-slices of 64-wide k-blocks (the fp32 slabs are reduced by dtp_launch_splitk_reduce)
+  SPLIT_HALO,    // K-slices of whole channel blocks: conv_halo_kernel unrolls the nine taps of a block, so a slice is a multiple of 9
+  SPLIT_BLOCKS,  // K-slices that are ranges of whole channel / k-blocks (conv_ws.hip, gemm_ws.hip): every factor is realised
+  SPLIT_COLS,    // column ranges per 128-row block (lnlin.hip); K is not split
+  SPLIT_NONE,    // unsplit only (gemm_wide.hip, gemm_fp8.hip)
+};
+struct DtpTile {
+  DtpFamily fam;
+  int var;              // the variant the family's launcher takes: halo 0..5, wide 0..1, fp8 0..4, convws 0..3
+  int bm, bn, ns;       // output tile and pipeline depth (0: the family has none)
+  int kh, lw;           // gemm_kernel: 1 / 2 k-halves (4 / 8 waves), loader waves (0 = none)
+  DtpSplit split;
+  int pk;               // PK_* profiling class
+};
+// 0..11: gemm_kernel, shape (id & 3) of {128x128, 128x64, 64x64, 64x128} at depth 2 + id / 4.  12..15: conv_halo_kernel variants
+// 0..3.  16..19: gemm_kernel {256x128, 256x128, 128x256, 128x256} at depth {2, 3, 2, 3}.  20 / 21: gemm_wide_kernel 256 x 256 /
+// 256 x 320 (8 waves).  24..27: gemm_fp8_kernel, the shapes of ids 0..3; 28: its 8-wave 256 x 256.  32..39: gemm_kernel with 8 waves
+// (KH = 2), shape (id & 3) at depth 2 + (id - 32) / 4.  40..47: gemm_kernel at depth 3 with 4 (40..43) or 8 loader waves.
+// 48 / 49: conv_halo_kernel variants 4 / 5 (three images per workgroup).  50 / 51..54 / 55: see DTP_TILE_*.  22, 23 and 29..31 are
+// holes: TF_NONE, as is any id outside 0 .. DTP_TILE_IDS - 1.
+inline DtpTile dtp_tile(int id) {
+  static constexpr int sm[4] = {128, 128, 64, 64}, sn[4] = {128, 64, 64, 128};
+  const int s = id & 3;
+  if (id >= 0 && id < 12) return {TF_GEMM, 0, sm[s], sn[s], 2 + id / 4, 1, 0, SPLIT_K, PK_GEMM0 + id};
+  if (id >= 12 && id < 16) return {TF_HALO, id - 12, 0, 0, 0, 0, 0, SPLIT_HALO, PK_HALO0 + id - 12};
+  if (id >= 16 && id < 20) return {TF_GEMM, 0, id < 18 ? 256 : 128, id < 18 ? 128 : 256, 2 + (id & 1), 1, 0, SPLIT_K, PK_BIG0 + id - 16};
+  if (id == 20 || id == 21) return {TF_WIDE, id - 20, 256, id == 20 ? 256 : 320, 2, 0, 0, SPLIT_NONE, PK_WIDE0 + id - 20};
+  if (id >= 24 && id < 28) return {TF_FP8, id - 24, sm[s], sn[s], 2, 0, 0, SPLIT_NONE, PK_FP8};
+  if (id == 28) return {TF_FP8, 4, 256, 256, 2, 0, 0, SPLIT_NONE, PK_FP8};
+  if (id >= 32 && id < 40) return {TF_GEMM, 0, sm[s], sn[s], 2 + (id - 32) / 4, 2, 0, SPLIT_K, PK_KH2 + id - 32};
+  if (id >= 40 && id < 48) return {TF_GEMM, 0, sm[s], sn[s], 3, 1, id < 44 ? 4 : 8, SPLIT_K, PK_LW + id - 40};
+  if (id == 48 || id == 49) return {TF_HALO, id - 44, 0, 0, 0, 0, 0, SPLIT_HALO, PK_HALO3 + id - 48};
+  if (id == DTP_TILE_LNLIN) return {TF_LNLIN, 0, 0, 0, 0, 0, 0, SPLIT_COLS, PK_LNLIN};
+  if (id >= DTP_TILE_WS0 && id < DTP_TILE_WS0 + DTP_WS_VARIANTS) return {TF_CONVWS, id - DTP_TILE_WS0, 0, 0, 0, 0, 0, SPLIT_BLOCKS, PK_WS0 + id - DTP_TILE_WS0};
+  if (id == DTP_TILE_GEMMWS) return {TF_GEMMWS, 0, 64, 64, 0, 0, 0, SPLIT_BLOCKS, PK_GEMMWS};
+  return {};
+}
+// Apply the configuration (tile, sp) -- a tune table entry -- to p: the K-slices (kb_per_split / splits) or the column ranges, and
+// the halo kernels' channel-block-major weights (W = Wcb).  False when the tile cannot realise sp: p then holds the split it would take.
+inline bool dtp_tile_apply(GemmParams& p, int tile, int sp) {
+  const DtpTile t = dtp_tile(tile);
   if (sp < 1) sp = 1;
-  if (tile == DTP_TILE_LNLIN) { *kb_per_split = nkb; *splits = 1; return; }
-  if (dtp_is_ws_tile(tile) || tile == DTP_TILE_GEMMWS) { *kb_per_split = (nkb + sp - 1) / sp; *splits = sp; return; }  // slices are ranges of whole channel / k-blocks (conv_ws.hip, gemm_ws.hip)
-  int kbps = (nkb + sp - 1) / sp;
-  if (dtp_is_halo_tile(tile) && sp > 1) kbps = (((nkb + 8) / 9 + sp - 1) / sp) * 9;
-  *kb_per_split = kbps;
-  *splits = (nkb + kbps - 1) / kbps;
+  if (t.fam == TF_HALO) p.W = p.Wcb;
+  if (t.split == SPLIT_NONE || t.split == SPLIT_COLS) {
+    p.kb_per_split = p.nkb; p.splits = 1;
+    if (t.split == SPLIT_COLS) p.col_ranges = sp;
+    return t.split == SPLIT_COLS || sp == 1;
+  }
+  p.kb_per_split = (p.nkb + sp - 1) / sp;
+  if (t.split == SPLIT_BLOCKS) { p.splits = sp; return true; }
+  if (t.split == SPLIT_HALO && sp > 1) p.kb_per_split = (((p.nkb + 8) / 9 + sp - 1) / sp) * 9;
+  p.splits = (p.nkb + p.kb_per_split - 1) / p.kb_per_split;
+  return p.splits == sp;
+}
+// Row-statistics partials per row that p on tile writes (GF_ROWSTATS): one per column range (lnlin), one when K is split (the
+// reduce writes them), else one per N tile.  0 for the tile-less halo and convws kernels, whose launchers refuse GF_ROWSTATS.
+inline int dtp_tile_row_parts(const GemmParams& p, int tile) {
+  const DtpTile t = dtp_tile(tile);
+  if (t.split == SPLIT_COLS) return p.col_ranges;
+  if (!t.bn) return 0;
+  return p.splits > 1 ? 1 : (p.N + t.bn - 1) / t.bn;
 }
 // lnlin.hip: activation-stationary LayerNorm-folded Linear (+ GEGLU) for K = 320 / 640; nsplit = column ranges per 128-row block
 bool dtp_lnlin_supported(const GemmParams& p, int nsplit);

@@ -446,7 +446,8 @@ bool Builder::claim_reduce(const T& x, GemmParams& gp, int& bias_step_off, bool 
 bool Builder::claim_stats(const T& x, float** partials, int* nchunk) {
   static const bool off = [] { const char* e = getenv("DTP_NO_GN_EPILOGUE"); return e && e[0] && e[0] != '0'; }();
   const LastGemm lg = prog->last_gemm;
-  if (off || !lg.valid || lg.tile < DTP_TILE_WS0 + 2 || !dtp_is_ws_tile(lg.tile) || lg.p.splits != 1 || (f16*)lg.p.C != x.p || lg.p.ldc != x.ld ||
+  const DtpTile t = dtp_tile(lg.tile);
+  if (off || !lg.valid || t.fam != TF_CONVWS || t.var < 2 || lg.p.splits != 1 || (f16*)lg.p.C != x.p || lg.p.ldc != x.ld ||
       lg.p.M != (int)x.rows() || lg.p.N != x.C || !dtp_conv_output_can_carry_gn_stats(lg.p))
     return false;
   GemmParams gp = lg.p;
@@ -460,7 +461,7 @@ bool Builder::claim_stats(const T& x, float** partials, int* nchunk) {
   gp.flags |= GF_GNSTATS;
   gp.st_out = (float*)pp;
   gp.gn_cpg = x.C / 32;
-  if (!dtp_conv_ws_supported(gp, lg.tile - DTP_TILE_WS0, 1)) { ctx_pool_put(c, pp); return false; }
+  if (!dtp_conv_ws_supported(gp, t.var, 1)) { ctx_pool_put(c, pp); return false; }
   prog->ops.pop_back();
   prog_push(c, prog, lg.kind, lg.flops, lg.bytes, make_gemm_op(c, gp, lg.tile, lg.bias_step_off), lg.label + " (+gn stats)");
   *partials = (float*)pp;
@@ -670,23 +671,21 @@ void tune_cache_load(Ctx* c) {
 // different packing) or hand-edited: a halo tile without the channel-block-major packing, a GEGLU problem on a tile that is
 // not 128 wide, or a split LayerNorm-fold would otherwise reach the kernels.
 static bool tune_entry_valid(const GemmParams& p, int tile, int sp) {
-  if (sp < 1 || (sp > p.nkb && tile != DTP_TILE_LNLIN)) return false;
-  if (tile == DTP_TILE_GEMMWS) return dtp_gemm_ws_supported(p, sp);
-  if (tile != DTP_TILE_LNLIN && !dtp_is_ws_tile(tile)) {
-    int kbps, n;
-    dtp_split_k(p.nkb, tile, sp, &kbps, &n);
-    if (n != sp) return false;  // not a factor this tile can realise
+  const DtpTile t = dtp_tile(tile);
+  GemmParams q = p;
+  if (sp < 1 || (sp > p.nkb && t.fam != TF_LNLIN) || !dtp_tile_apply(q, tile, sp)) return false;  // not a factor this tile can realise
+  switch (t.fam) {
+    case TF_NONE: return false;
+    case TF_GEMMWS: return dtp_gemm_ws_supported(p, sp);
+    case TF_LNLIN: return dtp_lnlin_supported(p, sp);
+    case TF_CONVWS: return dtp_conv_ws_supported(p, t.var, sp);
+    case TF_HALO: return p.Wcb && (t.var >= 4 ? dtp_conv_halo3_supported(p) : dtp_conv_halo_supported(p)) && p.batch <= 1;
+    default: break;
   }
-  if (tile == DTP_TILE_LNLIN) return dtp_lnlin_supported(p, sp);
-  if (dtp_is_ws_tile(tile)) return dtp_conv_ws_supported(p, tile - DTP_TILE_WS0, sp);
-  const bool halo = dtp_is_halo_tile(tile);
-  if (halo) return p.Wcb && (tile >= 48 ? dtp_conv_halo3_supported(p) : dtp_conv_halo_supported(p)) && p.batch <= 1;
   if (p.flags & GF_GNAPPLY) return false;  // only the halo kernel normalises its staged input
-  int bm = 0, bn = 0, ns = 0;
-  if (!dtp_gemm_tile_dims(tile, &bm, &bn, &ns)) return false;
-  if (tile >= 24 && tile < 32) { GemmParams q = p; q.splits = 1; return sp == 1 && tile <= 28 && dtp_gemm_fp8_supported(q) && !((p.flags & GF_GEGLU) && (bn % 128)); }
-  if (tile >= 20 && tile < 32) { GemmParams q = p; q.splits = 1; return sp == 1 && dtp_gemm_wide_supported(q, tile - 20); }
-  if ((p.flags & GF_GEGLU) && (bn != 128 || sp != 1)) return false;
+  if (t.fam == TF_FP8) return dtp_gemm_fp8_supported(q) && !((p.flags & GF_GEGLU) && (t.bn % 128));
+  if (t.fam == TF_WIDE) return dtp_gemm_wide_supported(q, t.var);
+  if ((p.flags & GF_GEGLU) && (t.bn != 128 || sp != 1)) return false;
   if (sp > 1 && ((p.flags & (GF_LNFOLD | GF_SOFTMAX16)) || p.batch > 1)) return false;
   if (sp > 1 && (size_t)sp * p.M * p.N * sizeof(float) > ((size_t)512 << 20)) return false;  // the fp32 slabs of a split
   return true;
@@ -706,10 +705,90 @@ void tune_cache_save(Ctx* c) {
   c->tune_saved = c->tuned.size();
 }
 
+// The first-round candidates of a problem, as configurations (tile id, splits) in the order they are timed.  ws_ok[v]: the
+// weight-streaming conv variant v takes the problem; gw_ok: the weight-streaming GEMM does.
+struct TuneCfg { int tile, sp; };
+static std::vector<TuneCfg> tune_candidates(const GemmParams& p, const bool* ws_ok, bool gw_ok) {
+  static const bool no_lnlin = [] { const char* e = getenv("DTP_NO_LNLIN"); return e && e[0] && e[0] != '0'; }();
+  static const bool no_halo3 = [] { const char* e = getenv("DTP_NO_HALO3"); return e && e[0] && e[0] != '0'; }();
+  static const bool no_ws = [] { const char* e = getenv("DTP_NO_WS"); return e && e[0] && e[0] != '0'; }();
+  static const int cand_splits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
+  const bool geglu = (p.flags & GF_GEGLU) != 0;
+  std::vector<TuneCfg> out;
+  auto add = [&](int tile, int sp) {  // a split the tile cannot realise, or fp32 slabs over 512 MiB, is not a candidate
+    GemmParams q = p;
+    if (dtp_tile_apply(q, tile, sp) && dtp_gemm_workspace_bytes(q) <= ((size_t)512 << 20)) out.push_back({tile, sp});
+  };
+  // gemm_kernel in all its shapes, depths and wave layouts, the 8-wave wide tiles and fp8
+  for (int tile = 0; tile < DTP_TILE_IDS && !(p.flags & GF_GNAPPLY); ++tile) {
+    const DtpTile t = dtp_tile(tile);
+    if (t.fam != TF_GEMM && t.fam != TF_WIDE && t.fam != TF_FP8) continue;
+    // fp8 tiles need the e4m3 weight copy.  An fp8 problem keeps the choice of an fp16 tile while it is small (the register-
+    // staged activation operand costs latency-bound launches more than the MX MFMA returns: 256^2 / 8 steps 32.6 -> 27.5 ms);
+    // from M = 6144 on (every level-0..2 Linear of a batch-8 stamp) it runs on the fp8 tiles only -- there the cold single-launch
+    // timing of the tuner under-rates them (batch 8: 588 ms with fp8 tiles throughout, 606 ms with the tuner's mix, 605 ms in fp16)
+    if (t.fam == TF_FP8 ? !p.W8 : (p.W8 && p.M >= 6144)) continue;
+    const long long ntiles = (long long)((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn);
+    if (t.fam == TF_FP8) {
+      if (!(geglu && (t.bn % 128)) && !(t.var == 4 && ntiles < 96)) add(tile, 1);
+      continue;
+    }
+    if (t.fam == TF_WIDE) {  // gemm_wide_kernel: unsplit big-M problems only (at least half a wave of 256 CUs worth of tiles)
+      GemmParams q = p;
+      q.splits = 1;
+      if (!dtp_gemm_wide_supported(q, t.var) || ntiles < 96) continue;
+      if (t.var == 1 && (p.N % 320) > 0 && (p.N % 320) <= 192) continue;  // a mostly empty last column tile: 256 x 256 covers it better
+      add(tile, 1);
+      continue;
+    }
+    if (geglu && t.bn != 128) continue;
+    if (p.nkb < 3 && t.ns > 2) continue;
+    if ((t.bm == 256 && p.M < 192) || (t.bn == 256 && p.N < 192)) continue;
+    for (int sp : cand_splits) {
+      if (sp > 1 && (geglu || (p.flags & GF_LNFOLD) || p.batch > 1 || p.nkb / sp < 2)) break;
+      add(tile, sp);
+    }
+  }
+  {  // the activation-stationary kernel of the short LayerNorm-folded contractions: column ranges per 128-row block
+    static const int ranges[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40};
+    for (int sp : ranges)
+      if (!no_lnlin && dtp_lnlin_supported(p, sp)) add(DTP_TILE_LNLIN, sp);
+  }
+  for (int tile = 0; tile < DTP_TILE_IDS && p.Wcb && dtp_conv_halo_supported(p); ++tile) {  // the halo-tiled conv kernels (Wcb packing)
+    const DtpTile t = dtp_tile(tile);
+    if (t.fam != TF_HALO) continue;
+    const bool small = p.Hi * p.Wi <= 256;
+    // 8x8 pixel tiles for small feature maps, 8x16 otherwise; three images per workgroup: the small maps of a batch-1 stamp, where
+    // the weight slices are most of the LDS fill
+    if (t.var < 4 ? (t.var >= 2) != small : (no_halo3 || !small || !dtp_conv_halo3_supported(p))) continue;
+    for (int sp : cand_splits) {
+      if (sp > 1 && p.nkb / sp < 9) break;
+      add(tile, sp);
+    }
+  }
+  for (int tile = 0; tile < DTP_TILE_IDS; ++tile) {  // the weight-streaming conv: K-slices = ranges of whole channel blocks
+    const DtpTile t = dtp_tile(tile);
+    static const int slices[] = {1, 2, 3, 4, 5, 6, 8, 10};
+    if (t.fam != TF_CONVWS) continue;
+    for (int sp : slices) {
+      if (no_ws || !ws_ok[t.var] || !dtp_conv_ws_supported(p, t.var, sp)) continue;
+      if (t.var >= 2 && sp > 4) continue;
+      add(tile, sp);
+    }
+  }
+  if (gw_ok) {  // the weight-streaming GEMM: K-slices = ranges of whole k-blocks
+    static const int slices[] = {1, 2, 3, 4, 5, 6, 8};
+    for (int sp : slices)
+      if (dtp_gemm_ws_supported(p, sp) && !(sp > 1 && p.nkb / sp < 4)) add(DTP_TILE_GEMMWS, sp);
+  }
+  return out;
+}
+
 // Build-time autotuning: the stamp path has ~100 distinct contraction shapes, most of them far from
 // "large square GEMM" (M from 192 to 524288, N from 3 to 10240).  Each distinct shape is timed once
 // with every tile variant x split-K factor on the real buffers and the fastest pair is kept.
-static int tune_gemm(Ctx* c, GemmParams& p, int* tile_out) {
+// (*tile, *sp) is the caller's configuration on entry, the one to use on return.
+static int tune_gemm(Ctx* c, const GemmParams& p, int* tile, int* sp) {
   char key[200];
   // "k8|": bump when tile ids or pipelines change, so that a persisted table written by an older build is ignored
   int kl = snprintf(key, sizeof(key), "k8|%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", p.M, p.N, p.K, p.flags & ~GF_MFAST, p.Hi, p.Wi, p.Cin,
@@ -741,144 +820,51 @@ static int tune_gemm(Ctx* c, GemmParams& p, int* tile_out) {
     constexpr size_t THRASH_BYTES = (size_t)512 << 20;
     if (!c->tune_thrash) HIP_CHECK(hipMalloc(&c->tune_thrash, THRASH_BYTES));
     const size_t a_bytes = (p.flags & GF_CONV3) ? (size_t)(p.M / (p.Ho * p.Wo)) * p.Hi * p.Wi * p.lda * 2 : (size_t)p.M * p.lda * 2;
-    float best = 1e30f;
-    int bt = *tile_out, bs = p.splits;
-    const bool geglu = (p.flags & GF_GEGLU) != 0;
-    static const int cand_splits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
-    // One candidate = (tile id, split-K factor); tile ids 12..15 are the halo-tiled conv kernels (they read the Wcb packing).
-    // Timed the way the stamp sees it: weights COLD (1.7 GB of them stream through the 256 MiB Infinity Cache every UNet
+    // Timed the way the stamp sees it (cold): weights COLD (1.7 GB of them stream through the 256 MiB Infinity Cache every UNet
     // evaluation), activations warm (just written by the previous kernel); minimum over `reps` runs (a single cold run is noisy:
-    // DVFS, thrash write-back still draining).  Returns < 0 when the candidate does not apply.
-    auto time_cfg = [&](int tile, int sp, int reps, float* out_ms) -> int {
-      *out_ms = -1.f;
+    // DVFS, thrash write-back still draining).  Hot: nothing evicted, the first run not counted.
+    auto time_cfg = [&](int cfg_tile, int cfg_sp, int reps, bool cold, float* out_ms) -> int {
       GemmParams q = p;
-      const bool halo = dtp_is_halo_tile(tile);
-      if (halo) q.W = p.Wcb;
-      dtp_split_k(p.nkb, tile, sp, &q.kb_per_split, &q.splits);
-      if (tile == DTP_TILE_LNLIN) q.col_ranges = sp;
-      else if (q.splits != sp && sp > 1) return DTP_OK;
+      (void)dtp_tile_apply(q, cfg_tile, cfg_sp);
       const size_t need = dtp_gemm_workspace_bytes(q);
-      if (need > ((size_t)512 << 20)) return DTP_OK;
       if (need > c->ws_bytes) { c->ws_need = std::max(c->ws_need, need); RC(ensure_ws(c)); }
       q.part = c->ws;
       q.zero = c->zero;
       float ms = 1e30f;
       for (int rep = 0; rep < reps; ++rep) {
-        HIP_CHECK(hipMemsetAsync(c->tune_thrash, rep, THRASH_BYTES, 0));
-        RC(dtp_launch_touch(q.A, a_bytes, (float*)c->tune_thrash, 0));
-        if (q.R) RC(dtp_launch_touch(q.R, (size_t)q.M * q.ldr * 2, (float*)c->tune_thrash, 0));
+        if (cold) {
+          HIP_CHECK(hipMemsetAsync(c->tune_thrash, rep, THRASH_BYTES, 0));
+          RC(dtp_launch_touch(q.A, a_bytes, (float*)c->tune_thrash, 0));
+          if (q.R) RC(dtp_launch_touch(q.R, (size_t)q.M * q.ldr * 2, (float*)c->tune_thrash, 0));
+        }
         HIP_CHECK(hipEventRecord(c->tune_ev[0], 0));
-        if (tile == DTP_TILE_LNLIN) RC(dtp_launch_lnlin(q, sp, 0));
-        else if (tile == DTP_TILE_GEMMWS) RC(dtp_launch_gemm_ws(q, 0));
-        else if (dtp_is_ws_tile(tile)) RC(dtp_launch_conv_ws(q, tile - DTP_TILE_WS0, 0));
-        else if (halo) RC(dtp_launch_conv_halo(q, dtp_halo_variant(tile), 0)); else RC(dtp_launch_gemm(q, tile, 0));
+        RC(dtp_launch_tile(q, cfg_tile, 0));
         HIP_CHECK(hipEventRecord(c->tune_ev[1], 0));
         HIP_CHECK(hipEventSynchronize(c->tune_ev[1]));
-        float t = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&t, c->tune_ev[0], c->tune_ev[1]));
-        ms = std::min(ms, t);
+        float ev = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ev, c->tune_ev[0], c->tune_ev[1]));
+        if (cold || rep) ms = std::min(ms, ev);
       }
       *out_ms = ms;
       return DTP_OK;
     };
     struct Cand { float ms; int tile, sp; };
     std::vector<Cand> cands;
-    for (int tile = 0; tile < 48 && !(p.flags & GF_GNAPPLY); ++tile) {  // 4 tile shapes x 3 pipeline depths, the 256-row / 256-column tiles, the 8-wave wide tiles, fp8, the 8-wave twins of the small shapes, their loader-wave variants
-      int bm = 0, bn = 0, ns = 0;
-      if (!dtp_gemm_tile_dims(tile, &bm, &bn, &ns)) continue;
-      // fp8 tiles need the e4m3 weight copy.  An fp8 problem keeps the choice of an fp16 tile while it is small (the register-
-      // staged activation operand costs latency-bound launches more than the MX MFMA returns: 256^2 / 8 steps 32.6 -> 27.5 ms);
-      // from M = 6144 on (every level-0..2 Linear of a batch-8 stamp) it runs on the fp8 tiles only -- there the cold single-launch
-      // timing of the tuner under-rates them (batch 8: 588 ms with fp8 tiles throughout, 606 ms with the tuner's mix, 605 ms in fp16)
-      const bool f8t = tile >= 24 && tile < 32;
-      if (f8t ? !p.W8 : (p.W8 && p.M >= 6144)) continue;
-      if (tile >= 24 && tile < 32) {
-        if (geglu && (bn % 128)) continue;
-        if (tile == 28 && (long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) < 96) continue;
-        float ms;
-        RC(time_cfg(tile, 1, 5, &ms));
-        if (ms >= 0.f) cands.push_back({ms, tile, 1});
-        continue;
-      }
-      if (tile >= 20 && tile < 32) {  // gemm_wide_kernel: unsplit big-M problems only (at least half a wave of 256 CUs worth of tiles)
-        GemmParams q = p;
-        q.splits = 1;
-        if (!dtp_gemm_wide_supported(q, tile - 20)) continue;
-        if ((long long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) < 96) continue;
-        if (tile == 21 && (p.N % 320) > 0 && (p.N % 320) <= 192) continue;  // a mostly empty last column tile: 256 x 256 covers it better
-        float ms;
-        RC(time_cfg(tile, 1, 5, &ms));
-        if (ms >= 0.f) cands.push_back({ms, tile, 1});
-        continue;
-      }
-      if (geglu && bn != 128) continue;
-      if (p.nkb < 3 && ns > 2) continue;
-      if ((bm == 256 && p.M < 192) || (bn == 256 && p.N < 192)) continue;
-      for (int sp : cand_splits) {
-        if (sp > 1 && (geglu || (p.flags & GF_LNFOLD) || p.batch > 1 || p.nkb / sp < 2)) break;
-        float ms;
-        RC(time_cfg(tile, sp, 5, &ms));
-        if (ms >= 0.f) cands.push_back({ms, tile, sp});
-      }
-    }
-    {  // the activation-stationary kernel of the short LayerNorm-folded contractions: column ranges per 128-row block
-      static const bool no_lnlin = [] { const char* e = getenv("DTP_NO_LNLIN"); return e && e[0] && e[0] != '0'; }();
-      static const int ranges[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40};
-      for (int sp : ranges) {
-        if (no_lnlin || !dtp_lnlin_supported(p, sp)) continue;
-        float ms;
-        RC(time_cfg(DTP_TILE_LNLIN, sp, 5, &ms));
-        if (ms >= 0.f) cands.push_back({ms, DTP_TILE_LNLIN, sp});
-      }
-    }
-    if (p.Wcb && dtp_conv_halo_supported(p)) {
-      for (int v = 0; v < 4; ++v) {
-        if ((v >= 2) != (p.Hi * p.Wi <= 256)) continue;  // 8x8 pixel tiles for small feature maps, 8x16 otherwise
-        for (int sp : cand_splits) {
-          if (sp > 1 && p.nkb / sp < 9) break;
-          float ms;
-          RC(time_cfg(12 + v, sp, 5, &ms));
-          if (ms >= 0.f) cands.push_back({ms, 12 + v, sp});
-        }
-      }
-      // three images per workgroup: the small maps of a batch-1 stamp, where the weight slices are most of the LDS fill
-      static const bool no_halo3 = [] { const char* e = getenv("DTP_NO_HALO3"); return e && e[0] && e[0] != '0'; }();
-      for (int tile = 48; tile < 50 && !no_halo3 && p.Hi * p.Wi <= 256 && dtp_conv_halo3_supported(p); ++tile)
-        for (int sp : cand_splits) {
-          if (sp > 1 && p.nkb / sp < 9) break;
-          float ms;
-          RC(time_cfg(tile, sp, 5, &ms));
-          if (ms >= 0.f) cands.push_back({ms, tile, sp});
-        }
-    }
-    for (int v = 0; v < DTP_WS_VARIANTS; ++v) {  // the weight-streaming conv: K-slices = ranges of whole channel blocks
-      static const bool no_ws = [] { const char* e = getenv("DTP_NO_WS"); return e && e[0] && e[0] != '0'; }();
-      static const int slices[] = {1, 2, 3, 4, 5, 6, 8, 10};
-      for (int sp : slices) {
-        if (no_ws || !ws_ok[v] || !dtp_conv_ws_supported(p, v, sp)) continue;
-        if (v >= 2 && sp > 4) continue;
-        float ms;
-        RC(time_cfg(DTP_TILE_WS0 + v, sp, 5, &ms));
-        if (ms >= 0.f) cands.push_back({ms, DTP_TILE_WS0 + v, sp});
-      }
-    }
-    if (gw_ok) {  // the weight-streaming GEMM: K-slices = ranges of whole k-blocks
-      static const int slices[] = {1, 2, 3, 4, 5, 6, 8};
-      for (int sp : slices) {
-        if (!dtp_gemm_ws_supported(p, sp) || (sp > 1 && p.nkb / sp < 4)) continue;
-        float ms;
-        RC(time_cfg(DTP_TILE_GEMMWS, sp, 5, &ms));
-        if (ms >= 0.f) cands.push_back({ms, DTP_TILE_GEMMWS, sp});
-      }
+    for (const TuneCfg& cfg : tune_candidates(p, ws_ok, gw_ok)) {
+      float ms;
+      RC(time_cfg(cfg.tile, cfg.sp, 5, true, &ms));
+      cands.push_back({ms, cfg.tile, cfg.sp});
     }
     // second round: the three fastest candidates are usually within the measurement noise of each other -- time them again,
     // longer, and keep the minimum over both rounds
     std::sort(cands.begin(), cands.end(), [](const Cand& x, const Cand& y) { return x.ms < y.ms; });
     for (size_t i = 0; i < cands.size() && i < 3; ++i) {
       float ms;
-      RC(time_cfg(cands[i].tile, cands[i].sp, 8, &ms));
-      if (ms >= 0.f) cands[i].ms = std::min(cands[i].ms, ms);
+      RC(time_cfg(cands[i].tile, cands[i].sp, 8, true, &ms));
+      cands[i].ms = std::min(cands[i].ms, ms);
     }
+    float best = 1e30f;
+    int bt = *tile, bs = *sp;
     for (size_t i = 0; i < cands.size() && i < 3; ++i)
       if (cands[i].ms < best) { best = cands[i].ms; bt = cands[i].tile; bs = cands[i].sp; }
     // A conv is ranked by its own launch, but an UNSPLIT two-n-tile convws launch (tile 53 / 54) also delivers the GroupNorm statistics of
@@ -888,34 +874,17 @@ static int tune_gemm(Ctx* c, GemmParams& p, int* tile_out) {
     // statistics-capable candidate is credited with that pass when its output is one claim_stats would take.
     // (the tune key does not know the consumer: an output of such a shape is followed by a GroupNorm everywhere in these networks --
     // conv_out has N = 4 / 3, which the predicate excludes -- but in the up path that GroupNorm runs over a concatenation and cannot claim)
-    if (ws_any && !dtp_is_ws_tile(bt) && dtp_conv_output_can_carry_gn_stats(p)) {
+    if (ws_any && dtp_tile(bt).fam != TF_CONVWS && dtp_conv_output_can_carry_gn_stats(p)) {
       const float stats_ms = 0.005f + (float)((double)p.M * p.N * 2.0 / 4.0e12 * 1e3);  // dispatch floor + the tensor once at ~4 TB/s
-      for (const Cand& cd : cands)
-        if (cd.sp == 1 && (cd.tile == DTP_TILE_WS0 + 2 || cd.tile == DTP_TILE_WS0 + 3) && cd.ms - stats_ms < best) {
-          best = cd.ms - stats_ms; bt = cd.tile; bs = 1;
-        }
+      for (const Cand& cd : cands) {
+        const DtpTile t = dtp_tile(cd.tile);
+        if (cd.sp == 1 && t.fam == TF_CONVWS && t.var >= 2 && cd.ms - stats_ms < best) { best = cd.ms - stats_ms; bt = cd.tile; bs = 1; }
+      }
     }
     it = c->tuned.emplace(key, std::make_pair(bt, bs)).first;
     if (getenv("DTP_TUNE_REPORT")) {  // how much of the chosen configuration's time is the cold operands?
-      GemmParams q = p;
-      if (dtp_is_halo_tile(bt)) q.W = p.Wcb;
-      dtp_split_k(p.nkb, bt, bs, &q.kb_per_split, &q.splits);
-      if (bt == DTP_TILE_LNLIN) q.col_ranges = bs;
-      q.part = c->ws;
-      q.zero = c->zero;
-      float hot = 1e30f;
-      for (int rep = 0; rep < 4; ++rep) {
-        HIP_CHECK(hipEventRecord(c->tune_ev[0], 0));
-        if (bt == DTP_TILE_LNLIN) RC(dtp_launch_lnlin(q, bs, 0));
-        else if (bt == DTP_TILE_GEMMWS) RC(dtp_launch_gemm_ws(q, 0));
-        else if (dtp_is_ws_tile(bt)) RC(dtp_launch_conv_ws(q, bt - DTP_TILE_WS0, 0));
-        else if (dtp_is_halo_tile(bt)) RC(dtp_launch_conv_halo(q, dtp_halo_variant(bt), 0)); else RC(dtp_launch_gemm(q, bt, 0));
-        HIP_CHECK(hipEventRecord(c->tune_ev[1], 0));
-        HIP_CHECK(hipEventSynchronize(c->tune_ev[1]));
-        float t = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&t, c->tune_ev[0], c->tune_ev[1]));
-        if (rep) hot = std::min(hot, t);
-      }
+      float hot;
+      RC(time_cfg(bt, bs, 4, false, &hot));
       c->tune_ms[key] = std::make_pair(best, hot);
     }
   }
@@ -928,9 +897,8 @@ static int tune_gemm(Ctx* c, GemmParams& p, int* tile_out) {
               m->second.second * 1e3);
     }
   }
-  *tile_out = it->second.first;
-  dtp_split_k(p.nkb, it->second.first, it->second.second, &p.kb_per_split, &p.splits);
-  if (it->second.first == DTP_TILE_LNLIN) p.col_ranges = it->second.second;
+  *tile = it->second.first;
+  *sp = it->second.second;
   return DTP_OK;
 }
 
@@ -991,34 +959,26 @@ static Op make_gemm_op(Ctx* c, GemmParams p, int tile, int bias_step_off) {
       q.a_scale = *p.a_scale_host;
     }
     if (bias_step_off >= 0) q.bias = c->temb_table + (size_t)step * c->unet.temb_total + bias_step_off;
-    if (tile == DTP_TILE_LNLIN) return dtp_launch_lnlin(q, q.col_ranges, s);
-    if (tile == DTP_TILE_GEMMWS) return dtp_launch_gemm_ws(q, s);
-    if (dtp_is_ws_tile(tile)) return dtp_launch_conv_ws(q, tile - DTP_TILE_WS0, s);
-    if (dtp_is_halo_tile(tile)) { q.W = q.Wcb; return dtp_launch_conv_halo(q, dtp_halo_variant(tile), s); }
-    return dtp_launch_gemm(q, tile, s);
+    return dtp_launch_tile(q, tile, s);
   };
 }
 
 int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg, RowStats* emit) {
   int tile = 0;
   dtp_gemm_pick(p, &tile, c->num_cu);
-  if (p.W8) {  // fp8: unsplit, one of the four fp8 tiles
-    p.splits = 1; p.kb_per_split = p.nkb;
-    tile = 24 + ((p.flags & GF_GEGLU) ? (p.M >= 512 ? 0 : 3) : (p.M >= 512 ? 0 : 2));
-  }
-  if ((p.flags & GF_GNAPPLY) && (p.flags & GF_CONV3)) { tile = (p.Hi * p.Wi <= 256) ? 14 : 12; p.splits = 1; p.kb_per_split = p.nkb; }  // halo kernel only
+  int sp = p.splits;
+  if (p.W8) { tile = 24 + ((p.flags & GF_GEGLU) ? (p.M >= 512 ? 0 : 3) : (p.M >= 512 ? 0 : 2)); sp = 1; }  // fp8: unsplit, one of the four fp8 tiles
+  if ((p.flags & GF_GNAPPLY) && (p.flags & GF_CONV3)) { tile = (p.Hi * p.Wi <= 256) ? 14 : 12; sp = 1; }  // halo kernel only
   if ((p.flags & GF_GNAPPLY) && !(p.flags & GF_CONV3)) {  // dense: GroupNorm on the resident fragments of lnlin_kernel, nothing else applies it
-    tile = DTP_TILE_LNLIN; p.splits = 1; p.kb_per_split = p.nkb;
-    const int pick = lnlin_default_ranges(p);
-    if (!pick) { dtp_set_error("push_gemm: no lnlin configuration for the GroupNorm-on-load Linear (M %d N %d K %d)", p.M, p.N, p.K); return DTP_ERR_ARG; }
-    p.col_ranges = pick;
+    tile = DTP_TILE_LNLIN;
+    sp = lnlin_default_ranges(p);
+    if (!sp) { dtp_set_error("push_gemm: no lnlin configuration for the GroupNorm-on-load Linear (M %d N %d K %d)", p.M, p.N, p.K); return DTP_ERR_ARG; }
   }
-  if (c->autotune) RC(tune_gemm(c, p, &tile));
+  if (c->autotune) RC(tune_gemm(c, p, &tile, &sp));
+  (void)dtp_tile_apply(p, tile, sp);
+  const DtpTile t = dtp_tile(tile);
   if (emit) {  // the consumer must know how many partials this launch configuration writes per row
-    int bm = 0, bn = 128, ns = 0;
-    (void)dtp_gemm_tile_dims(tile, &bm, &bn, &ns);
-    if (tile == DTP_TILE_GEMMWS) bn = 64;
-    emit->parts = tile == DTP_TILE_LNLIN ? p.col_ranges : p.splits > 1 ? 1 : (p.N + bn - 1) / bn;
+    emit->parts = dtp_tile_row_parts(p, tile);
     emit->M = p.M * (p.batch > 1 ? p.batch : 1);
   }
   c->ws_need = std::max(c->ws_need, dtp_gemm_workspace_bytes(p));
@@ -1030,17 +990,16 @@ int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg,
   const double nb = p.batch > 1 ? (double)p.batch : 1.0;
   const double bytes = 2.0 * nb * (a_elems + (double)p.N * k_alg + (double)p.M * n_out);
   char lab[160];
-  const bool f8tile = tile >= 24 && tile < 32;  // an fp8 problem may have kept an fp16 tile (tune_gemm)
+  const bool f8tile = t.fam == TF_FP8;  // an fp8 problem may have kept an fp16 tile (tune_gemm)
   snprintf(lab, sizeof(lab), "%s M=%d N=%d K=%d tile=%d splits=%d%s%s%s%s", (p.flags & GF_CONV3) ? "conv3" : "gemm", p.M, p.N, p.K, tile,
-           tile == DTP_TILE_LNLIN ? p.col_ranges : p.splits, (p.flags & GF_UPS2) ? " ups" : "", (p.flags & GF_GEGLU) ? (f8tile ? " geglu fp8" : " geglu") : (f8tile ? " fp8" : ""), p.stride == 2 ? " s2" : "",
+           t.split == SPLIT_COLS ? p.col_ranges : p.splits, (p.flags & GF_UPS2) ? " ups" : "", (p.flags & GF_GEGLU) ? (f8tile ? " geglu fp8" : " geglu") : (f8tile ? " fp8" : ""), p.stride == 2 ? " s2" : "",
            p.batch > 1 ? (" x" + std::to_string(p.batch)).c_str() : "");
-  const int kind = tile == DTP_TILE_GEMMWS ? PK_GEMMWS : dtp_is_ws_tile(tile) ? PK_WS0 + tile - DTP_TILE_WS0 : tile == DTP_TILE_LNLIN ? PK_LNLIN : tile >= 48 ? PK_HALO3 + tile - 48 : tile >= 40 ? PK_LW + tile - 40 : tile >= 32 ? PK_KH2 + tile - 32 : tile >= 24 ? PK_FP8 : tile >= 20 ? PK_WIDE0 + tile - 20 : tile >= 16 ? PK_BIG0 + tile - 16 : tile >= 12 ? PK_HALO0 + tile - 12 : PK_GEMM0 + tile;
   const double flops = 2.0 * nb * p.M * (double)p.N * k_alg;
-  prog_push(c, prog, kind, flops, bytes, make_gemm_op(c, p, tile, bias_step_off), lab);
-  if (p.splits > 1 || (dtp_is_ws_tile(tile) && tile >= DTP_TILE_WS0 + 2)) {  // a GroupNorm pushed next may take over the reduce (Builder::gn) -- or, behind an unsplit
+  prog_push(c, prog, t.pk, flops, bytes, make_gemm_op(c, p, tile, bias_step_off), lab);
+  if (p.splits > 1 || (t.fam == TF_CONVWS && t.var >= 2)) {  // a GroupNorm pushed next may take over the reduce (Builder::gn) -- or, behind an unsplit
     LastGemm& lg = prog->last_gemm;                // two-n-tile convws launch, get its statistics from the conv's epilogue (claim_stats)
     lg.valid = true; lg.p = p; lg.tile = tile; lg.bias_step_off = bias_step_off; lg.op_index = prog->ops.size() - 1;
-    lg.kind = kind; lg.flops = flops; lg.bytes = bytes; lg.label = lab;
+    lg.kind = t.pk; lg.flops = flops; lg.bytes = bytes; lg.label = lab;
   }
   return DTP_OK;
 }

@@ -782,25 +782,6 @@ void dtp_gemm_init() {  // raise the dynamic-LDS limit once, outside any stream 
 #undef SET_ATTR3
 }
 
-static void lw_variant(int tile, int* ns, int* lw) {  // tile 40..47
-  *ns = 3; *lw = tile < 44 ? 4 : 8;
-}
-
-// 20 / 21: gemm_wide_kernel 256 x 256 / 256 x 320 (gemm_wide.hip).  24..27: gemm_fp8_kernel, the shapes of ids 0..3 (gemm_fp8.hip).
-// tile id -> (BM, BN, pipeline depth).  0..11: shape (id & 3) of {128x128, 128x64, 64x64, 64x128} at depth 2 + id / 4;
-// 16..19: the big tiles {256x128, 256x128, 128x256, 128x256} at depth {2, 3, 2, 3}.  (12..15 are the halo conv kernels.)
-bool dtp_gemm_tile_dims(int tile, int* bm, int* bn, int* ns) {
-  static const int sm[4] = {128, 128, 64, 64}, sn[4] = {128, 64, 64, 128};
-  if (tile >= 0 && tile < 12) { *bm = sm[tile & 3]; *bn = sn[tile & 3]; *ns = 2 + (tile >> 2); return true; }
-  if (tile >= 16 && tile < 20) { *bm = tile < 18 ? 256 : 128; *bn = tile < 18 ? 128 : 256; *ns = 2 + (tile & 1); return true; }
-  if (tile == 20 || tile == 21) { *bm = 256; *bn = tile == 20 ? 256 : 320; *ns = 2; return true; }  // gemm_wide_kernel (8 waves)
-  if (tile >= 24 && tile < 28) { *bm = sm[tile & 3]; *bn = sn[tile & 3]; *ns = 2; return true; }     // gemm_fp8_kernel
-  if (tile == 28) { *bm = 256; *bn = 256; *ns = 2; return true; }                                    // gemm_fp8_kernel, 8 waves
-  if (tile >= 32 && tile < 40) { *bm = sm[tile & 3]; *bn = sn[tile & 3]; *ns = 2 + ((tile - 32) >> 2); return true; }  // gemm_kernel, 8 waves (KH = 2)
-  if (tile >= 40 && tile < 48) { int lw; *bm = sm[tile & 3]; *bn = sn[tile & 3]; lw_variant(tile, ns, &lw); return true; }  // gemm_kernel with loader waves
-  return false;
-}
-
 size_t dtp_gemm_workspace_bytes(const GemmParams& p) {
   return p.splits > 1 ? (size_t)p.splits * p.M * p.N * sizeof(float) : 0;
 }
@@ -831,11 +812,33 @@ void dtp_gemm_pick(GemmParams& p, int* tile, int num_cu) {
   *tile = t;
 }
 
-int dtp_launch_gemm(const GemmParams& p, int tile, hipStream_t s) {
+// the first checks of dtp_launch_gemm, which the wide and fp8 tiles pass before their own
+static int gemm_family_args(const GemmParams& p) {
   if (p.nkb <= 0 || p.M <= 0 || p.N <= 0) { dtp_set_error("gemm: empty problem"); return DTP_ERR_ARG; }
   if (p.flags & GF_GNAPPLY) { dtp_set_error("gemm: GroupNorm-on-the-staged-patch is a conv_halo_kernel feature (tile ids 12..15)"); return DTP_ERR_ARG; }
-  if (tile == 20 || tile == 21) return dtp_launch_gemm_wide(p, tile - 20, s);
-  if (tile >= 24 && tile <= 28) return dtp_launch_gemm_fp8(p, tile - 24, s);
+  return DTP_OK;
+}
+
+int dtp_launch_tile(const GemmParams& p, int tile, hipStream_t s) {
+  const DtpTile t = dtp_tile(tile);
+  switch (t.fam) {
+    case TF_HALO: return dtp_launch_conv_halo(p, t.var, s);
+    case TF_LNLIN: return dtp_launch_lnlin(p, p.col_ranges, s);
+    case TF_CONVWS: return dtp_launch_conv_ws(p, t.var, s);
+    case TF_GEMMWS: return dtp_launch_gemm_ws(p, s);
+    case TF_WIDE:
+    case TF_FP8: {
+      const int rc = gemm_family_args(p);
+      if (rc != DTP_OK) return rc;
+      return t.fam == TF_WIDE ? dtp_launch_gemm_wide(p, t.var, s) : dtp_launch_gemm_fp8(p, t.var, s);
+    }
+    default: return dtp_launch_gemm(p, tile, s);  // TF_GEMM; a hole fails there, after the argument checks, as a bad tile id
+  }
+}
+
+int dtp_launch_gemm(const GemmParams& p, int tile, hipStream_t s) {
+  const int arc = gemm_family_args(p);
+  if (arc != DTP_OK) return arc;
   if ((p.lda & 7) || (p.ldw & 7)) { dtp_set_error("gemm: lda/ldw must be multiples of 8"); return DTP_ERR_ARG; }
   {  // the DMA addresses rows by 32-bit byte offsets into 2 GiB buffer descriptors
     const size_t a_rows = (p.flags & GF_CONV3) ? (size_t)(p.M / (p.Ho * p.Wo) + 1) * p.Hi * p.Wi : (size_t)p.M;
@@ -869,29 +872,25 @@ int dtp_launch_gemm(const GemmParams& p, int tile, hipStream_t s) {
     dtp_set_error("gemm: LayerNorm fold needs a dense, unsplit GEMM with lns");
     return DTP_ERR_ARG;
   }
-  int bm = 0, bn = 0, ns = 0;
-  if (!dtp_gemm_tile_dims(tile, &bm, &bn, &ns)) { dtp_set_error("gemm: bad tile id %d", tile); return DTP_ERR_ARG; }
-  if ((p.flags & GF_GEGLU) && (p.splits > 1 || bn != 128 || (p.N % 128))) {
+  const DtpTile t = dtp_tile(tile);
+  if (t.fam != TF_GEMM) { dtp_set_error("gemm: bad tile id %d", tile); return DTP_ERR_ARG; }
+  if ((p.flags & GF_GEGLU) && (p.splits > 1 || t.bn != 128 || (p.N % 128))) {
     dtp_set_error("gemm: GEGLU needs a 128-wide N tile, N %% 128 == 0 and no split-K");
     return DTP_ERR_ARG;
   }
   int rc = -1;
 #define DISPATCH(BM, BN, NS) \
-  if (rc < 0 && bm == BM && bn == BN && ns == NS) rc = launch_tile<BM, BN, NS>(p, s);
-  if (tile < 32) { FOR_ALL_VARIANTS(DISPATCH) }
+  if (rc < 0 && t.kh == 1 && !t.lw && t.bm == BM && t.bn == BN && t.ns == NS) rc = launch_tile<BM, BN, NS>(p, s);
+  FOR_ALL_VARIANTS(DISPATCH)
 #undef DISPATCH
 #define DISPATCH2(BM, BN, NS) \
-  if (rc < 0 && bm == BM && bn == BN && ns == NS) rc = launch_tile<BM, BN, NS, 2>(p, s);
-  if (tile >= 32 && tile < 40) { FOR_ALL_KH2(DISPATCH2) }
+  if (rc < 0 && t.kh == 2 && t.bm == BM && t.bn == BN && t.ns == NS) rc = launch_tile<BM, BN, NS, 2>(p, s);
+  FOR_ALL_KH2(DISPATCH2)
 #undef DISPATCH2
-  if (tile >= 40) {
-    int lns, lw;
-    lw_variant(tile, &lns, &lw);
 #define DISPATCH3(BM, BN, NS, LW) \
-    if (rc < 0 && bm == BM && bn == BN && lns == NS && lw == LW) rc = launch_tile<BM, BN, NS, 1, LW>(p, s);
-    FOR_ALL_LW(DISPATCH3)
+  if (rc < 0 && t.lw == LW && t.bm == BM && t.bn == BN && t.ns == NS) rc = launch_tile<BM, BN, NS, 1, LW>(p, s);
+  FOR_ALL_LW(DISPATCH3)
 #undef DISPATCH3
-  }
   if (rc != DTP_OK) { dtp_set_error("gemm launch failed: %s", hipGetErrorString(hipGetLastError())); return rc; }
   if (p.splits > 1 && !(p.flags & GF_NOREDUCE)) return dtp_launch_splitk_reduce(p, s);
   return DTP_OK;

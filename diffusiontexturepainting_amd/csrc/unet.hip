@@ -461,7 +461,7 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
     auto plain = [&](GemmParams g, int tile) {
       g.zero = c->zero; g.splits = 1; g.kb_per_split = g.nkb;
       const double nb = g.batch > 1 ? g.batch : 1;
-      b.push(PK_GEMM0 + tile, 2.0 * nb * g.M * (double)g.N * g.K, 2.0 * nb * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N),
+      b.push(dtp_tile(tile).pk, 2.0 * nb * g.M * (double)g.N * g.K, 2.0 * nb * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N),
              [=](hipStream_t s, int) { return dtp_launch_gemm(g, tile, s); });
     };
     for (const XfW* w : xfs) {
