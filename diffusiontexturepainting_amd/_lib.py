@@ -75,12 +75,14 @@ SYMBOLS = {
     "dtp_get_conditioning": (_i, [_vp, _vp, _vp, _vp]),
     "dtp_stamp": (_i, [_vp, _vp, C.POINTER(Settings), _vp, _vp, _vp, _i, _vp]),
     "dtp_stamp_slots": (_i, [_vp, _vp, C.POINTER(Settings), _vp, _vp, _vp, _i, C.POINTER(_i), _vp]),
+    "dtp_stamp_mixed": (_i, [_vp, _vp, C.POINTER(Settings), _vp, _vp, _vp, _i, C.POINTER(_i), _vp]),
     "dtp_set_brush_slot": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
     "dtp_set_conditioning_slot": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "dtp_get_conditioning_slot": (_i, [_vp, _i, _vp, _vp, _vp]),
     "dtp_ddim_tables": (_i, [_i, C.POINTER(_i64), C.POINTER(_f), C.POINTER(_f)]),
     "dtp_last_stamp_times": (_i, [_vp, C.POINTER(_f * 3)]),
     "dtp_last_stamp_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
+    "dtp_last_stamp_unet_rows": (_i, [_vp, C.POINTER(_i)]),
     "dtp_profile": (_i, [_vp, _i]),
     "dtp_profile_rows": (_i, [_vp, C.POINTER(ProfRow), _i, C.POINTER(_i)]),
     "dtp_profile_dump": (_i, [_vp, C.c_char_p]),
@@ -115,6 +117,7 @@ SYMBOLS = {
     "dtp_op_softmax_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _f, _vp]),
     "dtp_op_attention_fp8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _f, _f, _vp]),
     "dtp_op_dilate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "dtp_op_dilate_pads": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
 }
 
 

@@ -167,7 +167,7 @@ constexpr float DTP_FP8_MARGIN = 2.0f;        // head-room over the calibration 
 constexpr int DTP_FP8_OPERANDS_MIN_K = 1280;  // option fp8_operands: transformer Linears with K >= this contract two e4m3 operands (gemm_f8f8.hip)
 
 struct UNetProg {
-  int N = 0;          // UNet batch (3B or 2B)
+  int N = 0;          // UNet batch (2B + k: k texture-guided rows, 0 <= k <= B)
   size_t cal_begin = 0, cal_end = 0;  // this program's records in Ctx::fp8_cals
   bool fp8_calibrated = false;
   Prog kv, main;
@@ -182,11 +182,11 @@ struct UNetProg {
   std::vector<f16*> xW1, xW2;
   std::vector<float*> xb1, xl1;
   f16 *kexp = nullptr, *vexp = nullptr;  // scratch [N*128][1280]
-  // validity of ctx16 / the per-stamp cross-attention matrices: the layout [uncond x B | cond x (NB-1)B] depends on the
-  // (B, NB) split, not only on N = NB*B (B=2,NB=3 and B=3,NB=2 share a program)
+  // validity of ctx16 / the per-stamp cross-attention matrices: the layout [uncond x B | cond x B | cond x k] depends on the
+  // (B, k) split, not only on N = 2B + k (B=2,k=2 and B=3,k=0 share a program when the prefix is not de-duplicated)
   unsigned long long kv_ver = 0;
-  int kv_B = 0, kv_NB = 0;
-  std::vector<int> kv_slots;                       // conditioning slot of every stamp the K/V were built for
+  int kv_B = 0, kv_k = 0;
+  std::vector<int> kv_slots;                       // conditioning slot of every cond row [B + n] the K/V were built for (B + k entries)
   std::vector<unsigned long long> kv_slot_ver;     // ... and the version of that slot at the time
 };
 struct VaeEncProg {
@@ -217,6 +217,23 @@ struct StampGraph {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   int nodes = 0;
+  unsigned long long used = 0;  // Ctx::graph_clock at the last replay (LRU of the denoise-loop graphs)
+};
+// Captured denoise-loop graphs kept per context.  A loop graph is keyed by (B, steps, the sorted per-stamp tg_evals profile), and
+// batches of stamps with different guidance settings produce many profiles: the least recently replayed one is destroyed beyond this.
+constexpr int DTP_LOOP_GRAPH_CAP = 16;
+
+// Device parameter block the captured stamp kernels read.  The per-stamp part is written by a kernel whose ARGUMENTS carry the
+// values (set_header_kernel): dtp_stamp never stages through host memory, and a captured loop is replayed for any cfg / tg values.
+constexpr int DTP_STAMP_MAXB = 64;  // = the largest max_batch dtp_create accepts
+struct StampCoefs {
+  float cfg[DTP_STAMP_MAXB], tg[DTP_STAMP_MAXB];  // per stamp: cfg_weight, tg_weight
+  int order[DTP_STAMP_MAXB];  // the UNet's texture-guided row 2B + j belongs to stamp order[j] (stamps by descending tg_evals)
+  int rank[DTP_STAMP_MAXB];   // inverse of order: stamp b owns tg row 2B + rank[b] while rank[b] < k (k = tg rows of the program)
+};
+struct StampParams {
+  StampCoefs coef;
+  float sched[4 * 1000];  // per evaluation: sqrt(1 - a_t), sqrt(a_t), sqrt(a_prev), sqrt(1 - a_prev)
 };
 
 struct Ctx {
@@ -264,7 +281,7 @@ struct Ctx {
   float* x32 = nullptr;       // [maxB][h][w][4] current latent (fp32, NHWC)
   float* canvas32 = nullptr;  // [maxB][4][R][R] copy of the canvas (for compositing inside the graph-free tail)
   float* alpha_tmp = nullptr; // dilation scratch [2][maxB][R][R]
-  float* stamp_params = nullptr;  // device: per-step DDIM coefficients + weights
+  StampParams* stamp_params = nullptr;  // device: per-stamp guidance weights + row map, per-step DDIM coefficients
   std::map<int, StampBufs> stamp_bufs;  // keyed by stamp batch B; the buffers live in `persistent` and die with the context
   IencBufs ienc_bufs;
   int* finite_flag = nullptr;     // device: set to 1 by the post-loop finiteness check ("check_finite" option)
@@ -285,9 +302,10 @@ struct Ctx {
   int fp8_nslots = 0;
   bool calibrating = false;
   bool finite_pending = false;    // the last stamp ran the check; dtp_last_stamp_finite reads the flag
-  std::map<long long, StampGraph> graphs;
+  std::map<std::vector<long long>, StampGraph> graphs;  // key[0]: stage and batch; the loop stage appends the tg_evals profile
+  unsigned long long graph_clock = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  int last_evals = 0, last_nodes = 0;
+  int last_evals = 0, last_nodes = 0, last_unet_rows = 0;
   bool use_graph = true;
   bool exec_imgenc_ready = false;
   bool profile = false;

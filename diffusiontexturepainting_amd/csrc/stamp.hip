@@ -3,6 +3,7 @@
 // Reference: trt_inference/trt_model.py:90-121, handler.py:25-33,55-56, model_base.py:51-58,
 // inpaint_pipeline.py:39-153, stable_diffusion_pipeline.py:340-355,407-484, utilities.py:370-529.
 #include <math.h>
+#include <algorithm>
 #include <stdio.h>
 #include <string.h>
 
@@ -81,26 +82,29 @@ extern "C" int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, flo
 // ---------------------------------------------------------------- kernels
 namespace {
 
-// separable flat dilation (kornia.morphology.dilation with ones(pad,pad), geodesic border):
-// out[i] = max over [i - pad/2, i + pad - pad/2 - 1] clipped to the image.
-__global__ void dilate_row_kernel(const float* __restrict__ canvas, float* __restrict__ tmp, int B, int R, int lo, int hi) {
+// separable flat dilation (kornia.morphology.dilation with ones(pad,pad), geodesic border), each stamp with its own pad:
+// out[i] = max over [i - lo[b], i + hi[b]] clipped to the image, lo = pad/2, hi = pad - pad/2 - 1.
+struct PadArgs { int lo[DTP_STAMP_MAXB], hi[DTP_STAMP_MAXB]; };
+__global__ void dilate_row_kernel(const float* __restrict__ canvas, float* __restrict__ tmp, int B, int R, PadArgs pa) {
   const long long total = (long long)B * R * R;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int x = (int)(i % R);
     const long long by = i / R;
     const int y = (int)(by % R), b = (int)(by / R);
+    const int lo = pa.lo[b], hi = pa.hi[b];
     const float* a = canvas + ((size_t)b * 4 + 3) * R * R + (size_t)y * R;
     float m = -1e4f;
     for (int xx = max(0, x - lo); xx <= min(R - 1, x + hi); ++xx) m = fmaxf(m, a[xx]);
     tmp[i] = m;
   }
 }
-__global__ void dilate_col_kernel(const float* __restrict__ tmp, float* __restrict__ out, int B, int R, int lo, int hi) {
+__global__ void dilate_col_kernel(const float* __restrict__ tmp, float* __restrict__ out, int B, int R, PadArgs pa) {
   const long long total = (long long)B * R * R;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int x = (int)(i % R);
     const long long by = i / R;
     const int y = (int)(by % R), b = (int)(by / R);
+    const int lo = pa.lo[b], hi = pa.hi[b];
     const float* a = tmp + (size_t)b * R * R + x;
     float m = -1e4f;
     for (int yy = max(0, y - lo); yy <= min(R - 1, y + hi); ++yy) m = fmaxf(m, a[(size_t)yy * R]);
@@ -142,10 +146,11 @@ __global__ void prep_kernel(const float* __restrict__ canvas, const float* __res
   }
 }
 
-// UNet input assembly (inpaint_pipeline.py:116,136; sdp:423-427): branch-major [uncond|cond|tg] x B.
+// UNet input assembly (inpaint_pipeline.py:116,136; sdp:423-427): branch-major [uncond x B | cond x B | tg x k]; stamp b has the
+// texture-guided row 2B + rank[b] while rank[b] < k (StampCoefs).
 __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float* __restrict__ masks,
-                                const float* __restrict__ ml, f16* __restrict__ in16, float* __restrict__ x32, int B, int HWl,
-                                int NB) {
+                                const float* __restrict__ ml, const int* __restrict__ rank, f16* __restrict__ in16,
+                                float* __restrict__ x32, int B, int HWl, int k) {
   const long long total = (long long)B * HWl;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int b = (int)(i / HWl), p = (int)(i - (long long)b * HWl);
@@ -156,11 +161,14 @@ __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float*
         x[ch] = lat_nchw[((size_t)b * 4 + ch) * HWl + p];  // * init_noise_sigma (= 1.0)
         x32[i * 4 + ch] = x[ch];
       } else {
-        x[ch] = x32[i * 4 + ch];  // mid-loop switch to the 2-branch program: keep the running latent
+        x[ch] = x32[i * 4 + ch];  // mid-loop switch to a program with fewer tg rows: keep the running latent
       }
     }
+    const int r = rank[b];
+    const int NB = r < k ? 3 : 2;
     for (int br = 0; br < NB; ++br) {
       const int src = (br < 2) ? b : B + b;  // branches 0,1: masked image; branch 2: context image
+      const int row = (br < 2) ? br * B + b : 2 * B + r;
       f16x8 lo, hi;
 #pragma unroll
       for (int ch = 0; ch < 4; ++ch) lo[ch] = (f16)x[ch];
@@ -171,7 +179,7 @@ __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float*
       hi[0] = (f16)ml[((size_t)src * 4 + 3) * HWl + p];
 #pragma unroll
       for (int ch = 1; ch < 8; ++ch) hi[ch] = (f16)0.f;
-      f16* o = in16 + ((size_t)(br * B + b) * HWl + p) * 16;
+      f16* o = in16 + ((size_t)row * HWl + p) * 16;
       *(f16x8*)o = lo;
       *(f16x8*)(o + 8) = hi;
     }
@@ -179,26 +187,34 @@ __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float*
 }
 
 // guidance combine + DDIM eta=0 step + refresh of the latent channels of the UNet input
-// (sdp:419-420,449-455; utilities.py:463-503).  params: [0]=cfg [1]=tg [2]=tg_steps, then 4 per step.
+// (sdp:419-420,449-455; utilities.py:463-503).  Stamp b uses its own cfg / tg; its texture-guided branch is row 2B + rank[b] of a
+// program with k tg rows, present while rank[b] < k, i.e. while step_index < its tg_evals (the stamps are ordered by descending tg_evals).
 __global__ void step_kernel(const float* __restrict__ eps_out, float* __restrict__ x32, f16* __restrict__ in16,
-                            const float* __restrict__ params, int step_index, int B, int HWl, int NB) {
-  const float cfg = params[0];
-  const float tg = ((float)step_index > params[2] - 1.0f) ? 0.f : params[1];
-  const float* k = params + 4 + 4 * step_index;
-  const float sqrt_beta_t = k[0], sqrt_alpha_t = k[1], sqrt_alpha_prev = k[2], sqrt_beta_prev = k[3];
+                            const StampParams* __restrict__ params, int step_index, int B, int HWl, int k) {
+  const float* kc = params->sched + 4 * step_index;
+  const float sqrt_beta_t = kc[0], sqrt_alpha_t = kc[1], sqrt_alpha_prev = kc[2], sqrt_beta_prev = kc[3];
   const long long total = (long long)B * HWl * 4;
   const size_t bs = (size_t)B * HWl * 4;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int b = (int)(i / ((long long)HWl * 4));
+    const long long j = i - (long long)b * HWl * 4;  // element within the stamp
+    const int r = params->coef.rank[b];
+    const float cfg = params->coef.cfg[b];
     const float u = eps_out[i], c = eps_out[bs + i];
     float e = u + cfg * (c - u);
-    if (NB == 3) e += tg * (eps_out[2 * bs + i] - c);
+    if (r < k) e += params->coef.tg[b] * (eps_out[(2 * (size_t)B + r) * HWl * 4 + j] - c);
     const float x = x32[i];
     const float x0 = (x - sqrt_beta_t * e) / sqrt_alpha_t;
-    const float xn = sqrt_alpha_prev * x0 + sqrt_beta_prev * e;
+    float xn = sqrt_alpha_prev * x0 + sqrt_beta_prev * e;
     x32[i] = xn;
-    const long long pix = i >> 2;
+    // the fp16 copies are the rounded fp32 latent: keep the compiler from fusing the last fma into the conversion (v_fma_mix*_f16
+    // rounds the exact product once, i.e. differently)
+    asm volatile("" : "+v"(xn));
+    const long long pix = i >> 2, p = j >> 2;
     const int ch = (int)(i & 3);
-    for (int br = 0; br < NB; ++br) in16[((size_t)br * B * HWl + pix) * 16 + ch] = (f16)xn;
+    in16[((size_t)pix) * 16 + ch] = (f16)xn;
+    in16[((size_t)B * HWl + pix) * 16 + ch] = (f16)xn;
+    if (r < k) in16[((2 * (size_t)B + r) * HWl + p) * 16 + ch] = (f16)xn;
   }
 }
 
@@ -220,15 +236,16 @@ __global__ void finish_kernel(const float* __restrict__ dec, const float* __rest
   }
 }
 
-// ctx16[n][14][768]: branch 0 <- uncond, branches 1.. <- cond  (inpaint_pipeline.py:140), each from the stamp's own slot
-__global__ void build_ctx_kernel(const float* __restrict__ cond_slots, const int* __restrict__ slot_map, f16* __restrict__ ctx16, int B,
-                                 int NB) {
+// ctx16[n][14][768]: rows [0, B) <- uncond, [B, 2B) <- cond, the tg rows 2B + j <- cond of stamp order[j] (inpaint_pipeline.py:140),
+// each from the stamp's own slot
+__global__ void build_ctx_kernel(const float* __restrict__ cond_slots, const int* __restrict__ slot_map, const int* __restrict__ order,
+                                 f16* __restrict__ ctx16, int B, int N) {
   const int per = 14 * 768;
-  const long long total = (long long)NB * B * per;
+  const long long total = (long long)N * per;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int n = (int)(i / per), j = (int)(i - (long long)n * per);
-    const int br = n / B, b = n - br * B;
-    ctx16[i] = (f16)cond_slots[(size_t)slot_map[b] * 2 * per + (br == 0 ? per : 0) + j];
+    const int b = n < 2 * B ? n % B : order[n - 2 * B];
+    ctx16[i] = (f16)cond_slots[(size_t)slot_map[b] * 2 * per + (n < B ? per : 0) + j];
   }
 }
 
@@ -238,10 +255,11 @@ __global__ void set_slots_kernel(int* __restrict__ dst, SlotArgs a, int B) {
   if ((int)threadIdx.x < B) dst[threadIdx.x] = a.s[threadIdx.x];
 }
 
-// cfg / tg / tg_steps travel as kernel ARGUMENTS into the device parameter block the captured step kernels read: no host
-// staging buffer, so dtp_stamp never has to wait for the stream
-__global__ void set_header_kernel(float* __restrict__ params, float cfg, float tg, float tg_steps) {
-  if (threadIdx.x == 0) { params[0] = cfg; params[1] = tg; params[2] = tg_steps; params[3] = 0.f; }
+// the per-stamp cfg / tg and the tg row map travel as kernel ARGUMENTS into the device parameter block the captured kernels read:
+// no host staging buffer, so dtp_stamp never has to wait for the stream
+__global__ void set_header_kernel(StampCoefs* __restrict__ dst, StampCoefs a) {
+  constexpr int words = (int)(sizeof(StampCoefs) / 4);
+  for (int t = threadIdx.x; t < words; t += blockDim.x) ((int*)dst)[t] = ((const int*)&a)[t];
 }
 
 // post-loop finiteness guard (the reference asserts `not isnan` after every step, stable_diffusion_pipeline.py:415, at the
@@ -268,7 +286,7 @@ int stamp_init(Ctx* c) {
   RC(ctx_persistent(c, c->maxB * hw * 4 * 4, &p, true)); c->x32 = (float*)p;
   RC(ctx_persistent(c, c->maxB * 4 * RR * 4, &p, true)); c->canvas32 = (float*)p;
   RC(ctx_persistent(c, 2 * c->maxB * RR * 4, &p, true)); c->alpha_tmp = (float*)p;
-  RC(ctx_persistent(c, (4 + 4 * 1000) * 4, &p, true)); c->stamp_params = (float*)p;
+  RC(ctx_persistent(c, sizeof(StampParams), &p, true)); c->stamp_params = (StampParams*)p;
   RC(ctx_persistent(c, (size_t)DTP_MAX_SLOTS * 2 * 14 * 768 * 4, &p, true)); c->cond32 = (float*)p;
   RC(ctx_persistent(c, (size_t)DTP_MAX_SLOTS * 3 * RR * 4, &p, true)); c->brush32 = (float*)p;
   RC(ctx_persistent(c, 64 * sizeof(int), &p, true)); c->slot_map = (int*)p;
@@ -292,12 +310,32 @@ static int get_bufs(Ctx* c, int B, StampBufs** out) {
   return DTP_OK;
 }
 
-// run `body` on stream s, replaying a captured hipGraph when possible
+static void destroy_graph(StampGraph& g) {
+  if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  if (g.graph) (void)hipGraphDestroy(g.graph);
+}
+
+// run `body` on stream s, replaying a captured hipGraph when possible.  `loop`: a denoise-loop graph, of which the context keeps the
+// DTP_LOOP_GRAPH_CAP most recently replayed
 template <class F>
-static int run_stage(Ctx* c, long long key, hipStream_t s, F body) {
+static int run_stage(Ctx* c, const std::vector<long long>& key, bool loop, hipStream_t s, F body) {
   if (!c->use_graph || c->profile || s == nullptr) return body(s);
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) {
+    if (loop) {
+      int n = 0;
+      auto lru = c->graphs.end();
+      for (auto g = c->graphs.begin(); g != c->graphs.end(); ++g) {
+        if (g->first[0] >> 60 != 2) continue;
+        ++n;
+        if (lru == c->graphs.end() || g->second.used < lru->second.used) lru = g;
+      }
+      if (n >= DTP_LOOP_GRAPH_CAP) {  // (rare: a new profile; its capture costs far more than this wait)
+        HIP_CHECK(hipDeviceSynchronize());  // the evicted graph may still be replaying
+        destroy_graph(lru->second);
+        c->graphs.erase(lru);
+      }
+    }
     StampGraph g;
     HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     const int rc = body(s);
@@ -310,21 +348,40 @@ static int run_stage(Ctx* c, long long key, hipStream_t s, F body) {
     HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
     it = c->graphs.emplace(key, g).first;
   }
+  it->second.used = ++c->graph_clock;
   c->last_nodes += it->second.nodes;
   HIP_CHECK(hipGraphLaunch(it->second.exec, s));
   return DTP_OK;
 }
 
+static PadArgs pad_args(const int* pads, int B) {
+  PadArgs pa = {};
+  for (int b = 0; b < B; ++b) { pa.lo[b] = pads[b] / 2; pa.hi[b] = pads[b] - pads[b] / 2 - 1; }
+  return pa;
+}
+
 extern "C" {
 
-// kernel-level entry point: the separable flat dilation of add_extra_context (handler.py:28-29) on the alpha plane of a canvas
-int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s_) {
-  if (!canvas || !tmp || !out || B < 1 || R < 1 || pad < 1) { dtp_set_error("dtp_op_dilate: bad argument"); return DTP_ERR_ARG; }
+// kernel-level entry points: the separable flat dilation of add_extra_context (handler.py:28-29) on the alpha plane of a canvas,
+// with one pad for all B images / one pad per image
+int dtp_op_dilate_pads(const float* canvas, float* tmp, float* out, int B, int R, const int* pads, dtp_stream s_) {
+  if (!canvas || !tmp || !out || !pads || B < 1 || B > DTP_STAMP_MAXB || R < 1) { dtp_set_error("dtp_op_dilate: bad argument (B=%d, max %d)", B, DTP_STAMP_MAXB); return DTP_ERR_ARG; }
+  for (int b = 0; b < B; ++b)
+    if (pads[b] < 1) { dtp_set_error("dtp_op_dilate: pad %d of image %d must be >= 1", pads[b], b); return DTP_ERR_ARG; }
   hipStream_t s = (hipStream_t)s_;
-  const int lo = pad / 2, hi = pad - pad / 2 - 1;
-  hipLaunchKernelGGL(dilate_row_kernel, dim3(nblk((long long)B * R * R)), dim3(256), 0, s, canvas, tmp, B, R, lo, hi);
-  hipLaunchKernelGGL(dilate_col_kernel, dim3(nblk((long long)B * R * R)), dim3(256), 0, s, tmp, out, B, R, lo, hi);
+  const PadArgs pa = pad_args(pads, B);
+  hipLaunchKernelGGL(dilate_row_kernel, dim3(nblk((long long)B * R * R)), dim3(256), 0, s, canvas, tmp, B, R, pa);
+  hipLaunchKernelGGL(dilate_col_kernel, dim3(nblk((long long)B * R * R)), dim3(256), 0, s, tmp, out, B, R, pa);
   return LAUNCH_OK();
+}
+
+int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s) {
+  if (!canvas || !tmp || !out || B < 1 || R < 1 || pad < 1) { dtp_set_error("dtp_op_dilate: bad argument"); return DTP_ERR_ARG; }
+  const std::vector<int> pads(DTP_STAMP_MAXB, pad);
+  const size_t RR = (size_t)R * R;
+  for (int b0 = 0; b0 < B; b0 += DTP_STAMP_MAXB)
+    RC(dtp_op_dilate_pads(canvas + b0 * 4 * RR, tmp + b0 * RR, out + b0 * RR, std::min(B - b0, DTP_STAMP_MAXB), R, pads.data(), s));
+  return DTP_OK;
 }
 
 int dtp_finalize_weights(dtp_ctx* ctx) {
@@ -394,6 +451,14 @@ int dtp_stamp(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const f
 }
 
 int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                    void* out, int B, const int* slots, dtp_stream s) {
+  if (!st || B < 1 || B > DTP_STAMP_MAXB) return dtp_stamp_mixed(ctx, canvas, st, latents, vae_eps, out, B, slots, s);  // (its checks)
+  dtp_settings each[DTP_STAMP_MAXB];
+  for (int b = 0; b < B; ++b) each[b] = *st;
+  return dtp_stamp_mixed(ctx, canvas, each, latents, vae_eps, out, B, slots, s);
+}
+
+int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
                     void* out, int B, const int* slots, dtp_stream s_) {
   Ctx* c = (Ctx*)ctx;
   hipStream_t s = (hipStream_t)s_;
@@ -406,21 +471,52 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     if (!c->slot_set[sl]) { dtp_set_error("dtp_stamp: no brush set in slot %d (call dtp_set_brush / dtp_set_conditioning)", sl); return DTP_ERR_STATE; }
     sa.s[b] = sl;
   }
-  if (st->steps < 2 || st->steps > 999) { dtp_set_error("dtp_stamp: steps=%d outside 2..999", st->steps); return DTP_ERR_ARG; }
-  if (st->context_pad < 1) { dtp_set_error("dtp_stamp: context_pad must be >= 1"); return DTP_ERR_ARG; }
-  HIP_CHECK(hipSetDevice(c->device));
+  for (int b = 0; b < B; ++b) {
+    if (st[b].steps < 2 || st[b].steps > 999) { dtp_set_error("dtp_stamp: steps=%d of stamp %d outside 2..999", st[b].steps, b); return DTP_ERR_ARG; }
+    if (st[b].context_pad < 1) { dtp_set_error("dtp_stamp: context_pad=%d of stamp %d must be >= 1", st[b].context_pad, b); return DTP_ERR_ARG; }
+    if (st[b].steps != st[0].steps || st[b].composite != st[0].composite || st[b].output_u8 != st[0].output_u8) {
+      dtp_set_error("dtp_stamp: stamp %d has steps=%d composite=%d output_u8=%d, stamp 0 has %d/%d/%d (these are per call)", b, st[b].steps,
+                    st[b].composite, st[b].output_u8, st[0].steps, st[0].composite, st[0].output_u8);
+      return DTP_ERR_ARG;
+    }
+  }
   const int R = c->R, h = c->h, HW = R * R, HWl = h * h;
-  const int steps = st->steps, E = steps - 1;
-  // the third (texture-guided) branch contributes nothing once its coefficient is 0: skip it (bit-identical)
-  const int tg_evals = (st->tg_weight == 0.0f) ? 0 : std::max(0, std::min(E, st->tg_steps));
+  const int steps = st[0].steps, E = steps - 1;
+  // Per stamp: the third (texture-guided) branch contributes nothing once its coefficient is 0: skip it (bit-identical).  The stamps are
+  // ordered by descending tg_evals (a stable order: a uniform batch keeps the identity), and evaluation i runs the UNet on
+  // [uncond x B | cond x B | tg x k_i] with k_i = #{b : tg_evals_b > i}: finished stamps leave the batch.
+  int tg_evals[DTP_STAMP_MAXB];
+  StampCoefs coef = {};
+  for (int b = 0; b < B; ++b) {
+    tg_evals[b] = (st[b].tg_weight == 0.0f) ? 0 : std::max(0, std::min(E, st[b].tg_steps));
+    coef.cfg[b] = st[b].cfg_weight;
+    coef.tg[b] = st[b].tg_weight;
+    coef.order[b] = b;
+  }
+  std::stable_sort(coef.order, coef.order + B, [&](int x, int y) { return tg_evals[x] > tg_evals[y]; });
+  std::vector<long long> loop_key = {((long long)B << 32) | ((long long)steps << 12) | (2LL << 60)};
+  for (int j = 0; j < B; ++j) { coef.rank[coef.order[j]] = j; loop_key.push_back(tg_evals[coef.order[j]]); }
+  std::vector<int> ks(E);  // k_i
+  for (int i = 0; i < E; ++i) {
+    int k = 0;
+    while (k < B && tg_evals[coef.order[k]] > i) ++k;
+    ks[i] = k;
+  }
+  if ((c->fp8_linear || c->fp8_attention || c->fp8_operands) && loop_key[1] != loop_key[B]) {
+    // the fp8 options calibrate each program once, for a batch whose stamps all take the same branches
+    dtp_set_error("dtp_stamp: stamps with different texture-guidance evaluations (tg_evals %lld..%lld) cannot share a batch under the fp8 options",
+                  loop_key[B], loop_key[1]);
+    return DTP_ERR_STATE;
+  }
+  HIP_CHECK(hipSetDevice(c->device));
 
-  UNetProg *u3 = nullptr, *u2 = nullptr;
+  UNetProg* prog[DTP_STAMP_MAXB + 1] = {};  // by k
   VaeEncProg* enc;
   VaeDecProg* dec;
   StampBufs* sb;
   // branches 0 (uncond) and 1 (cond) see identical samples: the programs evaluate the UNet prefix once for both (unet.hip, struct Dup)
-  if (tg_evals > 0) RC(get_unet_prog(c, 3 * B, B, &u3));
-  if (tg_evals < E) RC(get_unet_prog(c, 2 * B, B, &u2));
+  for (int i = 0; i < E; ++i)
+    if (!prog[ks[i]]) RC(get_unet_prog(c, 2 * B + ks[i], B, &prog[ks[i]]));
   RC(get_enc_prog(c, 2 * B, &enc));
   RC(get_dec_prog(c, B, &dec));
   RC(get_bufs(c, B, &sb));
@@ -444,31 +540,37 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
       k[4 * i + 2] = sqrtf(a_prev);
       k[4 * i + 3] = sqrtf(1.0f - a_prev);
     }
-    HIP_CHECK(hipMemcpy(c->stamp_params + 4, k.data(), k.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(c->stamp_params->sched, k.data(), k.size() * 4, hipMemcpyHostToDevice));
     c->sched_steps = steps;
   }
-  hipLaunchKernelGGL(set_header_kernel, dim3(1), dim3(64), 0, s, c->stamp_params, st->cfg_weight, st->tg_weight, (float)st->tg_steps);
+  hipLaunchKernelGGL(set_header_kernel, dim3(1), dim3(256), 0, s, &c->stamp_params->coef, coef);
   hipLaunchKernelGGL(set_slots_kernel, dim3(1), dim3(64), 0, s, c->slot_map, sa, B);
 
-  // ---- cross-attention K/V for the current brush
-  for (UNetProg* up : {u3, u2}) {
+  // ---- cross-attention K/V for the current brushes
+  for (int k = 0; k <= B; ++k) {
+    UNetProg* up = prog[k];
     if (!up) continue;
-    const int NB = up->N / B;
-    // the cached per-stamp matrices are valid for exactly this (B, NB) split, these slots and these slot versions
-    bool valid = up->kv_ver != 0 && up->kv_B == B && up->kv_NB == NB && (int)up->kv_slots.size() == B;
-    for (int b = 0; valid && b < B; ++b) valid = up->kv_slots[b] == sa.s[b] && up->kv_slot_ver[b] == c->slot_version[sa.s[b]];
+    // the cached per-stamp matrices are valid for exactly this (B, k) split, the slots of the cond rows and these slot versions
+    std::vector<int> rows(sa.s, sa.s + B);
+    for (int j = 0; j < k; ++j) rows.push_back(sa.s[coef.order[j]]);
+    bool valid = up->kv_ver != 0 && up->kv_B == B && up->kv_k == k && up->kv_slots == rows;
+    for (size_t n = 0; valid && n < rows.size(); ++n) valid = up->kv_slot_ver[n] == c->slot_version[rows[n]];
     if (!valid) {
-      hipLaunchKernelGGL(build_ctx_kernel, dim3(nblk((long long)up->N * 14 * 768)), dim3(256), 0, s, c->cond32, c->slot_map, up->ctx16, B, NB);
+      hipLaunchKernelGGL(build_ctx_kernel, dim3(nblk((long long)up->N * 14 * 768)), dim3(256), 0, s, c->cond32, c->slot_map,
+                         c->stamp_params->coef.order, up->ctx16, B, up->N);
       RC(up->kv.run(s, 0));
-      up->kv_ver = c->cond_version; up->kv_B = B; up->kv_NB = NB;
-      up->kv_slots.assign(sa.s, sa.s + B);
-      up->kv_slot_ver.resize(B);
-      for (int b = 0; b < B; ++b) up->kv_slot_ver[b] = c->slot_version[sa.s[b]];
+      up->kv_ver = c->cond_version; up->kv_B = B; up->kv_k = k;
+      up->kv_slot_ver.resize(rows.size());
+      for (size_t n = 0; n < rows.size(); ++n) up->kv_slot_ver[n] = c->slot_version[rows[n]];
+      up->kv_slots = std::move(rows);
     }
   }
 
   c->last_nodes = 0;
   c->last_evals = E;
+  c->last_unet_rows = 0;
+  for (int i = 0; i < E; ++i) c->last_unet_rows += 2 * B + ks[i];
+  const int* rank = c->stamp_params->coef.rank;
   RoctxRange whole("dtp_stamp");
   HIP_CHECK(hipEventRecord(c->ev[0], s));
   // ---- stage 0: pre-processing + both VAE encodes (one batch-2B pass)
@@ -477,48 +579,52 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   HIP_CHECK(hipMemcpyAsync(sb->lat, latents, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
   if (vae_eps) HIP_CHECK(hipMemcpyAsync(sb->eps, vae_eps, (size_t)2 * B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(c->canvas32, canvas, (size_t)B * 4 * HW * 4, hipMemcpyDeviceToDevice, s));
-  const int lo = st->context_pad / 2, hi = st->context_pad - st->context_pad / 2 - 1;
-  hipLaunchKernelGGL(dilate_row_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, c->canvas32, c->alpha_tmp, B, R, lo, hi);
+  int pads[DTP_STAMP_MAXB];
+  for (int b = 0; b < B; ++b) pads[b] = st[b].context_pad;
+  const PadArgs pa = pad_args(pads, B);
+  hipLaunchKernelGGL(dilate_row_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, c->canvas32, c->alpha_tmp, B, R, pa);
   hipLaunchKernelGGL(dilate_col_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, c->alpha_tmp,
-                     c->alpha_tmp + (size_t)c->maxB * HW, B, R, lo, hi);
-  const int first_nb = tg_evals > 0 ? 3 : 2;
-  UNetProg* first = tg_evals > 0 ? u3 : u2;
-  RC(run_stage(c, ((long long)B << 32) | (vae_eps ? 2 : 0) | (first_nb == 3 ? 1 : 0) | (1LL << 60), s, [&](hipStream_t q) -> int {
+                     c->alpha_tmp + (size_t)c->maxB * HW, B, R, pa);
+  const int k0 = ks[0];
+  UNetProg* first = prog[k0];
+  RC(run_stage(c, {((long long)B << 32) | ((long long)k0 << 4) | (vae_eps ? 2 : 0) | (k0 > 0 ? 1 : 0) | (1LL << 60)}, false, s,
+               [&](hipStream_t q) -> int {
     hipLaunchKernelGGL(prep_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, q, c->canvas32, c->brush32, c->slot_map,
                        c->alpha_tmp + (size_t)c->maxB * HW, enc->in8, sb->masks, B, R);
     RC(enc->main.run(q, 0));
     RC(launch_vae_sample(c, enc->moments, vae_eps ? sb->eps : nullptr, sb->ml, 2 * B, VAE_SCALE, q));
-    hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, sb->lat, sb->masks, sb->ml, first->in16,
-                       c->x32, B, HWl, first_nb);
+    hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, sb->lat, sb->masks, sb->ml, rank, first->in16,
+                       c->x32, B, HWl, k0);
     return LAUNCH_OK();
   }));
   }
   HIP_CHECK(hipEventRecord(c->ev[1], s));
-  // fp8 (configs[4]): the first stamp of a program measures its activation ranges once, before the loop is captured
+  // fp8 (configs[4]): the first stamp of a program measures its activation ranges once, before the loop is captured.  (Under these
+  // options every stamp of the batch has the same tg_evals: the programs are the 3B one for the first evaluations, the 2B one after.)
   if ((c->fp8_linear || c->fp8_attention || c->fp8_operands)) {
+    UNetProg *u3 = prog[B], *u2 = prog[0];
     if (u3 && !u3->fp8_calibrated) RC(fp8_calibrate(c, u3, s, 0));
     if (u2 && !u2->fp8_calibrated) {
-      if (tg_evals > 0)  // (u2 is not the first program:) its input is normally assembled where the loop switches programs: do it now, from the initial latents
-        hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, s, (const float*)nullptr, sb->masks, sb->ml, u2->in16,
-                           c->x32, B, HWl, 2);
+      if (ks[0] > 0)  // (u2 is not the first program:) its input is normally assembled where the loop switches programs: do it now, from the initial latents
+        hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, s, (const float*)nullptr, sb->masks, sb->ml, rank,
+                           u2->in16, c->x32, B, HWl, 0);
       RC(fp8_calibrate(c, u2, s, 0));
     }
   }
   // ---- stage 1: the denoise loop
   {
   RoctxRange r1("dtp_stamp: denoise loop (unet)");
-  RC(run_stage(c, ((long long)B << 32) | ((long long)steps << 12) | tg_evals | (2LL << 60), s, [&](hipStream_t q) -> int {
+  RC(run_stage(c, loop_key, true, s, [&](hipStream_t q) -> int {
     for (int i = 0; i < E; ++i) {
-      UNetProg* up = (i < tg_evals) ? u3 : u2;
-      const int NB = (i < tg_evals) ? 3 : 2;
-      if (i == tg_evals && i > 0) {
-        // switching to the 2-branch program: its input needs mask/masked-latent channels + current x
+      UNetProg* up = prog[ks[i]];
+      if (i > 0 && ks[i] != ks[i - 1]) {
+        // switching to a program with fewer tg rows: its input needs mask/masked-latent channels + current x
         hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, (const float*)nullptr, sb->masks,
-                           sb->ml, up->in16, c->x32, B, HWl, 2);
+                           sb->ml, rank, up->in16, c->x32, B, HWl, ks[i]);
       }
       RC(up->main.run(q, i));
       hipLaunchKernelGGL(step_kernel, dim3(nblk((long long)B * HWl * 4)), dim3(256), 0, q, up->out32, c->x32, up->in16,
-                         c->stamp_params, i, B, HWl, NB);
+                         c->stamp_params, i, B, HWl, ks[i]);
     }
     return LAUNCH_OK();
   }));
@@ -527,12 +633,12 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   // ---- stage 2: latents / 0.18215 -> VAE decode -> clamp (+ composite, u8)
   {
   RoctxRange r2("dtp_stamp: vae decode + post-processing");
-  RC(run_stage(c, ((long long)B << 32) | (3LL << 60), s, [&](hipStream_t q) -> int {
+  RC(run_stage(c, {((long long)B << 32) | (3LL << 60)}, false, s, [&](hipStream_t q) -> int {
     RC(launch_post_quant(c, c->x32, 1, 1.0f / VAE_SCALE, dec->in8, B, q));
     return dec->main.run(q, 0);
   }));
   hipLaunchKernelGGL(finish_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, dec->out32, c->canvas32, out, B, HW,
-                     st->composite, st->output_u8);
+                     st[0].composite, st[0].output_u8);
   }
   c->finite_pending = c->check_finite;
   if (c->check_finite) {
@@ -627,10 +733,7 @@ int dtp_set_option(dtp_ctx* ctx, const char* name, int value) {
   }
   if (!strcmp(name, "dedupe_prefix")) {  // programs are keyed by it: switching only affects which (cached) program a stamp uses
     c->dedupe_prefix = value != 0;
-    for (auto& g : c->graphs) {  // captured stages hold the old program's launches
-      if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-      if (g.second.graph) (void)hipGraphDestroy(g.second.graph);
-    }
+    for (auto& g : c->graphs) destroy_graph(g.second);  // captured stages hold the old program's launches
     c->graphs.clear();
     return DTP_OK;
   }
@@ -667,6 +770,13 @@ int dtp_last_stamp_info(dtp_ctx* ctx, int* unet_evals, int* graph_nodes) {
   if (!c) return DTP_ERR_ARG;
   if (unet_evals) *unet_evals = c->last_evals;
   if (graph_nodes) *graph_nodes = c->last_nodes;
+  return DTP_OK;
+}
+
+int dtp_last_stamp_unet_rows(dtp_ctx* ctx, int* rows) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c || !rows) return DTP_ERR_ARG;
+  *rows = c->last_unet_rows;
   return DTP_OK;
 }
 

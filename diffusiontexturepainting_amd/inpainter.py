@@ -148,7 +148,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             self.image = img.unsqueeze(0)
             self.conditioning = (ce.unsqueeze(0), ue.unsqueeze(0))
 
-    def _stamp(self, canvas, settings, composite, latents=None, vae_eps=None, output_u8=False, slots=None):
+    def _stamp(self, canvas, settings, composite, latents=None, vae_eps=None, output_u8=False, slots=None, per_stamp=None):
         if not self._slots:
             raise _lib.DtpError("no brush set: call set_brush() first")
         R, h = self._resolution, self._resolution // 8
@@ -159,6 +159,12 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         s = {**DEFAULT_SETTINGS, **{k: v for k, v in settings.items() if k in DEFAULT_SETTINGS}}
         st = Settings(int(s["steps"]), int(s["context_pad"]), int(s["tg_steps"]), float(s["cfg_weight"]), float(s["tg_weight"]),
                       int(composite), int(output_u8))  # numpy scalars are cast here (server_io.py:104-119)
+        if per_stamp is not None:
+            if len(per_stamp) != B:
+                raise ValueError(f"{len(per_stamp)} per_stamp entries for {B} stamps")
+            each = [{**s, **{k: v for k, v in d.items() if k in DEFAULT_SETTINGS}} for d in per_stamp]
+            st = (Settings * B)(*[Settings(int(e["steps"]), int(e["context_pad"]), int(e["tg_steps"]), float(e["cfg_weight"]),
+                                           float(e["tg_weight"]), int(composite), int(output_u8)) for e in each])
         if latents is None:
             latents = torch.randn((B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
         if vae_eps is None:
@@ -168,11 +174,15 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         out = (torch.empty(B, R, R, 3, dtype=torch.uint8, device=self._device) if output_u8
                else torch.empty(B, 3, R, R, dtype=torch.float32, device=self._device))
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
-        if slots is None:
+        if slots is not None and len(slots) != B:
+            raise ValueError(f"{len(slots)} slots for {B} stamps")
+        if per_stamp is not None:
+            arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
+            check(self._lib.dtp_stamp_mixed(self._h, ptr(canvas), st, ptr(latents), ptr(vae_eps), ptr(out), B, arr, self._s()),
+                  "dtp_stamp_mixed")
+        elif slots is None:
             check(self._lib.dtp_stamp(self._h, ptr(canvas), C.byref(st), ptr(latents), ptr(vae_eps), ptr(out), B, self._s()), "dtp_stamp")
         else:
-            if len(slots) != B:
-                raise ValueError(f"{len(slots)} slots for {B} stamps")
             arr = (C.c_int * B)(*[int(v) for v in slots])
             check(self._lib.dtp_stamp_slots(self._h, ptr(canvas), C.byref(st), ptr(latents), ptr(vae_eps), ptr(out), B, arr, self._s()),
                   "dtp_stamp_slots")
@@ -185,20 +195,21 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
         return out
 
-    def generate_raw(self, canvas, latents=None, vae_eps=None, slots=None, **settings):
+    def generate_raw(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, **settings):
         """canvas B x 4 x R x R 0..1 -> B x 3 x R x R 0..1 (trt_model.py:90-121).  `latents`
         ([B,4,h,w]) / `vae_eps` ([2,B,4,h,w]; False = use the latent mean) override the internal
-        generator -- the parity tests feed CPU-generated noise through them."""
-        return self._stamp(canvas, settings, composite=False, latents=latents, vae_eps=vae_eps, slots=slots)
+        generator -- the parity tests feed CPU-generated noise through them.  `per_stamp`: one dict of setting overrides per stamp
+        (context_pad, tg_steps, cfg_weight, tg_weight), merged over `settings` and the defaults; `steps` must agree across the batch."""
+        return self._stamp(canvas, settings, composite=False, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp)
 
-    def generate(self, canvas, latents=None, vae_eps=None, slots=None, **settings):
+    def generate(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, **settings):
         """generate_raw + alpha composite (model_base.py:51-58), fused into the final kernel.  `slots`: one conditioning slot per
-        stamp of the batch (stamps of different clients / brushes in one call); None = slot 0 for all."""
-        return self._stamp(canvas, settings, composite=True, latents=latents, vae_eps=vae_eps, slots=slots)
+        stamp of the batch (stamps of different clients / brushes in one call); None = slot 0 for all.  `per_stamp`: see generate_raw."""
+        return self._stamp(canvas, settings, composite=True, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp)
 
-    def generate_u8(self, canvas, composite=True, slots=None, **settings):
+    def generate_u8(self, canvas, composite=True, slots=None, per_stamp=None, **settings):
         """Same as generate() but returns the handler's wire image: uint8 HWC, truncated (handler.py:55-56)."""
-        return self._stamp(canvas, settings, composite=composite, output_u8=True, slots=slots)
+        return self._stamp(canvas, settings, composite=composite, output_u8=True, slots=slots, per_stamp=per_stamp)
 
     def stage_times_ms(self):
         """[vae_encoder x2 + pre, denoise loop, vae + post] GPU ms of the last stamp (print_summary, sdp:486-503)."""
@@ -210,6 +221,12 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         a, b = C.c_int(), C.c_int()
         check(self._lib.dtp_last_stamp_info(self._h, C.byref(a), C.byref(b)), "dtp_last_stamp_info")
         return dict(unet_evals=a.value, graph_nodes=b.value)
+
+    def stamp_unet_rows(self):
+        """UNet rows the last stamp evaluated, summed over its evaluations (2B per evaluation + one per stamp still texture-guided)."""
+        n = C.c_int()
+        check(self._lib.dtp_last_stamp_unet_rows(self._h, C.byref(n)), "dtp_last_stamp_unet_rows")
+        return n.value
 
     def profile(self, enable):
         """Bracket every kernel launch with HIP events (graph replay off) / switch back."""

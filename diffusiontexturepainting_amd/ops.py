@@ -405,3 +405,17 @@ def dilate_alpha(canvas, pad):
     out = torch.empty(b, 1, r, r, dtype=torch.float32, device=canvas.device)
     check(lib.dtp_op_dilate(ptr(canvas), ptr(tmp), ptr(out), b, r, int(pad), _stream()), "dilate")
     return out
+
+
+def dilate_alpha_pads(canvas, pads):
+    """dilate_alpha with one pad per image (pads: B ints), in one launch pair as a mixed-settings stamp runs it."""
+    lib = _lib.load()
+    b, _, r, _ = canvas.shape
+    if len(pads) != b:
+        raise ValueError(f"{len(pads)} pads for {b} images")
+    canvas = canvas.contiguous().float()
+    tmp = torch.empty(b, r, r, dtype=torch.float32, device=canvas.device)
+    out = torch.empty(b, 1, r, r, dtype=torch.float32, device=canvas.device)
+    arr = (C.c_int * b)(*[int(p) for p in pads])
+    check(lib.dtp_op_dilate_pads(ptr(canvas), ptr(tmp), ptr(out), b, r, arr, _stream()), "dilate")
+    return out

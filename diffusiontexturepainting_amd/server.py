@@ -12,7 +12,11 @@ things a multi-client deployment needs:
     previous result, kit_app .../ui/brush.py:185-194), so ONE client never has two stamps in flight; DIFFERENT clients are
     independent.  The queue collects the stamps that are pending at the same time, groups those with equal inference
     settings and runs each group as one batched call (the B <= max_batch launch programs), every stamp conditioned on its
-    own client's brush through a conditioning slot.
+    own client's brush through a conditioning slot.  With `mixed_settings=True` (and a model whose generate() takes
+    `per_stamp`) the stamps are grouped by `steps` only: every stamp of the batch runs with its own client's context_pad,
+    cfg_weight, tg_weight and tg_steps (dtp_stamp_mixed), so clients who moved their sliders still share a batch.  Gathering
+    still stops at a brush change, a slot release, a stamp with other `steps` or a second stamp of a client already in the
+    batch.  Off by default: the grouping is then exactly the equal-settings rule.
   * `StampServer` -- routes every new client to the least-loaded replica (one model / process-local GPU each) and keeps it
     there (its brush lives in that replica's slot table).
   * error replies -- the reference logs an exception and sends nothing (handler.py:83-89), which leaves the Kit client waiting
@@ -23,6 +27,7 @@ Nothing here touches the GPU directly: the model only has to provide resolution(
 slot_image(slot) / generate(canvas, slots=[...], **settings) -- MI355ConditionalInpainter does, and so do the CPU fakes of the
 tests.
 """
+import inspect
 import logging
 import queue
 import struct
@@ -90,12 +95,25 @@ def _settings_key(s):
     return tuple((k, float(s[k])) for k in ("steps", "context_pad", "tg_steps", "cfg_weight", "tg_weight") if k in s)
 
 
+def _steps_key(s):
+    return float(s["steps"]) if "steps" in s else None
+
+
+def _takes_per_stamp(model):
+    """Whether model.generate accepts per-stamp settings (MI355ConditionalInpainter does; older models and fakes may not)."""
+    try:
+        return "per_stamp" in inspect.signature(model.generate).parameters
+    except (TypeError, ValueError):
+        return False
+
+
 class StampQueue:
     """Work queue of ONE replica (one model on one GPU).  A worker thread drains it: brush changes run alone (they re-encode
     a slot), stamps pending at the same time are grouped by settings and batched."""
 
-    def __init__(self, model, max_batch=8, error_replies=False, gather_window_s=0.002, n_slots=16, post=None):
+    def __init__(self, model, max_batch=8, error_replies=False, gather_window_s=0.002, n_slots=16, post=None, mixed_settings=False):
         self.model, self.max_batch, self.error_replies, self.window = model, int(max_batch), error_replies, gather_window_s
+        self.mixed = bool(mixed_settings) and _takes_per_stamp(model)  # batch stamps whose settings differ (all but `steps`)
         self.post = post               # post(reply_fn, data): how a reply leaves the worker thread (None: call reply_fn here)
         self.q = queue.Queue()
         self.front = []                # requests taken off the queue while gathering a batch that did not belong to it: served first
@@ -214,7 +232,11 @@ class StampQueue:
         try:
             m = self.model
             canvas = torch.stack([j.payload for j in jobs]).to(m.device())            # handler.py:106, batched
-            result = m.generate(canvas, slots=[j.slot for j in jobs], **jobs[0].settings).cpu()  # :107
+            if any(_settings_key(j.settings) != _settings_key(jobs[0].settings) for j in jobs):  # (mixed_settings only)
+                result = m.generate(canvas, slots=[j.slot for j in jobs], per_stamp=[dict(j.settings) for j in jobs],
+                                    **jobs[0].settings).cpu()
+            else:
+                result = m.generate(canvas, slots=[j.slot for j in jobs], **jobs[0].settings).cpu()  # :107
             self.batch_sizes.append(len(jobs))
         except Exception as e:
             if len(jobs) == 1:
@@ -258,12 +280,16 @@ class StampQueue:
             # Gather the stamps that are pending right now (plus a short window for stamps that are about to arrive).  Gathering
             # stops at the FIRST request that does not belong to the batch, of any kind: a stamp with other settings, a brush
             # change or a slot release must not overtake -- or be overtaken by -- anything of its own client, so it is served
-            # next, in arrival order (it goes to `front`, never back to the tail of the queue).
+            # next, in arrival order (it goes to `front`, never back to the tail of the queue).  With mixed settings a stamp
+            # belongs to the batch when its `steps` agree and its client has no stamp in the batch yet (the client's next stamp is
+            # rendered from the previous result: it is never batched with it).
             pending = [job]
             try:
                 while len(pending) < self.max_batch:
                     nxt = self._next(timeout=self.window)
-                    if nxt is not None and nxt.kind == "stamp" and _settings_key(nxt.settings) == _settings_key(job.settings):
+                    if nxt is not None and nxt.kind == "stamp" and (
+                            _settings_key(nxt.settings) == _settings_key(job.settings) if not self.mixed else
+                            _steps_key(nxt.settings) == _steps_key(job.settings) and all(p.slot != nxt.slot for p in pending)):
                         pending.append(nxt)
                     else:
                         self.front.insert(0, nxt)  # including the shutdown sentinel: it is seen right after this batch
@@ -277,9 +303,10 @@ class StampServer:
     """Front of N replicas.  `on_message(client_id, message, write_message)` is the whole per-connection protocol
     (handler.py:78-123); `close_client` frees the client's slot."""
 
-    def __init__(self, models, max_batch=8, error_replies=False, gather_window_s=0.002, post=None):
-        self.queues = [StampQueue(m, max_batch=max_batch, error_replies=error_replies, gather_window_s=gather_window_s, post=post)
-                       for m in models]
+    def __init__(self, models, max_batch=8, error_replies=False, gather_window_s=0.002, post=None, mixed_settings=False):
+        """mixed_settings: batch stamps whose guidance settings differ (see the module docstring); off = equal settings only."""
+        self.queues = [StampQueue(m, max_batch=max_batch, error_replies=error_replies, gather_window_s=gather_window_s, post=post,
+                                  mixed_settings=mixed_settings) for m in models]
         self.post = post
         self.route = {}  # client id -> queue index
         self.error_replies = error_replies

@@ -104,6 +104,17 @@ int dtp_stamp(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const f
  * of slot slots[b] (its conditioning tokens and its hint image, trt_model.py:103-114); everything else is shared. */
 int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
                     void* out, int B, const int* slots, dtp_stream s);
+/* The same with one dtp_settings per stamp: st = host dtp_settings[B].  Stamp b gets exactly what dtp_stamp computes for it alone
+ * with st[b]: its own context_pad (dilation window), cfg_weight, tg_weight and tg_steps.  steps, composite and output_u8 are per call:
+ * DTP_ERR_ARG, naming the stamp, when they differ.  Every entry gets dtp_stamp's checks (steps 2..999, context_pad >= 1).
+ * Stamp b evaluates the texture-guided branch for its first tg_evals_b = (tg_weight_b == 0 ? 0 : clamp(tg_steps_b, 0, steps - 1))
+ * evaluations; the UNet batch of evaluation i is 2B + #{b : tg_evals_b > i}, so a stamp whose guidance has ended costs two rows, not
+ * three.  Programs are built per (B, tg rows) on first use, and the denoise loop is captured once per (B, steps, sorted tg_evals
+ * profile); the context keeps the 16 most recently used loop graphs.  Any cfg / tg values replay the same graph.  Under the fp8
+ * options (fp8_attention, fp8_linear, fp8_operands), which calibrate one program per batch shape, the stamps of a batch must share
+ * tg_evals: DTP_ERR_STATE otherwise.  dtp_stamp and dtp_stamp_slots are this call with st[0] applied to every stamp. */
+int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                    void* out, int B, const int* slots, dtp_stream s);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
@@ -116,6 +127,8 @@ int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, float* final_a
 int dtp_last_stamp_times(dtp_ctx* ctx, float ms[3]);
 /* number of UNet evaluations / kernel launches captured for the last stamp */
 int dtp_last_stamp_info(dtp_ctx* ctx, int* unet_evals, int* graph_nodes);
+/* UNet rows (samples) the last stamp evaluated, summed over its evaluations: sum_i (2B + tg rows of evaluation i) */
+int dtp_last_stamp_unet_rows(dtp_ctx* ctx, int* rows);
 
 /* ---------------------------------------------------------------- measurement
  * dtp_profile(ctx, 1): from now on every kernel launch of the engines is bracketed by HIP events on
@@ -334,6 +347,8 @@ int dtp_op_softmax_rows(const void* x, int ldx, void* y, int ldy, int rows, int 
 /* kornia.morphology.dilation(alpha, ones(pad,pad)) of add_extra_context (handler.py:28-29) as the stamp runs it: canvas f32
  * [B,4,R,R] (the alpha plane is read), tmp / out f32 [B,R,R]; window rows/cols [i - pad/2, i + pad - pad/2 - 1], clipped */
 int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s);
+/* the same with one pad per image (host int pads[B], B <= 64), as dtp_stamp_mixed runs it */
+int dtp_op_dilate_pads(const float* canvas, float* tmp, float* out, int B, int R, const int* pads, dtp_stream s);
 
 #ifdef __cplusplus
 }
