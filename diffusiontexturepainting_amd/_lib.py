@@ -9,6 +9,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DTP_LIB") or os.path.join(_HERE, "libdtp.so")  # DTP_LIB: A/B another build of the same ABI
 _lib = None
 MAX_SLOTS = 16  # DTP_MAX_SLOTS
+# samplers of the stamp loop by the reference's names (stable_diffusion_pipeline.py:115-127): DTP_SCHED_* of include/dtp.h
+SCHEDULERS = {"DDIM": 0, "DPM": 1, "LMSD": 2}
+SCHED_ROW = 8  # DTP_SCHED_ROW
+
+
+def scheduler_id(name):
+    """DTP_SCHED_* of a scheduler name; ValueError naming the supported set for anything else (EulerA and PNDM are not ported)."""
+    if name not in SCHEDULERS:
+        raise ValueError(f"scheduler {name!r} is not supported: choose one of {', '.join(SCHEDULERS)}")
+    return SCHEDULERS[name]
 
 
 class DtpError(RuntimeError):
@@ -118,6 +128,8 @@ SYMBOLS = {
     "dtp_op_attention_fp8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _f, _f, _vp]),
     "dtp_op_dilate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "dtp_op_dilate_pads": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
+    "dtp_scheduler_tables": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
+    "dtp_op_sched_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -219,7 +219,7 @@ struct StampGraph {
   int nodes = 0;
   unsigned long long used = 0;  // Ctx::graph_clock at the last replay (LRU of the denoise-loop graphs)
 };
-// Captured denoise-loop graphs kept per context.  A loop graph is keyed by (B, steps, the sorted per-stamp tg_evals profile), and
+// Captured denoise-loop graphs kept per context.  A loop graph is keyed by (B, steps, scheduler, the sorted per-stamp tg_evals profile), and
 // batches of stamps with different guidance settings produce many profiles: the least recently replayed one is destroyed beyond this.
 constexpr int DTP_LOOP_GRAPH_CAP = 16;
 
@@ -233,7 +233,9 @@ struct StampCoefs {
 };
 struct StampParams {
   StampCoefs coef;
-  float sched[4 * 1000];  // per evaluation: sqrt(1 - a_t), sqrt(a_t), sqrt(a_prev), sqrt(1 - a_prev)
+  float sched[DTP_SCHED_ROW * 1000];  // per evaluation: the scheduler's coefficient row (dtp_scheduler_tables, include/dtp.h)
+  float in_scale[1001];               // per evaluation: scale_model_input of the latent channels (entry E: 1)
+  float init_sigma;                   // init_noise_sigma: the initial latent is latents * init_sigma
 };
 
 struct Ctx {
@@ -266,6 +268,8 @@ struct Ctx {
   f16* temb_sin = nullptr;   // [rows][320]
   f16 *temb_h1 = nullptr, *temb_h2 = nullptr;  // [rows][1280]
   int sched_steps = -1;      // step count the table/coefficients were built for
+  int sched_kind = -1;       // ... and scheduler (DTP_SCHED_*)
+  int scheduler = DTP_SCHED_DDIM;  // option "scheduler": the sampler of the next stamp
 
   // conditioning
   // conditioning SLOTS: one brush per slot (a client of the multi-client server); slot 0 is what the single-brush entry
@@ -279,6 +283,7 @@ struct Ctx {
 
   // stamp state
   float* x32 = nullptr;       // [maxB][h][w][4] current latent (fp32, NHWC)
+  float* hist32 = nullptr;    // [3][B][h][w][4] sampler history of a B-stamp batch (DPM: previous x0; LMSD: the last three derivatives)
   float* canvas32 = nullptr;  // [maxB][4][R][R] copy of the canvas (for compositing inside the graph-free tail)
   float* alpha_tmp = nullptr; // dilation scratch [2][maxB][R][R]
   StampParams* stamp_params = nullptr;  // device: per-stamp guidance weights + row map, per-step DDIM coefficients

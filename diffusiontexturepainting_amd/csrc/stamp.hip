@@ -49,15 +49,12 @@ void dtp_gemm_fp8_init();
 #define VAE_SCALE 0.18215f
 
 // ---------------------------------------------------------------- DDIM tables (host, fp32 like torch)
-// utilities.py:383-388 (betas, cumprod), :432-439 (timesteps), :416 (gather), :397 (final alpha).
-extern "C" int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, float* final_alpha) {
-  // the largest timestep is (steps-1)*(1000/steps) + 1: steps = 1000 would index alphas_cumprod[1000] (the reference raises
-  // IndexError there, utilities.py:416)
-  if (steps < 1 || steps > 999) { dtp_set_error("ddim: steps %d outside 1..999", steps); return DTP_ERR_ARG; }
-  const int T = 1000;
+// alphas_cumprod of the scaled-linear beta schedule every sampler shares (utilities.py:383-388, :283-285, :684-688)
+static const float* alphas_cumprod() {
   static float full[1000];
   static bool have = false;
   if (!have) {
+    const int T = 1000;
     const float start = (float)sqrt(0.00085), end = (float)sqrt(0.012);
     const float step = (end - start) / (float)(T - 1);
     double acc = 1.0;  // torch's CPU cumprod accumulates float in double and rounds every output
@@ -69,6 +66,16 @@ extern "C" int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, flo
     }
     have = true;
   }
+  return full;
+}
+
+// utilities.py:432-439 (timesteps), :416 (gather), :397 (final alpha).
+extern "C" int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, float* final_alpha) {
+  // the largest timestep is (steps-1)*(1000/steps) + 1: steps = 1000 would index alphas_cumprod[1000] (the reference raises
+  // IndexError there, utilities.py:416)
+  if (steps < 1 || steps > 999) { dtp_set_error("ddim: steps %d outside 1..999", steps); return DTP_ERR_ARG; }
+  const int T = 1000;
+  const float* full = alphas_cumprod();
   const int ratio = T / steps;
   for (int i = 0; i < steps; ++i) {
     const int64_t t = (int64_t)(steps - 1 - i) * ratio + 1;
@@ -76,6 +83,118 @@ extern "C" int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, flo
     if (alphas) alphas[i] = full[t];
   }
   if (final_alpha) *final_alpha = full[0];
+  return DTP_OK;
+}
+
+// ---------------------------------------------------------------- schedule tables of every sampler (host)
+static int sched_evals(int scheduler, int steps) { return scheduler == DTP_SCHED_DDIM ? steps - 1 : steps; }
+
+// integral over [a, b] of prod_{m != j} (tau - s[m]) / (s[j] - s[m]) (m, j < n <= 4): the Lagrange basis polynomial is expanded
+// into monomials and integrated exactly (the reference integrates it numerically, scipy quad with epsrel 1e-4: utilities.py:330-341)
+static double lagrange_integral(const double* s, int n, int j, double a, double b) {
+  double p[4] = {1.0, 0.0, 0.0, 0.0};  // p[d]: coefficient of tau^d
+  int deg = 0;
+  for (int m = 0; m < n; ++m) {
+    if (m == j) continue;
+    const double inv = 1.0 / (s[j] - s[m]);
+    for (int d = deg + 1; d >= 0; --d) p[d] = ((d > 0 ? p[d - 1] : 0.0) - s[m] * p[d]) * inv;
+    ++deg;
+  }
+  double r = 0.0;
+  for (int d = 0; d <= deg; ++d) r += p[d] * (pow(b, d + 1) - pow(a, d + 1)) / (d + 1);
+  return r;
+}
+
+extern "C" int dtp_scheduler_tables(int scheduler, int steps, int* evals, float* init_sigma, float* timesteps, float* in_scale,
+                                    float* coefs) {
+  if (scheduler != DTP_SCHED_DDIM && scheduler != DTP_SCHED_DPM && scheduler != DTP_SCHED_LMSD) {
+    dtp_set_error("scheduler tables: unknown scheduler %d (DDIM = 0, DPM = 1, LMSD = 2)", scheduler);
+    return DTP_ERR_ARG;
+  }
+  if (steps < 2 || steps > 999) { dtp_set_error("scheduler tables: steps %d outside 2..999", steps); return DTP_ERR_ARG; }
+  const int E = sched_evals(scheduler, steps), W = DTP_SCHED_ROW;
+  const float* full = alphas_cumprod();
+  std::vector<float> ts(E), sc(E + 1, 1.0f), k((size_t)E * W, 0.0f);
+  float sig0 = 1.0f;
+  if (scheduler == DTP_SCHED_DDIM) {  // the N - 1 evaluations of timesteps[1:] (stable_diffusion_pipeline.py:348-355)
+    std::vector<int64_t> t(steps);
+    std::vector<float> al(steps);
+    float fin;
+    RC(dtp_ddim_tables(steps, t.data(), al.data(), &fin));
+    for (int i = 0; i < E; ++i) {
+      const int idx = 1 + i;
+      const float a_t = al[idx], a_prev = (idx + 1 < steps) ? al[idx + 1] : fin;
+      ts[i] = (float)t[idx];
+      k[W * i + 0] = sqrtf(1.0f - a_t);
+      k[W * i + 1] = sqrtf(a_t);
+      k[W * i + 2] = sqrtf(a_prev);
+      k[W * i + 3] = sqrtf(1.0f - a_prev);
+    }
+  } else if (scheduler == DTP_SCHED_DPM) {
+    // set_timesteps: linspace(0, 999, N + 1).round()[::-1][:-1] -- numpy rounds half to even (utilities.py:797-805)
+    std::vector<int> t(steps + 1);
+    for (int i = 0; i < steps; ++i) t[i] = (int)nearbyint((double)(steps - i) * (999.0 / steps));
+    t[0] = 999;
+    t[steps] = 0;  // prev_timestep of the last evaluation (utilities.py:970)
+    // alpha_t, sigma_t, lambda_t in fp32 like the reference's torch tables (utilities.py:692-694)
+    auto alpha = [&](int i) { return sqrtf(full[i]); };
+    auto sigma = [&](int i) { return sqrtf(1.0f - full[i]); };
+    auto lambda = [&](int i) { return logf(alpha(i)) - logf(sigma(i)); };
+    for (int i = 0; i < E; ++i) {
+      const int s0 = t[i], tt = t[i + 1];
+      const float h = lambda(tt) - lambda(s0);
+      const float c2 = alpha(tt) * (expf(-h) - 1.0f);
+      // first order at the first evaluation and, for schedules shorter than 15, at the last (lower_order_final, :971-985)
+      const bool first = i == 0 || (i == E - 1 && steps < 15);
+      float inv_r0 = 0.0f;
+      if (i > 0) {
+        const float h0 = lambda(s0) - lambda(t[i - 1]);
+        inv_r0 = 1.0f / (h0 / h);  // D1 = (1 / r0) (m0 - m1), utilities.py:907-912
+      }
+      ts[i] = (float)s0;
+      float* r = &k[W * i];
+      r[0] = alpha(s0);
+      r[1] = sigma(s0);
+      r[2] = first ? 1.0f : 2.0f;
+      r[3] = sigma(tt) / sigma(s0);
+      r[4] = c2;
+      r[5] = 0.5f * c2;
+      r[6] = first ? 0.0f : inv_r0;
+    }
+  } else {  // LMSD
+    // sigmas of the training schedule, fp32 like torch; init_noise_sigma is their maximum (utilities.py:286-292)
+    float sfull[1000];
+    for (int i = 0; i < 1000; ++i) sfull[i] = sqrtf((1.0f - full[i]) / full[i]);
+    sig0 = *std::max_element(sfull, sfull + 1000);
+    // set_timesteps: timesteps = linspace(0, 999, N)[::-1], sigmas = np.interp(timesteps, arange(1000), sfull) + [0] (:298-306)
+    std::vector<float> sg(steps + 1, 0.0f);
+    for (int i = 0; i < steps; ++i) {
+      const double x = i == 0 ? 999.0 : (double)(steps - 1 - i) * (999.0 / (steps - 1));
+      const int j = std::min((int)x, 998);
+      const double v = x == (double)j ? (double)sfull[j]
+                                      : ((double)sfull[j + 1] - (double)sfull[j]) * (x - (double)j) + (double)sfull[j];
+      ts[i] = (float)x;
+      sg[i] = (float)v;
+    }
+    for (int i = 0; i <= steps; ++i) sc[i] = 1.0f / sqrtf(sg[i] * sg[i] + 1.0f);  // latent_scales (:314)
+    // configure() (:316-343) rebinds its local `order` to min(step_index + 1, order) on every pass, so after the first evaluation it
+    // stays 1: every row of the reference is first order.  Reproduced; the row and the kernel carry orders up to 4.
+    int order = 4;
+    for (int i = 0; i < E; ++i) {
+      order = std::min(i + 1, order);
+      double s[4];
+      for (int m = 0; m < order; ++m) s[m] = (double)sg[i - m];
+      float* r = &k[W * i];
+      r[0] = sg[i];
+      r[1] = (float)order;
+      for (int j = 0; j < order; ++j) r[2 + j] = (float)lagrange_integral(s, order, j, (double)sg[i], (double)sg[i + 1]);
+    }
+  }
+  if (evals) *evals = E;
+  if (init_sigma) *init_sigma = sig0;
+  if (timesteps) memcpy(timesteps, ts.data(), (size_t)E * 4);
+  if (in_scale) memcpy(in_scale, sc.data(), (size_t)(E + 1) * 4);
+  if (coefs) memcpy(coefs, k.data(), k.size() * 4);
   return DTP_OK;
 }
 
@@ -147,22 +266,27 @@ __global__ void prep_kernel(const float* __restrict__ canvas, const float* __res
 }
 
 // UNet input assembly (inpaint_pipeline.py:116,136; sdp:423-427): branch-major [uncond x B | cond x B | tg x k]; stamp b has the
-// texture-guided row 2B + rank[b] while rank[b] < k (StampCoefs).
+// texture-guided row 2B + rank[b] while rank[b] < k (StampCoefs).  At stage 0 (lat_nchw set) the running latent starts as
+// latents * init_noise_sigma (sdp:345); the latent channels of the input are scaled by scale_model_input of evaluation `eval_index`
+// (sdp:424; the mask and masked-latent channels are concatenated after scaling, :426-427).
 __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float* __restrict__ masks,
                                 const float* __restrict__ ml, const int* __restrict__ rank, f16* __restrict__ in16,
-                                float* __restrict__ x32, int B, int HWl, int k) {
+                                float* __restrict__ x32, const StampParams* __restrict__ params, int eval_index, int B, int HWl, int k) {
   const long long total = (long long)B * HWl;
+  const float sig0 = params->init_sigma, scale = params->in_scale[eval_index];
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int b = (int)(i / HWl), p = (int)(i - (long long)b * HWl);
     float x[4];
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch) {
       if (lat_nchw) {
-        x[ch] = lat_nchw[((size_t)b * 4 + ch) * HWl + p];  // * init_noise_sigma (= 1.0)
+        x[ch] = lat_nchw[((size_t)b * 4 + ch) * HWl + p] * sig0;
         x32[i * 4 + ch] = x[ch];
       } else {
         x[ch] = x32[i * 4 + ch];  // mid-loop switch to a program with fewer tg rows: keep the running latent
       }
+      x[ch] *= scale;
+      asm volatile("" : "+v"(x[ch]));  // round the scaled latent to fp32 before fp16, as the reference does
     }
     const int r = rank[b];
     const int NB = r < k ? 3 : 2;
@@ -186,30 +310,58 @@ __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float*
   }
 }
 
-// guidance combine + DDIM eta=0 step + refresh of the latent channels of the UNet input
-// (sdp:419-420,449-455; utilities.py:463-503).  Stamp b uses its own cfg / tg; its texture-guided branch is row 2B + rank[b] of a
-// program with k tg rows, present while rank[b] < k, i.e. while step_index < its tg_evals (the stamps are ordered by descending tg_evals).
-__global__ void step_kernel(const float* __restrict__ eps_out, float* __restrict__ x32, f16* __restrict__ in16,
-                            const StampParams* __restrict__ params, int step_index, int B, int HWl, int k) {
-  const float* kc = params->sched + 4 * step_index;
-  const float sqrt_beta_t = kc[0], sqrt_alpha_t = kc[1], sqrt_alpha_prev = kc[2], sqrt_beta_prev = kc[3];
+// guidance combine + one sampler update + refresh of the latent channels of the UNet input (sdp:419-420,449-455).  Stamp b uses its
+// own cfg / tg; its texture-guided branch is row 2B + rank[b] of a program with k tg rows, present while rank[b] < k, i.e. while
+// step_index < its tg_evals (the stamps are ordered by descending tg_evals).  `kc`: this evaluation's coefficient row
+// (dtp_scheduler_tables); `hist`: [3][B][HWl][4] sampler history.  One instantiation per sampler:
+//   DDIM  eta = 0 step (utilities.py:463-503)
+//   DPM   DPM-Solver++ first order / multistep second order, midpoint (utilities.py:838-852,873-880,888-931,953-994)
+//   LMSD  linear multistep in sigma space (utilities.py:345-362)
+template <int S>
+__global__ void step_kernel(const float* __restrict__ eps_out, float* __restrict__ x32, f16* __restrict__ in16, float* __restrict__ hist,
+                            const float* __restrict__ kc, const float* __restrict__ next_scale, const float* __restrict__ cfgs,
+                            const float* __restrict__ tgs, const int* __restrict__ ranks, int step_index, int B, int HWl, int k) {
   const long long total = (long long)B * HWl * 4;
   const size_t bs = (size_t)B * HWl * 4;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int b = (int)(i / ((long long)HWl * 4));
     const long long j = i - (long long)b * HWl * 4;  // element within the stamp
-    const int r = params->coef.rank[b];
-    const float cfg = params->coef.cfg[b];
+    const int r = ranks[b];
+    const float cfg = cfgs[b];
     const float u = eps_out[i], c = eps_out[bs + i];
     float e = u + cfg * (c - u);
-    if (r < k) e += params->coef.tg[b] * (eps_out[(2 * (size_t)B + r) * HWl * 4 + j] - c);
+    if (r < k) e += tgs[b] * (eps_out[(2 * (size_t)B + r) * HWl * 4 + j] - c);
     const float x = x32[i];
-    const float x0 = (x - sqrt_beta_t * e) / sqrt_alpha_t;
-    float xn = sqrt_alpha_prev * x0 + sqrt_beta_prev * e;
+    float xn;
+    if constexpr (S == DTP_SCHED_DDIM) {
+      const float sqrt_beta_t = kc[0], sqrt_alpha_t = kc[1], sqrt_alpha_prev = kc[2], sqrt_beta_prev = kc[3];
+      // the contractions spelled out: which product of the update the compiler folds into the fma otherwise depends on the
+      // surrounding code, and these are the ones DDIM stamps have always been computed with
+      const float x0 = fmaf(-sqrt_beta_t, e, x) / sqrt_alpha_t;
+      xn = fmaf(sqrt_beta_prev, e, sqrt_alpha_prev * x0);
+    } else if constexpr (S == DTP_SCHED_DPM) {
+      const float m0 = (x - kc[1] * e) / kc[0];  // convert_model_output: the data prediction x0
+      xn = kc[3] * x - kc[4] * m0;
+      if (kc[2] > 1.5f) xn = xn - kc[5] * (kc[6] * (m0 - hist[i]));  // second order: D1 = (1 / r0) (m0 - m_prev)
+      hist[i] = m0;
+    } else {
+      const float sigma = kc[0];
+      const float x0 = x - sigma * e;
+      const float d = (x - x0) / sigma;  // the ODE derivative, computed as the reference does
+      const int order = min(max((int)kc[1], 1), 4);
+      float acc = kc[2] * d;
+      for (int m = 1; m < order; ++m) acc += kc[2 + m] * hist[(size_t)((step_index - m + 3) % 3) * bs + i];
+      xn = x + acc;
+      hist[(size_t)(step_index % 3) * bs + i] = d;
+    }
     x32[i] = xn;
     // the fp16 copies are the rounded fp32 latent: keep the compiler from fusing the last fma into the conversion (v_fma_mix*_f16
     // rounds the exact product once, i.e. differently)
     asm volatile("" : "+v"(xn));
+    if constexpr (S == DTP_SCHED_LMSD) {  // scale_model_input of the next evaluation (DDIM, DPM: 1)
+      xn *= next_scale[0];
+      asm volatile("" : "+v"(xn));
+    }
     const long long pix = i >> 2, p = j >> 2;
     const int ch = (int)(i & 3);
     in16[((size_t)pix) * 16 + ch] = (f16)xn;
@@ -284,6 +436,7 @@ int stamp_init(Ctx* c) {
   void* p;
   const size_t hw = (size_t)c->h * c->h, RR = (size_t)c->R * c->R;
   RC(ctx_persistent(c, c->maxB * hw * 4 * 4, &p, true)); c->x32 = (float*)p;
+  RC(ctx_persistent(c, 3 * c->maxB * hw * 4 * 4, &p, true)); c->hist32 = (float*)p;
   RC(ctx_persistent(c, c->maxB * 4 * RR * 4, &p, true)); c->canvas32 = (float*)p;
   RC(ctx_persistent(c, 2 * c->maxB * RR * 4, &p, true)); c->alpha_tmp = (float*)p;
   RC(ctx_persistent(c, sizeof(StampParams), &p, true)); c->stamp_params = (StampParams*)p;
@@ -373,6 +526,32 @@ int dtp_op_dilate_pads(const float* canvas, float* tmp, float* out, int B, int R
   hipLaunchKernelGGL(dilate_row_kernel, dim3(nblk((long long)B * R * R)), dim3(256), 0, s, canvas, tmp, B, R, pa);
   hipLaunchKernelGGL(dilate_col_kernel, dim3(nblk((long long)B * R * R)), dim3(256), 0, s, tmp, out, B, R, pa);
   return LAUNCH_OK();
+}
+
+static int launch_step(int scheduler, const float* eps_out, float* x, f16* in16, float* hist, const float* row, const float* next_scale,
+                       const float* cfg, const float* tg, const int* rank, int step_index, int B, int HWl, int k, hipStream_t s) {
+  const dim3 grid(nblk((long long)B * HWl * 4)), block(256);
+  if (scheduler == DTP_SCHED_DDIM)
+    hipLaunchKernelGGL(step_kernel<DTP_SCHED_DDIM>, grid, block, 0, s, eps_out, x, in16, hist, row, next_scale, cfg, tg, rank, step_index, B, HWl, k);
+  else if (scheduler == DTP_SCHED_DPM)
+    hipLaunchKernelGGL(step_kernel<DTP_SCHED_DPM>, grid, block, 0, s, eps_out, x, in16, hist, row, next_scale, cfg, tg, rank, step_index, B, HWl, k);
+  else
+    hipLaunchKernelGGL(step_kernel<DTP_SCHED_LMSD>, grid, block, 0, s, eps_out, x, in16, hist, row, next_scale, cfg, tg, rank, step_index, B, HWl, k);
+  return LAUNCH_OK();
+}
+
+int dtp_op_sched_step(int scheduler, const float* eps_out, float* x, float* hist, void* in16, const float* row, const float* next_scale,
+                      const float* cfg, const float* tg, const int* rank, int step_index, int B, int hw, int k, dtp_stream s) {
+  if (scheduler != DTP_SCHED_DDIM && scheduler != DTP_SCHED_DPM && scheduler != DTP_SCHED_LMSD) {
+    dtp_set_error("dtp_op_sched_step: unknown scheduler %d (DDIM = 0, DPM = 1, LMSD = 2)", scheduler);
+    return DTP_ERR_ARG;
+  }
+  if (!eps_out || !x || !hist || !in16 || !row || !next_scale || !cfg || !tg || !rank || B < 1 || B > DTP_STAMP_MAXB || hw < 1 || k < 0 ||
+      k > B || step_index < 0) {
+    dtp_set_error("dtp_op_sched_step: bad argument (B=%d, max %d, k=%d, hw=%d, step_index=%d)", B, DTP_STAMP_MAXB, k, hw, step_index);
+    return DTP_ERR_ARG;
+  }
+  return launch_step(scheduler, eps_out, x, (f16*)in16, hist, row, next_scale, cfg, tg, rank, step_index, B, hw, k, (hipStream_t)s);
 }
 
 int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s) {
@@ -481,7 +660,7 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     }
   }
   const int R = c->R, h = c->h, HW = R * R, HWl = h * h;
-  const int steps = st[0].steps, E = steps - 1;
+  const int steps = st[0].steps, sched = c->scheduler, E = sched_evals(sched, steps);
   // Per stamp: the third (texture-guided) branch contributes nothing once its coefficient is 0: skip it (bit-identical).  The stamps are
   // ordered by descending tg_evals (a stable order: a uniform batch keeps the identity), and evaluation i runs the UNet on
   // [uncond x B | cond x B | tg x k_i] with k_i = #{b : tg_evals_b > i}: finished stamps leave the batch.
@@ -494,7 +673,7 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     coef.order[b] = b;
   }
   std::stable_sort(coef.order, coef.order + B, [&](int x, int y) { return tg_evals[x] > tg_evals[y]; });
-  std::vector<long long> loop_key = {((long long)B << 32) | ((long long)steps << 12) | (2LL << 60)};
+  std::vector<long long> loop_key = {((long long)B << 32) | ((long long)sched << 40) | ((long long)steps << 12) | (2LL << 60)};
   for (int j = 0; j < B; ++j) { coef.rank[coef.order[j]] = j; loop_key.push_back(tg_evals[coef.order[j]]); }
   std::vector<int> ks(E);  // k_i
   for (int i = 0; i < E; ++i) {
@@ -521,27 +700,19 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   RC(get_dec_prog(c, B, &dec));
   RC(get_bufs(c, B, &sb));
 
-  // ---- schedule tables (update_infer_settings, inpaint_pipeline.py:39-50): rebuilt when the step count changes
-  if (c->sched_steps != steps) {  // rare (a settings change): the only host-blocking part of dtp_stamp
+  // ---- schedule tables (update_infer_settings, inpaint_pipeline.py:39-50): rebuilt when the step count or the scheduler changes
+  if (c->sched_steps != steps || c->sched_kind != sched) {  // rare (a settings change): the only host-blocking part of dtp_stamp
     HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<int64_t> ts(steps);
-    std::vector<float> al(steps);
-    float fin;
-    RC(dtp_ddim_tables(steps, ts.data(), al.data(), &fin));
-    std::vector<float> tsf;
-    for (int i = 1; i < steps; ++i) tsf.push_back((float)ts[i]);  // timesteps[1:] (sdp:348-355)
-    RC(ensure_temb(c, tsf));
-    std::vector<float> k(4 * E);
-    for (int i = 0; i < E; ++i) {
-      const int idx = 1 + i;
-      const float a_t = al[idx], a_prev = (idx + 1 < steps) ? al[idx + 1] : fin;
-      k[4 * i + 0] = sqrtf(1.0f - a_t);
-      k[4 * i + 1] = sqrtf(a_t);
-      k[4 * i + 2] = sqrtf(a_prev);
-      k[4 * i + 3] = sqrtf(1.0f - a_prev);
-    }
+    std::vector<float> ts(E), sc(E + 1), k((size_t)DTP_SCHED_ROW * E);
+    int ne;
+    float sig0;
+    RC(dtp_scheduler_tables(sched, steps, &ne, &sig0, ts.data(), sc.data(), k.data()));
+    RC(ensure_temb(c, ts));
     HIP_CHECK(hipMemcpy(c->stamp_params->sched, k.data(), k.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(c->stamp_params->in_scale, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(&c->stamp_params->init_sigma, &sig0, 4, hipMemcpyHostToDevice));
     c->sched_steps = steps;
+    c->sched_kind = sched;
   }
   hipLaunchKernelGGL(set_header_kernel, dim3(1), dim3(256), 0, s, &c->stamp_params->coef, coef);
   hipLaunchKernelGGL(set_slots_kernel, dim3(1), dim3(64), 0, s, c->slot_map, sa, B);
@@ -594,7 +765,7 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     RC(enc->main.run(q, 0));
     RC(launch_vae_sample(c, enc->moments, vae_eps ? sb->eps : nullptr, sb->ml, 2 * B, VAE_SCALE, q));
     hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, sb->lat, sb->masks, sb->ml, rank, first->in16,
-                       c->x32, B, HWl, k0);
+                       c->x32, c->stamp_params, 0, B, HWl, k0);
     return LAUNCH_OK();
   }));
   }
@@ -607,7 +778,7 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     if (u2 && !u2->fp8_calibrated) {
       if (ks[0] > 0)  // (u2 is not the first program:) its input is normally assembled where the loop switches programs: do it now, from the initial latents
         hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, s, (const float*)nullptr, sb->masks, sb->ml, rank,
-                           u2->in16, c->x32, B, HWl, 0);
+                           u2->in16, c->x32, c->stamp_params, 0, B, HWl, 0);
       RC(fp8_calibrate(c, u2, s, 0));
     }
   }
@@ -620,11 +791,12 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
       if (i > 0 && ks[i] != ks[i - 1]) {
         // switching to a program with fewer tg rows: its input needs mask/masked-latent channels + current x
         hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, (const float*)nullptr, sb->masks,
-                           sb->ml, rank, up->in16, c->x32, B, HWl, ks[i]);
+                           sb->ml, rank, up->in16, c->x32, c->stamp_params, i, B, HWl, ks[i]);
       }
       RC(up->main.run(q, i));
-      hipLaunchKernelGGL(step_kernel, dim3(nblk((long long)B * HWl * 4)), dim3(256), 0, q, up->out32, c->x32, up->in16,
-                         c->stamp_params, i, B, HWl, ks[i]);
+      StampParams* sp = c->stamp_params;
+      RC(launch_step(sched, up->out32, c->x32, up->in16, c->hist32, sp->sched + DTP_SCHED_ROW * i, sp->in_scale + i + 1, sp->coef.cfg,
+                     sp->coef.tg, sp->coef.rank, i, B, HWl, ks[i], q));
     }
     return LAUNCH_OK();
   }));
@@ -717,6 +889,14 @@ int dtp_profile_dump(dtp_ctx* ctx, const char* path) {
 int dtp_set_option(dtp_ctx* ctx, const char* name, int value) {
   Ctx* c = (Ctx*)ctx;
   if (!c || !name) return DTP_ERR_ARG;
+  if (!strcmp(name, "scheduler")) {  // takes effect from the next stamp, which rebuilds the schedule tables
+    if (value != DTP_SCHED_DDIM && value != DTP_SCHED_DPM && value != DTP_SCHED_LMSD) {
+      dtp_set_error("dtp_set_option: scheduler %d is not one of DDIM = 0, DPM = 1, LMSD = 2", value);
+      return DTP_ERR_ARG;
+    }
+    c->scheduler = value;
+    return DTP_OK;
+  }
   if (!strcmp(name, "use_graph")) { c->use_graph = value != 0; return DTP_OK; }
   if (!strcmp(name, "autotune")) { c->autotune = value != 0; return DTP_OK; }
   if (!strcmp(name, "check_finite")) { c->check_finite = value != 0; return DTP_OK; }

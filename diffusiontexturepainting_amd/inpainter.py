@@ -21,11 +21,14 @@ DEFAULT_SETTINGS = dict(steps=20, context_pad=150, tg_steps=20, cfg_weight=2.0, 
 
 class MI355ConditionalInpainter(ConditionalInpainterBase):
     def __init__(self, resolution, device=0, weights="synthetic", max_batch=1, seed=42, use_graph=True, fp8_attention=None, fp8_linear=None,
-                 fp8_operands=None):
+                 fp8_operands=None, scheduler="DDIM"):
         """weights: "synthetic" (seeded random tensors with the real shapes -- no checkpoints can be
         downloaded in this environment) or a dict {unet, vae, [lora], [clip], [penc]} of
-        {diffusers key: tensor} state dicts (see weights.load_checkpoint_file)."""
+        {diffusers key: tensor} state dicts (see weights.load_checkpoint_file).
+        scheduler: the sampler of every stamp, by the reference pipeline's names (stable_diffusion_pipeline.py:115-127):
+        "DDIM" (default), "DPM" (DPM-Solver++ 2M) or "LMSD"; see set_scheduler."""
         super().__init__()
+        sched_id = _lib.scheduler_id(scheduler)  # ValueError for EulerA / PNDM / unknown names, before any device work
         if not torch.cuda.is_available():
             raise _lib.DtpError("MI355ConditionalInpainter needs a ROCm GPU (torch.cuda.is_available() is False)")
         # GEMM (tile, split-K) choices are timed once per shape at build time and persisted in a per-user cache; the table
@@ -69,6 +72,9 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.fp8_operands = bool(fp8_operands)
         if self.fp8_operands:  # PARITY-ONLY: transformer Linears with K >= 1280 on e4m3 activations in memory (before any program is built)
             check(self._lib.dtp_set_option(self._h, b"fp8_operands", 1), "dtp_set_option(fp8_operands)")
+        self.scheduler = scheduler
+        if sched_id != _lib.SCHEDULERS["DDIM"]:
+            check(self._lib.dtp_set_option(self._h, b"scheduler", sched_id), "dtp_set_option(scheduler)")
         # noise: seeded once, never reseeded (trt_model.py:54, stable_diffusion_pipeline.py:154-156)
         self.generator = torch.Generator(device=self._device).manual_seed(seed)
         self.stream = torch.cuda.Stream(device=self._device)
@@ -241,6 +247,13 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def profile_dump(self, path):
         check(self._lib.dtp_profile_dump(self._h, str(path).encode()), "dtp_profile_dump")
+
+    def set_scheduler(self, name):
+        """Switch the sampler ("DDIM" | "DPM" | "LMSD") from the next stamp on; that stamp rebuilds the schedule tables once (a host
+        wait, like a change of steps).  DDIM runs steps - 1 UNet evaluations per stamp, DPM and LMSD run steps."""
+        sid = _lib.scheduler_id(name)
+        check(self._lib.dtp_set_option(self._h, b"scheduler", sid), "dtp_set_option(scheduler)")
+        self.scheduler = name
 
     def set_option(self, name, value):
         check(self._lib.dtp_set_option(self._h, name.encode(), int(value)), "dtp_set_option")

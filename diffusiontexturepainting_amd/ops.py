@@ -419,3 +419,45 @@ def dilate_alpha_pads(canvas, pads):
     arr = (C.c_int * b)(*[int(p) for p in pads])
     check(lib.dtp_op_dilate_pads(ptr(canvas), ptr(tmp), ptr(out), b, r, arr, _stream()), "dilate")
     return out
+
+
+def scheduler_tables(scheduler, steps):
+    """Host-only schedule tables of a sampler ("DDIM" | "DPM" | "LMSD" or its id) for `steps` steps, as the stamp uploads them:
+    dict(evals=E, init_sigma, timesteps f32 [E], in_scale f32 [E + 1], coefs f32 [E, 8]) -- row layouts in include/dtp.h."""
+    import numpy as np
+    lib = _lib.load()
+    sid = _lib.scheduler_id(scheduler) if isinstance(scheduler, str) else int(scheduler)
+    n = max(int(steps), 1)
+    ev, sig = C.c_int(), C.c_float()
+    ts, sc, cf = (C.c_float * n)(), (C.c_float * (n + 1))(), (C.c_float * (n * _lib.SCHED_ROW))()
+    check(lib.dtp_scheduler_tables(sid, int(steps), C.byref(ev), C.byref(sig), ts, sc, cf), "dtp_scheduler_tables")
+    e = ev.value
+    return dict(evals=e, init_sigma=sig.value, timesteps=np.array(ts[:e], dtype=np.float32),
+                in_scale=np.array(sc[:e + 1], dtype=np.float32),
+                coefs=np.array(cf[:e * _lib.SCHED_ROW], dtype=np.float32).reshape(e, _lib.SCHED_ROW))
+
+
+def sched_step(scheduler, row, next_scale, eps_out, x, hist, cfg, tg, rank, k, step_index):
+    """One sampler update with the stamp's own step kernel (dtp_op_sched_step), in place on the caller's device tensors.
+    eps_out f32 [2B + k, 4, h, w] UNet outputs in the stamp's row order; x f32 [B, 4, h, w] (updated); hist f32 [3, B, h*w*4]
+    (NHWC history, persists across calls); row: one coefficient row (8 floats); cfg / tg / rank: B per-stamp values.
+    Returns the fp16 UNet input rows the kernel wrote, latent channels only: f16 [2B + k, 4, h, w]."""
+    lib = _lib.load()
+    sid = _lib.scheduler_id(scheduler) if isinstance(scheduler, str) else int(scheduler)
+    b, _, h, w = x.shape
+    dev = x.device
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().float()  # noqa: E731
+    e = nhwc(eps_out)
+    xs = nhwc(x)
+    in16 = torch.zeros(2 * b + int(k), h, w, 16, dtype=torch.float16, device=dev)
+    row_t = torch.as_tensor(row, dtype=torch.float32).reshape(-1)[: _lib.SCHED_ROW].to(dev).contiguous()
+    sc = torch.tensor([float(next_scale)], dtype=torch.float32, device=dev)
+    cfg_t = torch.tensor([float(v) for v in cfg], dtype=torch.float32, device=dev)
+    tg_t = torch.tensor([float(v) for v in tg], dtype=torch.float32, device=dev)
+    rank_t = torch.tensor([int(v) for v in rank], dtype=torch.int32, device=dev)
+    if hist.numel() < 3 * b * h * w * 4 or not hist.is_contiguous() or hist.dtype != torch.float32:
+        raise ValueError("hist must be a contiguous f32 tensor of 3 * B * h * w * 4 elements")
+    check(lib.dtp_op_sched_step(sid, ptr(e), ptr(xs), ptr(hist), ptr(in16), ptr(row_t), ptr(sc), ptr(cfg_t), ptr(tg_t), ptr(rank_t),
+                                int(step_index), b, h * w, int(k), _stream()), "sched_step")
+    x.copy_(xs.permute(0, 3, 1, 2))
+    return in16[..., :4].permute(0, 3, 1, 2)

@@ -96,8 +96,10 @@ typedef struct {
  *   out     f32 [B,3,R,R] 0..1 (or u8, see output_u8)
  * Asynchronous on `s`: the call only enqueues (copies of the inputs, graph replays, kernels with the settings as kernel
  * arguments) and returns; back-to-back stamps overlap host enqueue with device work.  The caller keeps canvas / latents /
- * vae_eps / out alive until the stream has consumed them.  The one exception is a CHANGE of `steps` between two calls,
- * which rebuilds the schedule tables (update_infer_settings, inpaint_pipeline.py:39-50) and waits for the stream once. */
+ * vae_eps / out alive until the stream has consumed them.  The one exception is a CHANGE of `steps` between two calls, or of the
+ * "scheduler" option since the last stamp, which rebuilds the schedule tables (update_infer_settings, inpaint_pipeline.py:39-50)
+ * and waits for the stream once.  The sampler is the handle's "scheduler" option (dtp_set_option; DDIM by default): it runs E
+ * UNet evaluations, E = steps - 1 under DDIM and steps under DPM / LMSD (dtp_scheduler_tables). */
 int dtp_stamp(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
               void* out, int B, dtp_stream s);
 /* The same with one conditioning slot per stamp: slots = host int[B] (NULL = all slot 0).  Stamp b is conditioned on the brush
@@ -107,10 +109,10 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
 /* The same with one dtp_settings per stamp: st = host dtp_settings[B].  Stamp b gets exactly what dtp_stamp computes for it alone
  * with st[b]: its own context_pad (dilation window), cfg_weight, tg_weight and tg_steps.  steps, composite and output_u8 are per call:
  * DTP_ERR_ARG, naming the stamp, when they differ.  Every entry gets dtp_stamp's checks (steps 2..999, context_pad >= 1).
- * Stamp b evaluates the texture-guided branch for its first tg_evals_b = (tg_weight_b == 0 ? 0 : clamp(tg_steps_b, 0, steps - 1))
- * evaluations; the UNet batch of evaluation i is 2B + #{b : tg_evals_b > i}, so a stamp whose guidance has ended costs two rows, not
- * three.  Programs are built per (B, tg rows) on first use, and the denoise loop is captured once per (B, steps, sorted tg_evals
- * profile); the context keeps the 16 most recently used loop graphs.  Any cfg / tg values replay the same graph.  Under the fp8
+ * Stamp b evaluates the texture-guided branch for its first tg_evals_b = (tg_weight_b == 0 ? 0 : clamp(tg_steps_b, 0, E))
+ * evaluations (E: see dtp_stamp); the UNet batch of evaluation i is 2B + #{b : tg_evals_b > i}, so a stamp whose guidance has ended costs two rows, not
+ * three.  Programs are built per (B, tg rows) on first use, and the denoise loop is captured once per (B, steps, scheduler, sorted
+ * tg_evals profile); the context keeps the 16 most recently used loop graphs.  Any cfg / tg values replay the same graph.  Under the fp8
  * options (fp8_attention, fp8_linear, fp8_operands), which calibrate one program per batch shape, the stamps of a batch must share
  * tg_evals: DTP_ERR_STATE otherwise.  dtp_stamp and dtp_stamp_slots are this call with st[0] applied to every stamp. */
 int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
@@ -120,6 +122,29 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
  * (DDIMScheduler.set_timesteps/configure, utilities.py:408-439).  Any pointer may be NULL. */
 int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, float* final_alpha);
+
+/* Samplers of the stamp loop (dtp_set_option "scheduler"), the reference's names (stable_diffusion_pipeline.py:115-127):
+ *   DTP_SCHED_DDIM  DDIMScheduler, eta 0, steps_offset 1 (utilities.py:370-529): E = steps - 1 evaluations
+ *   DTP_SCHED_DPM   DPMScheduler: DPM-Solver++ multistep, order 2, midpoint, first order at the last evaluation when steps < 15
+ *                   (utilities.py:649-1008): E = steps
+ *   DTP_SCHED_LMSD  LMSDiscreteScheduler: linear multistep in sigma space (utilities.py:267-367): E = steps */
+#define DTP_SCHED_DDIM 0
+#define DTP_SCHED_DPM 1
+#define DTP_SCHED_LMSD 2
+#define DTP_SCHED_ROW 8 /* floats per evaluation in the coefficient table */
+/* Host-only: everything a stamp needs for (scheduler, steps), steps 2..999.  Outputs (any pointer may be NULL):
+ *   evals        E, the number of UNet evaluations
+ *   init_sigma   init_noise_sigma (the initial latents are latents * init_sigma): 1 for DDIM / DPM, sigma_max for LMSD
+ *   timesteps    f32 [E] the UNet's timestep input per evaluation (LMSD's are not integers)
+ *   in_scale     f32 [E + 1] scale_model_input of the latent channels before evaluation i (entry E = 1: no evaluation follows)
+ *   coefs        f32 [E][DTP_SCHED_ROW], unused entries 0:
+ *     DDIM  sqrt(1 - a_t), sqrt(a_t), sqrt(a_prev), sqrt(1 - a_prev)                     x0 = (x - [0] e) / [1]; x' = [2] x0 + [3] e
+ *     DPM   alpha_s, sigma_s, order (1 | 2), sigma_t / sigma_s, alpha_t (exp(-h) - 1), 0.5 alpha_t (exp(-h) - 1), 1 / r0
+ *           m0 = (x - sigma_s e) / alpha_s;  x' = [3] x - [4] m0 (order 1)  or  [3] x - [4] m0 - [5] [6] (m0 - m_prev) (order 2)
+ *     LMSD  sigma_i, order (1..4), c_0 .. c_3 (c_j = exact integral over [sigma_i, sigma_i+1] of the Lagrange basis polynomial of
+ *           sigma_{i-j} on sigma_i .. sigma_{i-order+1})          d_i = (x - x0) / sigma_i, x0 = x - sigma_i e;  x' = x + sum c_j d_{i-j}
+ * The DDIM rows are the values dtp_stamp has always used (from dtp_ddim_tables).  DTP_ERR_ARG for an unknown scheduler or steps. */
+int dtp_scheduler_tables(int scheduler, int steps, int* evals, float* init_sigma, float* timesteps, float* in_scale, float* coefs);
 
 /* per-stage GPU time of the last dtp_stamp on this handle, ms (print_summary,
  * stable_diffusion_pipeline.py:486-503): [0]=pre+vae_encoder x2, [1]=denoise loop, [2]=vae decode+post.
@@ -151,7 +176,10 @@ int dtp_profile(dtp_ctx* ctx, int enable);
 int dtp_profile_rows(dtp_ctx* ctx, dtp_prof_row* rows, int max_rows, int* n_rows);
 /* one CSV line per recorded launch: kind,us,tflops,algo_GBps,label */
 int dtp_profile_dump(dtp_ctx* ctx, const char* path);
-/* options: "use_graph" (default 1): replay captured hipGraphs; "autotune" (default 1): time tile x split-K candidates per
+/* options: "scheduler" (default DTP_SCHED_DDIM): the sampler of the stamp loop, DTP_SCHED_DDIM | DTP_SCHED_DPM | DTP_SCHED_LMSD (any
+ * other value: DTP_ERR_ARG); may be set at any time and takes effect from the next stamp, which rebuilds the schedule tables once (a
+ * host-blocking wait, like a change of steps).  No sampler history carries over between stamps (set_timesteps runs on every infer,
+ * stable_diffusion_pipeline.py:349).  "use_graph" (default 1): replay captured hipGraphs; "autotune" (default 1): time tile x split-K candidates per
  * contraction shape when a launch program is built; "check_finite" (default 0): after every stamp ONE reduction over the
  * final latents and the decoded image looks for NaN/inf (the reference asserts `not isnan` after every step with a host
  * sync each, stable_diffusion_pipeline.py:415) -- read the verdict with dtp_last_stamp_finite; "fp8_attention" / "fp8_linear"
@@ -349,6 +377,16 @@ int dtp_op_softmax_rows(const void* x, int ldx, void* y, int ldy, int rows, int 
 int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s);
 /* the same with one pad per image (host int pads[B], B <= 64), as dtp_stamp_mixed runs it */
 int dtp_op_dilate_pads(const float* canvas, float* tmp, float* out, int B, int R, const int* pads, dtp_stream s);
+/* One sampler update exactly as the stamp's loop runs it after UNet evaluation `step_index` (the same kernel): the guidance combine
+ * e_b = u + cfg[b] (c - u) [+ tg[b] (g - c) while rank[b] < k], then the `scheduler` update of x with coefficient row `row`.
+ *   eps_out f32 [2B + k][h*w][4]  the UNet's outputs in the stamp's row order [uncond x B | cond x B | tg x k], NHWC
+ *   x       f32 [B][h*w][4]       the running latent, updated in place
+ *   hist    f32 [3][B][h*w][4]    the sampler history (DPM: previous x0 in slot 0; LMSD: derivatives d_{i-1..i-3} in slot i % 3)
+ *   in16    f16 [2B + k][h*w][16] channels 0-3 of every row receive x' * next_scale[0] (the next evaluation's input)
+ *   row     f32 [DTP_SCHED_ROW] (device) a row of dtp_scheduler_tables' coefs; next_scale f32 [1] (device)
+ *   cfg, tg f32 [B], rank int [B] (device): stamp b's texture-guided row is 2B + rank[b] while rank[b] < k.  B <= 64, 0 <= k <= B. */
+int dtp_op_sched_step(int scheduler, const float* eps_out, float* x, float* hist, void* in16, const float* row, const float* next_scale,
+                      const float* cfg, const float* tg, const int* rank, int step_index, int B, int hw, int k, dtp_stream s);
 
 #ifdef __cplusplus
 }
