@@ -67,6 +67,7 @@ GF_BIAS, GF_BIAS_M, GF_RESID, GF_GEGLU, GF_GELU, GF_QUICKGELU, GF_OUT_F32, GF_SI
 GF_SOFTMAX16 = 4096
 GF_ROWSTATS = 2048
 GF_GNSTATS = 1 << 24
+GF_RAGGED = 1 << 25  # convws tiles 53 / 54: partial 8 x 16 pixel tiles, cropped upsample window
 
 # every symbol include/dtp.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64

@@ -361,6 +361,15 @@ __global__ __launch_bounds__(64 * NW, (OCC4 ? 4 : (DP <= 64 ? 3 : (DP <= 80 ? 2 
 
 }  // namespace
 
+// round 5: the long launches (UNet levels 0 / 1) run on the LDS-DMA kernel (attn_dma.hip); $DTP_ATTN_DMA=0 keeps them here (A/B)
+bool dtp_attention_uses_dma(const AttnParams& p) {
+  static const int dma_env = [] { const char* e = getenv("DTP_ATTN_DMA"); return e ? atoi(e) : 1; }();
+  // (from 512 keys on: measured inside a stamp, S = 4096 -3 %, S = 1024 -11 ... -16 %, S = 256 +-1 %; the kernel itself also takes 128 / 256)
+  // ($DTP_ATTN_DMA_MIN_S: A/B switch, read once; the parity tests drive the kernel on short sequences through dtp_op_attention_dma)
+  static const int dma_min = [] { const char* e = getenv("DTP_ATTN_DMA_MIN_S"); return e ? atoi(e) : 512; }();
+  return dma_env && p.Skv >= dma_min && dtp_attention_dma_supported(p);
+}
+
 int dtp_launch_attention(const AttnParams& pin, hipStream_t s) {
   AttnParams p = pin;
   // s_setprio(1) around the QK^T (bit 0) and PV (bit 1) MFMA clusters: the co-resident workgroups of a CU are at different phases, so
@@ -374,12 +383,7 @@ int dtp_launch_attention(const AttnParams& pin, hipStream_t s) {
     dtp_set_error("attention: D=%d ldq=%d ldk=%d ldv=%d ldo=%d unsupported", p.D, p.ldq, p.ldk, p.ldv, p.ldo);
     return DTP_ERR_ARG;
   }
-  // round 5: the long full-tile launches (UNet levels 0 / 1) run on the LDS-DMA kernel (attn_dma.hip); $DTP_ATTN_DMA=0 keeps them here (A/B)
-  static const int dma_env = [] { const char* e = getenv("DTP_ATTN_DMA"); return e ? atoi(e) : 1; }();
-  // (from 512 keys on: measured inside a stamp, S = 4096 -3 %, S = 1024 -11 ... -16 %, S = 256 +-1 %; the kernel itself also takes 128 / 256)
-  // ($DTP_ATTN_DMA_MIN_S: A/B switch, read once; the parity tests drive the kernel on short sequences through dtp_op_attention_dma)
-  static const int dma_min = [] { const char* e = getenv("DTP_ATTN_DMA_MIN_S"); return e ? atoi(e) : 512; }();
-  if (dma_env && p.Skv >= dma_min && dtp_attention_dma_supported(p)) return dtp_launch_attention_dma(p, s);
+  if (dtp_attention_uses_dma(p)) return dtp_launch_attention_dma(p, s);
   dim3 grid((p.Sq + 127) / 128, p.H, p.B), block(256);
   static const int cus = [] {
     int dev = 0;

@@ -1,5 +1,5 @@
 // Self-attention for the UNet's long sequences (reference: the fMHA plugin the TensorRT build inserts for attn1,
-// trt_inference/models.py:467-518, 594-646, 762-780): O = softmax(Q K^T * scale) V per (batch, head), d = 40 / 80, S a multiple of 64.
+// trt_inference/models.py:467-518, 594-646, 762-780): O = softmax(Q K^T * scale) V per (batch, head), d = 40 / 80, S a multiple of 64 (or, RAG, with a ragged last key tile).
 //
 // Round 5 rewrite of the data path of attention.hip (which stays the general kernel: ragged S, d = 64 / 160 / 192, tiny sequences).
 // The round-4 ablation (profiles/r04_attention_ablation.txt) priced the register-staged K / V^T tile -- 8 ds_write_b128 + 32
@@ -124,8 +124,10 @@ struct AdGeom {
   static constexpr bool BIGRING = (NS - 1) * STAGE + IMGV + 256 >= 65536;
 };
 
-// one tile's DMA pieces of this wave: piece pi = wave + 4 i -> LDS slot pi of ring slot `stage`; the lanes of a V row's ones chunk are off
-template <int KC, int NP, int PW, int STAGE, int NW, class RS_T>
+// one tile's DMA pieces of this wave: piece pi = wave + 4 i -> LDS slot pi of ring slot `stage`; the lanes of a V row's ones chunk (voff
+// -1) are off.  RAG: other negative offsets (OOB, the missing keys of a ragged last tile) stay on -- the DMA writes zeros for them, and
+// every wave still issues every piece (the counted vmcnt waits rely on it)
+template <int KC, int NP, int PW, int STAGE, int NW, bool RAG, class RS_T>
 __device__ __forceinline__ void issue_tile(const RS_T (&rs)[PW], char* smem, const int (&voff)[PW], const int (&soff)[PW], int wave, int stage) {
 #pragma unroll
   for (int i = 0; i < PW; ++i) {
@@ -134,14 +136,17 @@ __device__ __forceinline__ void issue_tile(const RS_T (&rs)[PW], char* smem, con
       char* const dst = smem + stage * STAGE + pi * 1024;
       const int so = __builtin_amdgcn_readfirstlane(soff[i]);  // (uniform, but not provably so under the EXEC mask below: hipcc would wrap the DMA in a waterfall loop)
       if (NW * i + NW - 1 < KC) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[i], (lds_ptr_t)dst, 16, voff[i], so, 0, 0);  // a K piece for every wave: all lanes
-      else if (voff[i] >= 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[i], (lds_ptr_t)dst, 16, voff[i], so, 0, 0);
+      else if (RAG ? voff[i] != -1 : voff[i] >= 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[i], (lds_ptr_t)dst, 16, voff[i], so, 0, 0);
     }
   }
 }
 
 // NW = 8: one K / V tile staged for 256 queries (half the DMA pieces and LDS writes per query); taken when the launch still has >= 8 x CUs
 // workgroups (a batched stamp's level 0), compiled for two workgroups per CU
-template <int D, int NS, int NW>
+// RAG: Skv % 64 != 0.  The last key tile is ragged: its missing keys are DMA'd as zeros (out-of-range offsets) and their
+// scores are set to -1e30 before the row maximum and the exponentials see them (attention.hip does the same), so they add nothing to P V
+// or to the row sums.  RAG = false is the aligned build.
+template <int D, int NS, int NW, bool RAG = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 : 1))) void attn_dma_kernel(const AttnParams p, const int qblocks) {
   using G = AdGeom<D, NS, NW>;
   constexpr int NTHR = 64 * NW;
@@ -165,7 +170,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
   const f16* const Qb = p.Q + p.qbs * b + h * D;
   const f16* const Kb = p.K + p.kbs * b + h * D;
   const f16* const Vb = p.V + p.vbs * b + h * D;
-  const int T = p.Skv >> 6;  // 64-key tiles (Skv % 64 == 0: launcher)
+  const int T = RAG ? (p.Skv + 63) >> 6 : p.Skv >> 6;  // 64-key tiles (Skv % 64 == 0 unless RAG: launcher)
 
   // ---- zero the ring once (reads beyond a row's chunks -- d = 40: chunk 5 of a K row, columns 48..63 of a V row -- hit the next row,
   // the other image or the tail: always finite bytes, multiplied by zero columns of Q' or landing in O^T rows nobody stores), then the
@@ -178,7 +183,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
   // ---- this wave's DMA pieces: piece pi = wave + 4 i of a tile (pi < KC: K image, else V image), 64 lanes x 16 bytes, lane-linear in LDS
   constexpr int OOB = (int)0x80000000u;
   __amdgpu_buffer_rsrc_t rs[PW];
-  int voff[PW], step[PW], soff[PW];
+  int voff[PW], step[PW], soff[PW], pkey[PW];
 #pragma unroll
   for (int i = 0; i < PW; ++i) {
     const int pi = wave + NW * i;
@@ -199,14 +204,26 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
       else key = row;
     }
     voff[i] = on ? (key * (isk ? p.ldk : p.ldv) + c * 8) * 2 : -1;
+    pkey[i] = key;
     rs[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(isk ? Kb : Vb), 0, OOB, 0x00020000);
     step[i] = 64 * 2 * (isk ? p.ldk : p.ldv);  // bytes from one 64-key tile to the next
     soff[i] = 0;
   }
   // (a device function, not a lambda: a lambda that reads voff[] made hipcc's HOST pass drop the kernel's stub without a diagnostic)
-#define DTP_AD_ISSUE(stage)                                        \
+// RAG: the last tile's pieces carry the tile offset in the lane offset (range-checked, unlike the scalar one) and OOB for missing keys
+#define DTP_AD_ISSUE(stage, tix)                                   \
   {                                                                \
-    issue_tile<KC, NP, PW, STAGE, NW>(rs, smem, voff, soff, wave, (stage)); \
+    if (RAG && (tix) == T - 1) {                                   \
+      int vl_[PW], sl_[PW];                                        \
+      const int lim_ = p.Skv - 64 * (T - 1);                       \
+      _Pragma("unroll") for (int i_ = 0; i_ < PW; ++i_) {          \
+        vl_[i_] = voff[i_] == -1 ? -1 : (pkey[i_] < lim_ ? voff[i_] + soff[i_] : OOB); \
+        sl_[i_] = 0;                                               \
+      }                                                            \
+      issue_tile<KC, NP, PW, STAGE, NW, RAG>(rs, smem, vl_, sl_, wave, (stage)); \
+    } else {                                                       \
+      issue_tile<KC, NP, PW, STAGE, NW, RAG>(rs, smem, voff, soff, wave, (stage)); \
+    }                                                              \
     _Pragma("unroll") for (int i_ = 0; i_ < PW; ++i_) soff[i_] += step[i_]; \
   }
 
@@ -225,7 +242,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
   __syncthreads();  // the fill is complete before the first DMA piece can land
 #pragma unroll
   for (int t = 0; t < NS - 1; ++t)
-    if (t < T) DTP_AD_ISSUE(t)
+    if (t < T) DTP_AD_ISSUE(t, t)
   f16x8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -400,6 +417,18 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
     return mloc;
   };
 
+  // RAG: scores of keys >= kv of a 32-key half (register r of the lane holds key 8 (r / 4) + 4 hf + r % 4) -> -1e30; returns the lane's
+  // new maximum over the half (what half_step returned, without the missing keys)
+  auto mask_scores = [&](f32x16& nxt, int kv) -> float {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (8 * (r >> 2) + 4 * hf + (r & 3) >= kv) nxt[r] = -1.0e30f;
+    float m = fmaxf(nxt[0], nxt[1]);
+#pragma unroll
+    for (int r = 2; r < 16; r += 2) m = fmaxf(fmaxf(m, nxt[r]), nxt[r + 1]);
+    return m;
+  };
+
   // ---- prologue: tile 0 has landed (for every wave); scores of its first half, every row's reference onto its first maximum
   if (T >= NS - 1) {
     if constexpr (NP % NW == 0) wait_vm<(NS - 2) * PW>();
@@ -441,7 +470,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
       const int t = t0 + S;
       if (t < T) {
         DTP_AD_STAMP(0)
-        const float mB = half_step(sA, sB, IC<S>{}, IC<32 * RSK>{}, IC<S>{}, IC<0>{});
+        float mB = half_step(sA, sB, IC<S>{}, IC<32 * RSK>{}, IC<S>{}, IC<0>{});
+        if constexpr (RAG) {
+          if (p.Skv - (64 * t + 32) < 32) mB = mask_scores(sB, p.Skv - (64 * t + 32));
+        }
         DTP_AD_STAMP(1)
 #ifndef DTP_AD_NO_CHECK
         if (__any(mB > THR)) rebase(sB, mB, THR);
@@ -465,11 +497,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : (D <= 40 ? 3 : (D <= 80 ? 2 
         asm volatile("" ::: "memory");
         DTP_AD_STAMP(4)
 #ifndef DTP_AD_NO_DMA
-        if (t + NS - 1 < T) DTP_AD_ISSUE(SI)
+        if (t + NS - 1 < T) DTP_AD_ISSUE(SI, t + NS - 1)
 #endif
         DTP_AD_STAMP(5)
         // (the last tile's second half multiplies whatever the next slot holds -- finite -- into scores nobody uses, without a check)
-        const float mA = half_step(sB, sA, IC<SN>{}, IC<0>{}, IC<S>{}, IC<32 * RSV>{});
+        float mA = half_step(sB, sA, IC<SN>{}, IC<0>{}, IC<S>{}, IC<32 * RSV>{});
+        if constexpr (RAG) {
+          if (t + 1 < T && p.Skv - 64 * (t + 1) < 32) mA = mask_scores(sA, p.Skv - 64 * (t + 1));
+        }
         DTP_AD_STAMP(6)
 #ifndef DTP_AD_NO_CHECK
         if (t + 1 < T && __any(mA > THR)) rebase(sA, mA, THR);
@@ -515,23 +550,27 @@ int launch(const AttnParams& p, hipStream_t s) {
   static bool init = false;
   if (!init) {
     (void)hipFuncSetAttribute((const void*)attn_dma_kernel<D, NS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
+    (void)hipFuncSetAttribute((const void*)attn_dma_kernel<D, NS, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
     init = true;
   }
   const int qblocks = (p.Sq + 32 * NW - 1) / (32 * NW);
-  hipLaunchKernelGGL((attn_dma_kernel<D, NS, NW>), dim3(qblocks * p.H * p.B), dim3(64 * NW), G::LDS, s, p, qblocks);
+  if (p.Skv & 63) hipLaunchKernelGGL((attn_dma_kernel<D, NS, NW, true>), dim3(qblocks * p.H * p.B), dim3(64 * NW), G::LDS, s, p, qblocks);
+  else hipLaunchKernelGGL((attn_dma_kernel<D, NS, NW>), dim3(qblocks * p.H * p.B), dim3(64 * NW), G::LDS, s, p, qblocks);
   return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
 }
 
 }  // namespace
 
-// the LDS-DMA kernel takes the launch when every tile is a full 64-key tile and the 32-bit DMA offsets reach the whole sequence
+// the LDS-DMA kernel takes the launch when the 32-bit DMA offsets reach the whole sequence and every tile is a full 64-key tile -- or, at
+// d = 40 / 80, the last one is ragged (more than one tile: the first tile sets every row's softmax reference on real keys)
 bool dtp_attention_dma_supported(const AttnParams& p) {
 #ifdef DTP_EXPERIMENTAL  // d = 160 (levels 2-3, S = 256 / 64): parity-green, but the launches are ramp + one round trip and do not get faster
   if (p.D != 40 && p.D != 80 && p.D != 160) return false;  // (20.0 -> 20.2 us at S = 256, 11.3 -> 13.3 us at S = 64 inside a stamp): not in the product build
 #else
   if (p.D != 40 && p.D != 80) return false;
 #endif
-  if (p.Skv < (p.D == 160 ? 64 : 128) || (p.Skv & 63) || p.Sq < 1) return false;
+  if ((p.Skv & 63) ? (p.D == 160 || p.Skv <= 64) : p.Skv < (p.D == 160 ? 64 : 128)) return false;
+  if (p.Sq < 1) return false;
   if ((p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.ldo & 3)) return false;
   if (((uintptr_t)p.K & 15) || ((uintptr_t)p.V & 15) || ((uintptr_t)p.Q & 15) || ((uintptr_t)p.O & 7)) return false;
   if ((p.kbs & 7) || (p.vbs & 7) || (p.qbs & 7) || (p.obs & 3)) return false;

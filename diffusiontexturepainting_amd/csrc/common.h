@@ -254,6 +254,8 @@ enum {
   GF_XCDSPLIT = 1 << 23,// internal (set by the launcher): 1-D grid of tiles x splits blocks, K-slice z pinned to XCD z % 8 (see dtp_xcd_split)
   GF_GNSTATS = 1 << 24, // convws_kernel only (unsplit, two-n-tile builds): also emit the per-(pixel tile, group) sums / sums of squares of the
                         // rounded output for the GroupNorm that consumes it -> st_out [image][2 * tiles][N / gn_cpg][2] (conv_ws.hip)
+  GF_RAGGED = 1 << 25,  // convws_kernel variants 2 / 3 may cover a map whose size is not a multiple of the 8 x 16 tile (and take the
+                        // GF_UPS2 window cropped to 2 Hi - 1); set by the builder at resolutions that are not multiples of 64 only
   GF_GNAPPLY = 1 << 22, // conv_halo_kernel only: A is the RAW pre-GroupNorm tensor; the staged input patch is normalised (+ SiLU) in LDS
                         // from the statistics partials gn_part (GemmParams::gn_*): no apply launch, no normalised tensor
 };
@@ -405,6 +407,7 @@ struct AttnParams {
 };
 int dtp_launch_attention(const AttnParams& p, hipStream_t s);
 // attn_dma.hip: K / V by LDS-DMA, V^T fragments by transpose reads (d = 40 / 80, Skv a multiple of 64); dtp_launch_attention dispatches
+bool dtp_attention_uses_dma(const AttnParams& p);  // dtp_launch_attention hands p to attn_dma_kernel
 bool dtp_attention_dma_supported(const AttnParams& p);
 int dtp_launch_attention_dma(const AttnParams& p, hipStream_t s, int nw_force = 0);
 // attention_fp8.hip: the same contraction on the fp8 (e4m3) MX MFMA; q_scale / v_scale = per-tensor scales (powers of two)
@@ -590,6 +593,7 @@ bool dtp_conv_ws_supported(const GemmParams& p, int variant, int nsplit);
 int dtp_launch_conv_ws(const GemmParams& p, int variant, hipStream_t s);
 void dtp_conv_ws_init();
 size_t dtp_conv_ws_packed_elems(int Cout, int Cin, int Cin2);
+int dtp_conv_ws_gn_chunks(int Ho, int Wo);  // GF_GNSTATS partials per image (two per 8 x 16 pixel tile, partial tiles included)
 int dtp_launch_pack_conv_ws(const float* w, const float* w1, f16* out, int Cout, int Cin, int Cin2, hipStream_t s);
 // gemm_ws.hip: weight-streaming dense GEMM (64 x 64 per workgroup, the waves split the contraction by k-blocks)
 bool dtp_gemm_ws_supported(const GemmParams& p, int nsplit);

@@ -104,7 +104,9 @@ __device__ __forceinline__ void rd_frags(f16x8 (&dst)[G::TM], uint32_t ct) {
   }
 }
 
-template <int TH, int TW, int NI, int NT, bool NTW, bool CO = false>
+// RAG (GF_RAGGED): the map is covered by ceil(H / TH) x ceil(W / TW) tiles; pixels of the last row / column of tiles that
+// lie outside it read zeros (patch and shortcut), store nothing and add nothing to the GroupNorm sums.  RAG = false is the aligned build.
+template <int TH, int TW, int NI, int NT, bool NTW, bool CO = false, bool RAG = false>
 __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParams p) {
   using G = WsGeom<TH, TW, NI, NT, CO>;
   constexpr int TM = G::TM, HL = G::HL, PW = G::PW, PH = G::PH, HP1 = G::HP1, PB = G::PBYTES, NTM = NT * TM;
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
   // a 20-50 us launch.  Map sizes and tile counts are powers of two everywhere in this model: shifts on that path, one division pair
   // for the block index, none for the K-slices of an unsplit launch; the general forms stay as the fallback.)
   const int H = p.Ho, W = p.Wo;
-  const int tiles_x = W / TW, tiles_y = H / TH;  // (TW, TH: compile-time powers of two)
+  const int tiles_x = RAG ? (W + TW - 1) / TW : W / TW, tiles_y = RAG ? (H + TH - 1) / TH : H / TH;  // (TW, TH: compile-time powers of two)
   const int hw = H * W;
   const bool pow2 = ((hw & (hw - 1)) | (tiles_x & (tiles_x - 1)) | (tiles_y & (tiles_y - 1))) == 0;
   const int images = pow2 ? (p.M >> __builtin_ctz(hw)) : p.M / hw;
@@ -344,6 +346,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
       for (int j = 0; j < TM; ++j) {
         const int il = j / G::TPI, py = G::RPT * (j % G::TPI) + pyl;
         voffT[j] = ((((img0 + il) * H + y0 + py) * W + x0 + pxl) * p.lda2 + 8 * fhalf) * 2;
+        if (RAG && (y0 + py >= H || x0 + pxl >= W)) voffT[j] = OOB;  // outside the map: zeros
       }
       int tbase[NT];
 #pragma unroll
@@ -455,6 +458,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = ((v0[e] + v1[e]) + v2[e]) + v3[e];
         const int il = j / G::TPI, py = G::RPT * (j % G::TPI) + epyl;
+        if (RAG && (y0 + py >= H || x0 + epxl >= W)) continue;  // outside the map: no store, no residual, no statistics
         const size_t m = ((size_t)(img0 + il) * H + y0 + py) * W + x0 + epxl;
         if (!ncol) continue;
         if (p.splits > 1) {
@@ -526,7 +530,8 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
 template <int TH, int TW, int NI, int NT, bool CO = false>
 int launch_ws(const GemmParams& p, hipStream_t s) {
   using G = WsGeom<TH, TW, NI, NT, CO>;
-  const int npg = (p.M / (p.Ho * p.Wo) / NI) * (p.Ho / TH) * (p.Wo / TW);
+  const bool rag = (p.Ho % TH) || (p.Wo % TW);  // (only with GF_RAGGED: dtp_conv_ws_supported)
+  const int npg = (p.M / (p.Ho * p.Wo) / NI) * ((p.Ho + TH - 1) / TH) * ((p.Wo + TW - 1) / TW);
   const int nrs = (((p.N + 31) >> 5) + NT - 1) / NT;
   const int units = nrs * p.splits;
   const int blocks = (units & 7) == 0 ? units * npg : ((npg + 7) >> 3) * 8 * units;  // the kernel's two block -> (pixel group, unit) maps
@@ -536,6 +541,13 @@ int launch_ws(const GemmParams& p, hipStream_t s) {
   GemmParams q = p;
   q.sm_valid = dbg & 3;
   const bool nt = (dbg & 4) ? false : (dbg & 8) ? true : npg == 1;
+  if constexpr (NI == 1 && NT == 2) {
+    if (rag) {
+      if (nt) hipLaunchKernelGGL((convws_kernel<TH, TW, NI, NT, true, CO, true>), dim3(blocks), dim3(256), G::LDS, s, q);
+      else hipLaunchKernelGGL((convws_kernel<TH, TW, NI, NT, false, CO, true>), dim3(blocks), dim3(256), G::LDS, s, q);
+      return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
+    }
+  }
   if (nt) hipLaunchKernelGGL((convws_kernel<TH, TW, NI, NT, true, CO>), dim3(blocks), dim3(256), G::LDS, s, q);
   else hipLaunchKernelGGL((convws_kernel<TH, TW, NI, NT, false, CO>), dim3(blocks), dim3(256), G::LDS, s, q);
   return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
@@ -545,6 +557,10 @@ template <int TH, int TW, int NI, int NT, bool CO = false>
 void set_ws_attr() {
   (void)hipFuncSetAttribute((const void*)convws_kernel<TH, TW, NI, NT, true, CO>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<TH, TW, NI, NT, CO>::LDS);
   (void)hipFuncSetAttribute((const void*)convws_kernel<TH, TW, NI, NT, false, CO>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<TH, TW, NI, NT, CO>::LDS);
+  if constexpr (NI == 1 && NT == 2) {  // the ragged builds of variants 2 / 3
+    (void)hipFuncSetAttribute((const void*)convws_kernel<TH, TW, NI, NT, true, CO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<TH, TW, NI, NT, CO>::LDS);
+    (void)hipFuncSetAttribute((const void*)convws_kernel<TH, TW, NI, NT, false, CO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<TH, TW, NI, NT, CO>::LDS);
+  }
 }
 
 }  // namespace
@@ -555,6 +571,9 @@ void dtp_conv_ws_init() {
   set_ws_attr<8, 16, 1, 2>();
   set_ws_attr<8, 16, 1, 2, true>();
 }
+
+// GF_GNSTATS partials per image of a variant 2 / 3 launch: two per 8 x 16 pixel tile (ragged maps: the partial tiles count)
+int dtp_conv_ws_gn_chunks(int Ho, int Wo) { return 2 * ((Ho + 7) / 8) * ((Wo + 15) / 16); }
 
 // elements of the packing: the 3x3 fragments, then (Cin2 > 0) the fragments of the fused 1x1 shortcut
 size_t dtp_conv_ws_packed_elems(int Cout, int Cin, int Cin2) { return (size_t)((Cout + 31) / 32) * ((size_t)(Cin / 64) * 36 + (size_t)(Cin2 / 64) * 4) * 512; }
@@ -575,21 +594,26 @@ int dtp_launch_pack_conv_ws(const float* w, const float* w1, f16* out, int Cout,
 
 // variant 0: pixel group = three 8 x 8 images (the image IS the tile), one n-tile per workgroup; variant 1: one 16 x 16 image, one
 // n-tile; variant 2: an 8 x 16 pixel tile of one image of any size (H % 8 == 0, W % 16 == 0), TWO n-tiles (64 output channels) per
-// workgroup; variant 3: variant 2 built for two co-resident workgroups per CU (WsGeom CO).  Stride 1, pad 1 (optionally over the nearest-2x upsample of the input: GF_UPS2), Cin % 64 == 0 (and Cin2 % 64 == 0 with a fused shortcut).  nsplit K-slices (<= Cin / 64), each a
+// workgroup; variant 3: variant 2 built for two co-resident workgroups per CU (WsGeom CO).  Variants 2 / 3 with GF_RAGGED: a map of any
+// size (ceil(H / 8) x ceil(W / 16) tiles, the ragged build), and with GF_UPS2 an output of 2 Hi - 1 (the upsample cropped by one row /
+// column: the reference's interpolate(size=skip) at an odd level).  Stride 1, pad 1 (optionally over the nearest-2x upsample of the input: GF_UPS2), Cin % 64 == 0 (and Cin2 % 64 == 0 with a fused shortcut).  nsplit K-slices (<= Cin / 64), each a
 // range of whole channel blocks; nsplit > 1 leaves fp32 slabs.
 bool dtp_conv_ws_supported(const GemmParams& p, int variant, int nsplit) {
   if (!p.Wfr || !(p.flags & GF_CONV3) || p.batch > 1) return false;
   if (p.A2 && ((p.Cin2 & 63) || (p.lda2 & 7) || (size_t)p.M * p.lda2 * 2 >= ((size_t)1 << 31))) return false;
   if (p.flags & (GF_GEGLU | GF_OUT_F32 | GF_LNFOLD | GF_ROWSTATS | GF_BIAS_M | GF_GELU | GF_QUICKGELU | GF_SILU | GF_GNAPPLY | GF_SOFTMAX16)) return false;
   if (p.stride != 1 || p.pad != 1 || (p.Cin & 63) || (p.N & 3) || (p.lda & 7) || (p.ldc & 3)) return false;
-  if (p.flags & GF_UPS2) { if (p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi) return false; }   // the window slides over the nearest-2x upsample
+  const bool rag = (p.flags & GF_RAGGED) != 0;
+  if (p.flags & GF_UPS2) {  // the window slides over the nearest-2x upsample (cropped by one row / column: ragged builds only)
+    if ((p.Ho != 2 * p.Hi && !(rag && p.Ho == 2 * p.Hi - 1)) || (p.Wo != 2 * p.Wi && !(rag && p.Wo == 2 * p.Wi - 1))) return false;
+  }
   else if (p.Ho != p.Hi || p.Wo != p.Wi) return false;
   if ((p.flags & GF_RESID) && (p.ldr & 3)) return false;
   if (p.Ho < 1 || p.Wo < 1 || p.M % (p.Ho * p.Wo)) return false;
   const int images = p.M / (p.Ho * p.Wo);
   if (variant == 0) { if (p.Ho != 8 || p.Wo != 8 || images % 3) return false; }
   else if (variant == 1) { if (p.Ho != 16 || p.Wo != 16) return false; }
-  else if (variant == 2 || variant == 3) { if ((p.Ho & 7) || (p.Wo & 15)) return false; }
+  else if (variant == 2 || variant == 3) { if (((p.Ho & 7) || (p.Wo & 15)) && !rag) return false; }
   else return false;
   if (p.flags & GF_GNSTATS) {  // statistics for the consuming GroupNorm: unsplit launches of the two-n-tile builds, groups of <= 64 channels
     if (variant < 2 || nsplit != 1 || !p.st_out || p.gn_cpg < 4 || p.gn_cpg > 64 || (p.N % p.gn_cpg) || p.N / p.gn_cpg > 32) return false;

@@ -379,12 +379,13 @@ static int lnlin_default_ranges(const GemmParams& p) {
 // buffer (ldc > N) is claimed when the next GroupNorm runs over that view alone (down path: the skip slot IS the layer output) and not
 // when it runs over the whole concatenation (up path); the tuner's credit stays a shape-level estimate.
 bool dtp_conv_output_can_carry_gn_stats(const GemmParams& p) {
-  const int keep = GF_BIAS | GF_RESID | GF_CONV3 | GF_UPS2 | GF_MFAST;
+  const int keep = GF_BIAS | GF_RESID | GF_CONV3 | GF_UPS2 | GF_MFAST | GF_RAGGED;
   if ((p.flags & ~keep) || !(p.flags & GF_CONV3) || p.batch > 1) return false;
   if ((p.N % 32) || p.N / 32 < 4 || p.N / 32 > 64) return false;
   // every block of the consumer re-reads its image's whole partials table (chunks x 32 x 8 bytes): beyond ~1k chunks (the VAE's 512^2 and
   // 256^2 maps: 1 MB per image) that is more traffic than the statistics pass it replaces (round-4 advisor) -- those keep the pass
-  if ((p.Ho & 7) || (p.Wo & 15) || 2 * (p.Ho / 8) * (p.Wo / 16) > 1024) return false;
+  if (!(p.flags & GF_RAGGED) && ((p.Ho & 7) || (p.Wo & 15))) return false;
+  if (dtp_conv_ws_gn_chunks(p.Ho, p.Wo) > 1024) return false;
   return true;
 }
 
@@ -419,7 +420,7 @@ static std::vector<MemRange> gemm_operand_ranges(const GemmParams& gp, long long
 // and writes x itself).  Re-pushes the conv with GF_NOREDUCE and returns its parameters.
 bool Builder::claim_reduce(const T& x, GemmParams& gp, int& bias_step_off, bool allow_concat) {
   const LastGemm lg = prog->last_gemm;
-  const int keep = GF_BIAS | GF_RESID | GF_CONV3 | GF_UPS2 | GF_MFAST;
+  const int keep = GF_BIAS | GF_RESID | GF_CONV3 | GF_UPS2 | GF_MFAST | GF_RAGGED;
   // round 5 (allow_concat): x may be a zero-copy concatenation [producer's N channels | skip] -- the split producer wrote (will write) the
   // FIRST lg.p.N channels of x's rows; the single-launch reduce + GroupNorm sums those from the slabs and reads the rest from x itself
   const bool whole = lg.p.N == x.C;
@@ -451,7 +452,7 @@ bool Builder::claim_stats(const T& x, float** partials, int* nchunk) {
       lg.p.M != (int)x.rows() || lg.p.N != x.C || !dtp_conv_output_can_carry_gn_stats(lg.p))
     return false;
   GemmParams gp = lg.p;
-  const int chunks = 2 * (gp.Ho / 8) * (gp.Wo / 16);
+  const int chunks = dtp_conv_ws_gn_chunks(gp.Ho, gp.Wo);
   // The conv's input (and residual / shortcut operand) may already be back in the pool -- gn_conv3 releases it before its consumer is
   // built -- and the pool would happily hand that very block out for the partials, which the re-pushed conv WRITES while other
   // workgroups still read the operand (round-4 advisor: a latent aliasing race): pool_get_clear_of.
@@ -1015,6 +1016,7 @@ int Builder::conv3(const T& x, const ConvW& w, int stride, int pad, bool ups, in
   p.nkb = w.ldw / 64;
   p.Hi = x.H; p.Wi = x.W; p.Ho = Ho; p.Wo = Wo; p.Cin = w.cin; p.stride = stride; p.pad = pad;
   p.flags = GF_CONV3 | (ups ? GF_UPS2 : 0) | extra_flags;
+  if (c->R % 64) p.flags |= GF_RAGGED;  // ragged maps: convws_kernel may cover them with partial 8 x 16 tiles
   if (tail) { p.A2 = tail->p; p.lda2 = tail->ld; p.Cin2 = w.cin2; }
   p.Wcb = w.wcb;
   p.Wfr = w.wfr;
@@ -1242,7 +1244,8 @@ int Builder::attention(const T& q, const T& k, const T& v, int heads, int Sq, in
          }
          return dtp_launch_attention_fp8(a, qs ? *qs : 1.0f, vs ? *vs : 1.0f, s);
        },
-       "attn B=" + std::to_string(Bn) + " Sq=" + std::to_string(Sq) + " Skv=" + std::to_string(Skv) + " D=" + std::to_string(a.D));
+       "attn B=" + std::to_string(Bn) + " Sq=" + std::to_string(Sq) + " Skv=" + std::to_string(Skv) + " D=" + std::to_string(a.D) +
+           (!fp8 && dtp_attention_uses_dma(a) ? " dma" : ""));
   return DTP_OK;
 }
 
@@ -1272,8 +1275,8 @@ int Builder::resnet(const T& x, const ResW& w, float eps, bool temb, T& y, const
 extern "C" {
 
 int dtp_create(int device, int resolution, int max_batch, dtp_ctx** out) {
-  if (!out || resolution < 64 || resolution % 64 || max_batch < 1 || max_batch > 64) {
-    dtp_set_error("dtp_create: resolution must be a positive multiple of 64, 1 <= max_batch <= 64");
+  if (!out || resolution < 64 || resolution % 8 || max_batch < 1 || max_batch > 64) {
+    dtp_set_error("dtp_create: resolution must be a multiple of 8 and at least 64, 1 <= max_batch <= 64 (got resolution %d, max_batch %d)", resolution, max_batch);
     return DTP_ERR_ARG;
   }
   HIP_CHECK(hipSetDevice(device));

@@ -156,7 +156,9 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
   const int kc = (((lane & 7) ^ ((lrow >> 1) & 7)) << 3);  // element offset inside the k-block
   constexpr bool conv = CONV;
   const int ups = (p.flags & GF_UPS2) ? 1 : 0;
-  const int Hlim = p.Hi << ups, Wlim = p.Wi << ups;
+  // with GF_UPS2 the window slides over the nearest-2x upsample CROPPED to the output size (Ho = 2 Hi or 2 Hi - 1: the reference's
+  // interpolate(size=skip) at an odd level) -- the crop's last row / column is padding, not the upsample's
+  const int Hlim = ups ? p.Ho : p.Hi, Wlim = ups ? p.Wo : p.Wi;
 
   // DMA pieces are buffer loads: a per-lane 32-bit byte offset (loop constant for the dense operands), the k advance in the scalar
   // offset, so a piece costs no vector arithmetic and no 64-bit pointer select.  A lane whose row / pixel does not exist carries

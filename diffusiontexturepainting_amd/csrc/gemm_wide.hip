@@ -71,7 +71,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
   const int kc = (((lane & 7) ^ ((lrow >> 1) & 7)) << 3);  // RPR % 16 == 0: the key does not depend on the round i
   const bool conv = (p.flags & GF_CONV3) != 0;
   const int ups = (p.flags & GF_UPS2) ? 1 : 0;
-  const int Hlim = p.Hi << ups, Wlim = p.Wi << ups;
+  const int Hlim = ups ? p.Ho : p.Hi, Wlim = ups ? p.Wo : p.Wi;  // GF_UPS2: the upsample cropped to the output size (gemm_conv.hip)
 
   // DMA pieces are buffer loads (32-bit lane offsets, scalar k advance, out-of-range zero fill): see gemm_conv.hip
   constexpr int OOB = (int)0x80000000u;

@@ -917,6 +917,12 @@ int dtp_set_option(dtp_ctx* ctx, const char* name, int value) {
     c->graphs.clear();
     return DTP_OK;
   }
+  // the fp8 options are parity-only (inside the 1e-2 gate at multiples of 64) and were never measured at the ragged
+  // maps of a resolution that is a multiple of 8 but not of 64: refused there
+  if (value && c->R % 64 && (!strcmp(name, "fp8_linear") || !strcmp(name, "fp8_operands") || !strcmp(name, "fp8_attention"))) {
+    dtp_set_error("dtp_set_option: %s is parity-only and not offered at resolution %d (a multiple of 8 that is not a multiple of 64)", name, c->R);
+    return DTP_ERR_STATE;
+  }
   if (!strcmp(name, "fp8_linear")) {
     if (!c->unet_progs.empty() && c->fp8_linear != (value != 0)) {
       dtp_set_error("dtp_set_option: fp8_linear must be chosen before the first UNet program is built");

@@ -530,7 +530,11 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
   // writes channels [0, Cx) of the same buffer through the row stride, so no concat kernel ever runs.
   const int Cs[12] = {320, 320, 320, 320, 640, 640, 640, 1280, 1280, 1280, 1280, 1280};   // skip k, in push order
   const int Cx[12] = {1280, 1280, 1280, 1280, 1280, 1280, 1280, 640, 640, 640, 320, 320};  // x at up position p = 11-k
-  const int Hs[12] = {h, h, h, h / 2, h / 2, h / 2, h / 4, h / 4, h / 4, h / 8, h / 8, h / 8};
+  // Level sizes: each stride-2, pad-1 downsampler gives ceil(n / 2) (R a multiple of 8 but not of 64 leaves odd levels).
+  // Every up-block upsampler then writes its skip's size, 2 n or 2 n - 1 (the reference's interpolate(size=skip)); for h % 8 == 0
+  // this is the exact halving / doubling it always was.
+  const int L1 = (h + 1) / 2, L2 = (L1 + 1) / 2, L3 = (L2 + 1) / 2;
+  const int Hs[12] = {h, h, h, L1, L1, L1, L2, L2, L2, L3, L3, L3};
   T cat[12], skipv[12], xslot[12];
   for (int k = 0; k < 12; ++k) {
     const int cx = Cx[11 - k];
@@ -576,7 +580,7 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
     }
     if (i < 3) {
       T y;
-      RC(b.conv3(x, u.down_conv[i], 2, 1, false, x.H / 2, x.W / 2, nullptr, -1, y, 0, nullptr, 0, nullptr, &skipv[sk++]));
+      RC(b.conv3(x, u.down_conv[i], 2, 1, false, (x.H + 1) / 2, (x.W + 1) / 2, nullptr, -1, y, 0, nullptr, 0, nullptr, &skipv[sk++]));
       x = y;
     }
   }
@@ -610,7 +614,8 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
     }
     if (i < 3) {
       T y;
-      RC(b.conv3(x, u.up_conv[i], 1, 1, true, x.H * 2, x.W * 2, nullptr, -1, y, 0, nullptr, 0, nullptr, &xslot[pk]));
+      // nearest upsample to the skip's size (2 n or 2 n - 1): the x2 window of GF_UPS2, cropped by the output size
+      RC(b.conv3(x, u.up_conv[i], 1, 1, true, xslot[pk].H, xslot[pk].W, nullptr, -1, y, 0, nullptr, 0, nullptr, &xslot[pk]));
       b.release(x);
       x = y;
     }
@@ -643,7 +648,11 @@ int launch_nhwc_f32_to_nchw(const float* x, float* y, int B, int C, int HW, int 
 }
 
 int get_unet_prog(Ctx* c, int N, int dupB, UNetProg** out) {
-  if (!c->dedupe_prefix || dupB >= N) dupB = 0;
+  // (the prefix's one row-copy launch moves 16-byte aligned segments: the level-0 row statistics -- dupB * h^2 rows at a pitch of N * h^2
+  // rows, 8 bytes each -- are that only when both counts are even; an odd latent size (R a multiple of 8 but not of 16)
+  // with an odd dupB or N evaluates every sample)
+  const long long hw = (long long)c->h * c->h;
+  if (!c->dedupe_prefix || dupB >= N || (dupB * hw) % 2 || (N * hw) % 2) dupB = 0;
   const int key = N * 128 + dupB;  // dupB <= max_batch <= 64: unique
   auto it = c->unet_progs.find(key);
   if (it == c->unet_progs.end()) {

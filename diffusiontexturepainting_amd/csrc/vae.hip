@@ -77,8 +77,19 @@ static int vae_attention(Builder& b, const T& x, const VaeAttnW& w, T& out) {
   RC(b.gn(x, w.gn, 1e-6f, false, t));
   RC(b.linear(t, w.qk, nullptr, 0, qk));
   o = b.alloc(x.B, x.H, x.W, C);
-  T sc = b.alloc(1, 1, S, S), vt = b.alloc(1, 1, C, S);
+  // S = h^2 is a multiple of 64 when R is a multiple of 64; otherwise the rows of the scores and of V^T -- the
+  // contraction of P V -- are padded to whole 64-wide k-blocks whose tail columns are zero, once per evaluation
+  const int Sp = (S % 64) ? (S + 63) / 64 * 64 : S;
+  T sc = b.alloc(1, 1, S, Sp), vt = b.alloc(1, 1, C, Sp);
   if (!o.p || !sc.p || !vt.p) return DTP_ERR_HIP;
+  if (Sp != S) {
+    const T scz = sc, vtz = vt;
+    b.push(PK_ELEM, 0.0, 2.0 * ((double)S + C) * Sp, [=](hipStream_t s, int) {
+      HIP_CHECK(hipMemsetAsync(scz.p, 0, (size_t)S * Sp * sizeof(f16), s));
+      HIP_CHECK(hipMemsetAsync(vtz.p, 0, (size_t)C * Sp * sizeof(f16), s));
+      return DTP_OK;
+    }, "vae attention: zero the k-block tails S=" + std::to_string(S));
+  }
   const float scale = 1.0f / sqrtf((float)C);
   for (int bi = 0; bi < B; ++bi) {
     auto push = [&](GemmParams g) {
@@ -93,19 +104,19 @@ static int vae_attention(Builder& b, const T& x, const VaeAttnW& w, T& out) {
     GemmParams g = {};
     // V^T[c][s] = Wv[c][:] . t[s][:] + bv[c]
     g.A = w.wv; g.W = t.p + (size_t)bi * S * t.ld; g.C = vt.p; g.bias = w.bv;
-    g.M = C; g.N = S; g.K = C; g.lda = C; g.ldw = t.ld; g.ldc = S; g.flags = GF_BIAS_M;
+    g.M = C; g.N = S; g.K = C; g.lda = C; g.ldw = t.ld; g.ldc = Sp; g.flags = GF_BIAS_M;
     push(g);
     // scores[q][k] = Q[q][:] . K[k][:]
     g = GemmParams();
     g.A = qk.p + (size_t)bi * S * qk.ld; g.W = qk.p + (size_t)bi * S * qk.ld + C; g.C = sc.p;
-    g.M = S; g.N = S; g.K = C; g.lda = qk.ld; g.ldw = qk.ld; g.ldc = S;
+    g.M = S; g.N = S; g.K = C; g.lda = qk.ld; g.ldw = qk.ld; g.ldc = Sp;
     push(g);
     const T scc = sc;
-    b.push(PK_SOFTMAX, 0.0, 4.0 * (double)S * S, [=](hipStream_t s, int) { return dtp_launch_softmax_rows(scc.p, S, scc.p, S, S, S, scale, s); });
+    b.push(PK_SOFTMAX, 0.0, 4.0 * (double)S * S, [=](hipStream_t s, int) { return dtp_launch_softmax_rows(scc.p, Sp, scc.p, Sp, S, S, scale, s); });
     // O[q][c] = P[q][:] . V^T[c][:]
     g = GemmParams();
     g.A = sc.p; g.W = vt.p; g.C = o.p + (size_t)bi * S * o.ld;
-    g.M = S; g.N = C; g.K = S; g.lda = S; g.ldw = S; g.ldc = o.ld;
+    g.M = S; g.N = C; g.K = S; g.lda = Sp; g.ldw = Sp; g.ldc = o.ld;
     push(g);
   }
   b.release(t); b.release(qk); b.release(sc); b.release(vt);

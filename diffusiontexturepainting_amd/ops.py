@@ -225,7 +225,7 @@ def conv3x3(x, wp, cout, stride=1, pad=1, upsample=False, bias=None, resid=None,
         d.Wfr = wfr.data_ptr()
     st = None
     if gn_groups:  # tiles 53 / 54, unsplit: also return the GroupNorm partial sums f32 [B, 2 * tiles, groups, 2] of the output
-        st = torch.full((b, 2 * (ho // 8) * (wo // 16), gn_groups, 2), float("nan"), dtype=torch.float32, device=x.device)
+        st = torch.full((b, 2 * ((ho + 7) // 8) * ((wo + 15) // 16), gn_groups, 2), float("nan"), dtype=torch.float32, device=x.device)
         d.st_out, d.gn_cpg = st.data_ptr(), cout // gn_groups
         d.flags |= _lib.GF_GNSTATS
     check(lib.dtp_op_gemm(C.byref(d), _stream()), "conv3x3")

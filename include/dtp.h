@@ -34,7 +34,9 @@ const char* dtp_last_error(void);
 /* ---------------------------------------------------------------- lifecycle
  * replaces: TRTConditionalInpainter.__init__ (trt_model.py:28-71) -> InpaintPipeline(...)
  * + loadEngines + loadResources (stable_diffusion_pipeline.py:138-162,189-334).
- * `resolution` is fixed per handle like the reference's (run.py:30); max_batch = stamps per call. */
+ * `resolution` is fixed per handle like the reference's (run.py:30): any multiple of 8 from 64 up (the reference's check_dims rule);
+ * at a multiple of 8 that is not one of 64 the UNet levels are ceil halvings of R / 8 and the parity-only fp8 options
+ * are refused (DTP_ERR_STATE).  max_batch = stamps per call. */
 int dtp_create(int device, int resolution, int max_batch, dtp_ctx** out);
 void dtp_destroy(dtp_ctx* ctx);
 
@@ -250,8 +252,9 @@ typedef struct {
   int ldw8;
   float a_scale, w_scale; /* A8 = e4m3(A / a_scale), W8 = e4m3(W / w_scale) (powers of two); the product is applied to the accumulators */
   int gn_cpg;        /* DTP_GF_GNSTATS (tiles 53 / 54, unsplit): channels per group of the GroupNorm that consumes the output; st_out then
-                        receives f32 [images][2 * (Ho/8) * (Wo/16)][N / gn_cpg][2] partial (sum, sum of squares) of the rounded outputs,
-                        the input of dtp_op_groupnorm_apply */
+                        receives f32 [images][2 * ceil(Ho/8) * ceil(Wo/16)][N / gn_cpg][2] partial (sum, sum of squares) of the rounded
+                        outputs, the input of dtp_op_groupnorm_apply.  DTP_GF_RAGGED (tiles 53 / 54): any Ho x Wo (partial 8 x 16 tiles),
+                        and with upsample2x also Ho = 2 Hi - 1 / Wo = 2 Wi - 1 (the upsample cropped by its last row / column) */
   const void* Wfr;   /* 3x3 conv, tiles 51 .. 54: the weights in MFMA fragment order (dtp_op_pack_conv_ws); dense, tile 55: dtp_op_pack_linear_ws */
   /* dtp_op_gemm_f8f8 only (both operands e4m3 in memory): */
   const void* A8;    /* e4m3 activations [M][lda8] bytes = e4m3(A / a_scale) (dtp_op_quant_e4m3) */
@@ -265,7 +268,7 @@ typedef struct {
 } dtp_gemm_desc;
 enum { DTP_GF_BIAS = 1, DTP_GF_BIAS_M = 2, DTP_GF_RESID = 4, DTP_GF_GEGLU = 8, DTP_GF_GELU = 64, DTP_GF_QUICKGELU = 128,
        DTP_GF_OUT_F32 = 256, DTP_GF_SILU = 512, DTP_GF_LNFOLD = 1024, DTP_GF_ROWSTATS = 2048, DTP_GF_SOFTMAX16 = 4096,
-       DTP_GF_GNSTATS = 1 << 24 };
+       DTP_GF_GNSTATS = 1 << 24, DTP_GF_RAGGED = 1 << 25 };
 
 int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s);
 /* Two-operand e4m3 GEMM (gemm_f8f8_kernel; option "fp8_operands" runs it): C = epilogue(a_scale * w_scale * A8 . W8^T) with A8 / A2_8 / W8
