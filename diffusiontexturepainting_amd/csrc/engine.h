@@ -297,7 +297,16 @@ struct Ctx {
   bool fuse_xattn = true;         // the two grouped GEMMs of a cross-attention as one launch (xattn.hip; $DTP_NO_XATTN=1: off, A/B)
   bool fold_gn_linear = true;     // transformer GroupNorm folded into per-sample proj_in weights at HW >= 1024 ($DTP_NO_FOLD_GN=1: off, A/B)
   bool fuse_reduce_gn = true;     // fold a split-K conv's reduce into the GroupNorm that consumes it ($DTP_NO_FUSE_REDUCE_GN=1: off, A/B)
-  bool pack_ws = false;           // load_conv also builds the fragment-order packing (set while the UNet's weights load; $DTP_NO_WS=1: never)
+  bool pack_ws = false;           // load_conv also builds the fragment-order packing (set while the UNet's / VAE's weights load, from the two below)
+  bool conv_ws = true, conv_ws_vae = true;  // weight-streaming conv: packing + tuner candidates / the VAE's packing ($DTP_NO_WS=1 / $DTP_NO_WS_VAE=1: off, A/B)
+  bool gemm_ws = false;           // fragment-order packing of the Linears for gemmws_kernel, tile 55 ($DTP_GEMMWS=1: on, A/B)
+  bool gn_epilogue = true;        // GroupNorm statistics from the producing conv's epilogue (Builder::claim_stats; $DTP_NO_GN_EPILOGUE=1: off, A/B)
+  bool reduce_in_concat_gn = true;  // ... the split-K reduce folded into a GroupNorm over a concatenation too ($DTP_NO_REDUCE_IN_CONCAT_GN=1: off, A/B)
+  bool gna_lnlin = true;          // GroupNorm applied on lnlin_kernel's resident fragments (Builder::gn_linear; $DTP_NO_GNA_LNLIN=1: off, A/B)
+  bool tune_lnlin = true, tune_halo3 = true;  // lnlin_kernel / the three-image halo tiles among the tuner's candidates ($DTP_NO_LNLIN=1 / $DTP_NO_HALO3=1: off, A/B)
+  bool xchain = true;             // level-0 to_out + cross-attention as one register-chained launch (xchain.hip; $DTP_NO_XCHAIN=1: off, A/B)
+  bool xattn_tiles = true;        // xattn: several column tiles per workgroup where that is one round ($DTP_XATTN_CT1=1: off, A/B)
+  int ffchain = -1;               // FF1 + FF2 + proj_out as one launch (ffchain.hip): < 0 by the row-count gate ($DTP_FFCHAIN=0 / 1: off / on, A/B)
   bool fp8_linear = false;        // UNet transformer Linears / 1x1 convs on the fp8 MX MFMA (configs[4]); fixed once a UNet program exists
   bool fp8_attention = false;     // UNet self-attention on the fp8 MX MFMA (BASELINE configs[4]); fixed once a UNet program exists
   bool fp8_operands = false;      // transformer Linears with K >= DTP_FP8_OPERANDS_MIN_K on e4m3 activations in memory (gemm_f8f8.hip); fixed once a UNet program exists
@@ -361,7 +370,7 @@ struct Builder {
   Ctx* c;
   Prog* prog;
   bool fp8 = false;  // dense Linears pushed through linear() / the transformer tail run on gemm_fp8_kernel when they can
-  bool f8ops = false;  // option fp8_operands: transformer() routes its K >= DTP_FP8_OPERANDS_MIN_K Linears through quant8 / linear8
+  bool f8ops = false;  // option fp8_operands: linear_f8ops() runs the K >= DTP_FP8_OPERANDS_MIN_K Linears through quant8 / linear8
   // append an op; when profiling is on, every launch is bracketed by HIP events on its own stream
   void push(int kind, double flops, double bytes, Op fn, const std::string& label = std::string());
   T alloc(int B, int H, int W, int C);
@@ -387,6 +396,9 @@ struct Builder {
   void release8(const T8& t);
   int quant8(const T& x, const T8& y, bool ln, const RowStats* st);
   int linear8(const T8& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit);
+  // linear() -- or, where option fp8_operands covers w, quant8 + linear8: x quantised after its LayerNorm (statistics `ln`, fixed scale)
+  // or, without `ln`, with a calibrated scale.  release_ln: `ln` goes back to the pool once its last reader is pushed.
+  int linear_f8ops(const T& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit, RowStats* ln, bool release_ln);
   int alloc_stats(long long rows, int C, RowStats& st);  // room for one partial per 64-column tile
   void release_stats(RowStats& st);
   int attention(const T& q, const T& k, const T& v, int heads, int Sq, int Skv, int Bn, T& o);

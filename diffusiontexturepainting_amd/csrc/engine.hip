@@ -173,11 +173,9 @@ int load_conv_with_shortcut(Ctx* c, const std::string& conv, const std::string& 
 
 // fragment-order copy of a packed Linear for gemmws_kernel (gemm_ws.hip) -- while the UNet's weights load (Ctx::pack_ws)
 static int pack_linear_ws(Ctx* c, ConvW& w) {
-  if (!c->pack_ws || w.taps != 1 || (w.K & 63) || w.K < 128 || w.cout < 32 || (w.cout & 3)) return DTP_OK;
-  // opt-in ($DTP_GEMMWS=1): measured in round 4, the kernel matches the tiled ones within +-10 % on the single-round launches and loses
+  // opt-in (Ctx::gemm_ws): measured in round 4, the kernel matches the tiled ones within +-10 % on the single-round launches and loses
   // on the multi-round ones -- without the packing no problem carries Wfr and the tuner never sees tile 55
-  static const bool on = [] { const char* e = getenv("DTP_GEMMWS"); return e && e[0] && e[0] != '0'; }();
-  if (!on) return DTP_OK;
+  if (!c->pack_ws || !c->gemm_ws || w.taps != 1 || (w.K & 63) || w.K < 128 || w.cout < 32 || (w.cout & 3)) return DTP_OK;
   void* p;
   RC(ctx_arena_alloc(c, dtp_gemm_ws_packed_elems(w.cout, w.K) * 2, &p));
   w.wfr = (f16*)p;
@@ -445,10 +443,9 @@ bool Builder::claim_reduce(const T& x, GemmParams& gp, int& bias_step_off, bool 
 // conv_ws.hip) -- the consumer then needs no statistics pass over x.  Re-pushes the conv with the flag and a planned partials buffer
 // [B][nchunk][32][2]; the caller returns the buffer to the pool once its consumer is pushed.
 bool Builder::claim_stats(const T& x, float** partials, int* nchunk) {
-  static const bool off = [] { const char* e = getenv("DTP_NO_GN_EPILOGUE"); return e && e[0] && e[0] != '0'; }();
   const LastGemm lg = prog->last_gemm;
   const DtpTile t = dtp_tile(lg.tile);
-  if (off || !lg.valid || t.fam != TF_CONVWS || t.var < 2 || lg.p.splits != 1 || (f16*)lg.p.C != x.p || lg.p.ldc != x.ld ||
+  if (!c->gn_epilogue || !lg.valid || t.fam != TF_CONVWS || t.var < 2 || lg.p.splits != 1 || (f16*)lg.p.C != x.p || lg.p.ldc != x.ld ||
       lg.p.M != (int)x.rows() || lg.p.N != x.C || !dtp_conv_output_can_carry_gn_stats(lg.p))
     return false;
   GemmParams gp = lg.p;
@@ -474,8 +471,7 @@ int Builder::gn(const T& x, const NormW& n, float eps, bool silu, T& y) {
   Ctx* cc = c;
   GemmParams gp;
   int bso = -1;
-  static const bool concat_off = [] { const char* e = getenv("DTP_NO_REDUCE_IN_CONCAT_GN"); return e && e[0] && e[0] != '0'; }();  // A/B
-  const bool claimed = claim_reduce(x, gp, bso, !concat_off);
+  const bool claimed = claim_reduce(x, gp, bso, cc->reduce_in_concat_gn);
   // The claimed reduce adds the producer's residual INSIDE the GroupNorm launch -- and that residual (a transformer block's input) is
   // normally back in the pool by now, so the pool may hand its block out for y: one workgroup would write y where another still reads
   // the residual.  (With y laid out exactly like the residual every thread reads the element it later overwrites, which is why the
@@ -543,9 +539,8 @@ int Builder::gn_linear(const T& x, const NormW& n, float eps, const ConvW& w, T&
   cc->ws_need = std::max(cc->ws_need, slab_bytes + dtp_groupnorm_ws_bytes(N, HW, C, 32));
   // Round 6: where the activation-stationary Linear takes the problem (K = C in {320, 640}: UNet levels 0-1), the GroupNorm is applied to
   // its RESIDENT activation fragments (lnlin_kernel GNA) -- [statistics ->] ONE launch on the raw tensor with the shared weights; the fold
-  // launch (190 per batch-1 stamp), the per-sample weight copies and the grouped problem disappear.  $DTP_NO_GNA_LNLIN=1: the fold (A/B).
-  static const bool gna_off = [] { const char* e = getenv("DTP_NO_GNA_LNLIN"); return e && e[0] && e[0] != '0'; }();
-  if (!gna_off && (C == 320 || C == 640) && (HW & 127) == 0 && !fp8) {
+  // launch (190 per batch-1 stamp), the per-sample weight copies and the grouped problem disappear.  Ctx::gna_lnlin off: the fold (A/B).
+  if (cc->gna_lnlin && (C == 320 || C == 640) && (HW & 127) == 0 && !fp8) {
     GemmParams g = {};
     g.A = x.p; g.lda = x.ld; g.W = w.w; g.ldw = w.ldw; g.nkb = w.ldw / 64;
     g.M = HW; g.N = w.cout; g.K = w.K;
@@ -709,10 +704,7 @@ void tune_cache_save(Ctx* c) {
 // The first-round candidates of a problem, as configurations (tile id, splits) in the order they are timed.  ws_ok[v]: the
 // weight-streaming conv variant v takes the problem; gw_ok: the weight-streaming GEMM does.
 struct TuneCfg { int tile, sp; };
-static std::vector<TuneCfg> tune_candidates(const GemmParams& p, const bool* ws_ok, bool gw_ok) {
-  static const bool no_lnlin = [] { const char* e = getenv("DTP_NO_LNLIN"); return e && e[0] && e[0] != '0'; }();
-  static const bool no_halo3 = [] { const char* e = getenv("DTP_NO_HALO3"); return e && e[0] && e[0] != '0'; }();
-  static const bool no_ws = [] { const char* e = getenv("DTP_NO_WS"); return e && e[0] && e[0] != '0'; }();
+static std::vector<TuneCfg> tune_candidates(const Ctx* c, const GemmParams& p, const bool* ws_ok, bool gw_ok) {
   static const int cand_splits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
   const bool geglu = (p.flags & GF_GEGLU) != 0;
   std::vector<TuneCfg> out;
@@ -753,7 +745,7 @@ static std::vector<TuneCfg> tune_candidates(const GemmParams& p, const bool* ws_
   {  // the activation-stationary kernel of the short LayerNorm-folded contractions: column ranges per 128-row block
     static const int ranges[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32, 40};
     for (int sp : ranges)
-      if (!no_lnlin && dtp_lnlin_supported(p, sp)) add(DTP_TILE_LNLIN, sp);
+      if (c->tune_lnlin && dtp_lnlin_supported(p, sp)) add(DTP_TILE_LNLIN, sp);
   }
   for (int tile = 0; tile < DTP_TILE_IDS && p.Wcb && dtp_conv_halo_supported(p); ++tile) {  // the halo-tiled conv kernels (Wcb packing)
     const DtpTile t = dtp_tile(tile);
@@ -761,7 +753,7 @@ static std::vector<TuneCfg> tune_candidates(const GemmParams& p, const bool* ws_
     const bool small = p.Hi * p.Wi <= 256;
     // 8x8 pixel tiles for small feature maps, 8x16 otherwise; three images per workgroup: the small maps of a batch-1 stamp, where
     // the weight slices are most of the LDS fill
-    if (t.var < 4 ? (t.var >= 2) != small : (no_halo3 || !small || !dtp_conv_halo3_supported(p))) continue;
+    if (t.var < 4 ? (t.var >= 2) != small : (!c->tune_halo3 || !small || !dtp_conv_halo3_supported(p))) continue;
     for (int sp : cand_splits) {
       if (sp > 1 && p.nkb / sp < 9) break;
       add(tile, sp);
@@ -772,7 +764,7 @@ static std::vector<TuneCfg> tune_candidates(const GemmParams& p, const bool* ws_
     static const int slices[] = {1, 2, 3, 4, 5, 6, 8, 10};
     if (t.fam != TF_CONVWS) continue;
     for (int sp : slices) {
-      if (no_ws || !ws_ok[t.var] || !dtp_conv_ws_supported(p, t.var, sp)) continue;
+      if (!c->conv_ws || !ws_ok[t.var] || !dtp_conv_ws_supported(p, t.var, sp)) continue;
       if (t.var >= 2 && sp > 4) continue;
       add(tile, sp);
     }
@@ -851,7 +843,7 @@ static int tune_gemm(Ctx* c, const GemmParams& p, int* tile, int* sp) {
     };
     struct Cand { float ms; int tile, sp; };
     std::vector<Cand> cands;
-    for (const TuneCfg& cfg : tune_candidates(p, ws_ok, gw_ok)) {
+    for (const TuneCfg& cfg : tune_candidates(c, p, ws_ok, gw_ok)) {
       float ms;
       RC(time_cfg(cfg.tile, cfg.sp, 5, true, &ms));
       cands.push_back({ms, cfg.tile, cfg.sp});
@@ -1209,6 +1201,20 @@ int Builder::linear8(const T8& x, const ConvW& w, const T* resid, int flags, T& 
   return DTP_OK;
 }
 
+int Builder::linear_f8ops(const T& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit, RowStats* ln, bool release_ln) {
+  if (f8ops && w.K >= DTP_FP8_OPERANDS_MIN_K && w.w8) {
+    const T8 x8 = ln ? alloc8(x, x.C, false, DTP_FP8_LN_A_SCALE) : alloc8(x, x.C, true);
+    RC(quant8(x, x8, ln != nullptr, ln));
+    if (ln && release_ln) release_stats(*ln);
+    RC(linear8(x8, w, resid, flags, y, emit));
+    release8(x8);
+    return DTP_OK;
+  }
+  RC(linear(x, w, resid, flags, y, emit, ln));
+  if (ln && release_ln) release_stats(*ln);
+  return DTP_OK;
+}
+
 int Builder::attention(const T& q, const T& k, const T& v, int heads, int Sq, int Skv, int Bn, T& o) {
   o = alloc(Bn, 1, Sq, q.C);
   if (!o.p) return DTP_ERR_HIP;
@@ -1291,13 +1297,18 @@ int dtp_create(int device, int resolution, int max_batch, dtp_ctx** out) {
   c->zero = (f16*)z;
   for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventCreate(&c->ev[i]));
   tune_cache_load(c);
-  if (const char* e = getenv("DTP_NO_FUSE_REDUCE_GN")) c->fuse_reduce_gn = !(e[0] && e[0] != '0');
-  if (const char* e = getenv("DTP_NO_DEDUPE")) c->dedupe_prefix = !(e[0] && e[0] != '0');
+  // the switches that shape a launch program (engine.h), read per context: set, and not "0"
+  auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] && e[0] != '0'; };
+  c->fuse_reduce_gn = !on("DTP_NO_FUSE_REDUCE_GN"); c->dedupe_prefix = !on("DTP_NO_DEDUPE");
 #ifdef DTP_EXPERIMENTAL
-  if (const char* e = getenv("DTP_GN_CONV")) c->fuse_gn_conv = (e[0] && e[0] != '0');
+  c->fuse_gn_conv = on("DTP_GN_CONV");
 #endif
-  if (const char* e = getenv("DTP_NO_XATTN")) c->fuse_xattn = !(e[0] && e[0] != '0');
-  if (const char* e = getenv("DTP_NO_FOLD_GN")) c->fold_gn_linear = !(e[0] && e[0] != '0');
+  c->fuse_xattn = !on("DTP_NO_XATTN"); c->fold_gn_linear = !on("DTP_NO_FOLD_GN");
+  c->conv_ws = !on("DTP_NO_WS"); c->conv_ws_vae = !on("DTP_NO_WS_VAE"); c->gemm_ws = on("DTP_GEMMWS");
+  c->gn_epilogue = !on("DTP_NO_GN_EPILOGUE"); c->reduce_in_concat_gn = !on("DTP_NO_REDUCE_IN_CONCAT_GN"); c->gna_lnlin = !on("DTP_NO_GNA_LNLIN");
+  c->tune_lnlin = !on("DTP_NO_LNLIN"); c->tune_halo3 = !on("DTP_NO_HALO3");
+  c->xchain = !on("DTP_NO_XCHAIN"); c->xattn_tiles = !on("DTP_XATTN_CT1");
+  if (const char* e = getenv("DTP_FFCHAIN")) c->ffchain = atoi(e);
   *out = (dtp_ctx*)c;
   return DTP_OK;
 }

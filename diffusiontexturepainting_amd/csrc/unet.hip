@@ -3,7 +3,6 @@
 // Reference: trt_inference/models.py:1017-1139 (model + LoRA merge + engine I/O); topology
 // SURVEY.md Appendix A.1.
 #include <math.h>
-#include <stdlib.h>
 
 #include "engine.h"
 
@@ -83,7 +82,7 @@ int load_unet_weights(Ctx* c) {
   RC(merge_lora(c));
   struct WsScope {  // the UNet's 3x3 convs also get the fragment-order packing (conv_ws.hip)
     Ctx* c;
-    explicit WsScope(Ctx* cc) : c(cc) { const char* e = getenv("DTP_NO_WS"); c->pack_ws = !(e && e[0] && e[0] != '0'); }
+    explicit WsScope(Ctx* cc) : c(cc) { c->pack_ws = c->conv_ws; }
     ~WsScope() { c->pack_ws = false; }
   } ws_scope(c);
   UNetW& u = c->unet;
@@ -188,32 +187,57 @@ struct Dup {
   T skip_full;     // the conv_in skip view for all N samples (channel slice of a concat buffer)
 };
 
-static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up, T& out, const T* dst = nullptr, const Dup* dup = nullptr) {
-  const int dB = dup ? dup->B : 0;
-  const int C = x.C, S = x.H * x.W, N = x.B + dB;  // x holds the samples that are really evaluated up to the cross-attention
-  T t, y, n1, qkv, a, y2, n2, y3, n3, f;
-  // LayerNorms are folded into their consumer GEMMs; the row statistics ride on the producer's epilogue
-  RowStats st1, st2, st3;
+// One row-copy launch of the de-duplicated prefix: uncond rows <- cond rows of the conv_in skip and the block input, and of the
+// self-attention output y2 and its row statistics st2 where the caller has those in memory
+static void push_dup_copy(Builder& b, const Dup& d, int S, const T* y2 = nullptr, const RowStats* st2 = nullptr) {
+  const long long rB = (long long)d.B * S;
+  CopySegs cs = {};
+  auto seg = [&](const void* src, void* dstp, long long rows, long long row_bytes, long long stride) {
+    cs.src[cs.n] = (const char*)src; cs.dst[cs.n] = (char*)dstp; cs.rows[cs.n] = rows; cs.row_bytes[cs.n] = row_bytes;
+    cs.src_stride[cs.n] = cs.dst_stride[cs.n] = stride; ++cs.n;
+  };
+  auto rows = [&](const T& t) { seg(t.p + rB * t.ld, t.p, rB, (long long)t.C * 2, (long long)t.ld * 2); };
+  rows(d.skip_full); rows(d.x_full);
+  if (y2) rows(*y2);
+  if (st2) seg(st2->buf + rB * 2, st2->buf, st2->parts, rB * 8, (long long)st2->M * 8);
+  double bytes = 0;
+  for (int k = 0; k < cs.n; ++k) bytes += 2.0 * cs.rows[k] * cs.row_bytes[k];
+  b.push(PK_ELEM, 0.0, bytes, [=](hipStream_t s, int) { return dtp_launch_copy_rows(cs, s); }, "dup uncond<-cond rows=" + std::to_string(rB));
+}
+
+// the block output: the caller's destination view, or a fresh buffer -- shaped like `like`
+static int block_out(Builder& b, const T* dst, const T& like, T& out) {
+  if (dst) {
+    if (dst->C != like.C || dst->rows() != like.rows()) { dtp_set_error("transformer: destination view mismatch"); return DTP_ERR_ARG; }
+    out = *dst;
+    return DTP_OK;
+  }
+  out = b.alloc(like.B, like.H, like.W, like.C);
+  return out.p ? DTP_OK : DTP_ERR_HIP;
+}
+
+// One SD transformer block in three stages.  LayerNorms are folded into their consumer GEMMs; the row statistics ride on the producer's
+// epilogue.  Option fp8_operands: q/k/v, to_out and FF1 with K >= DTP_FP8_OPERANDS_MIN_K (the C = 1280 blocks; no de-duplicated prefix
+// reaches them) contract two e4m3 operands (gemm_f8f8.hip, Builder::linear_f8ops).  A LayerNorm'd operand is quantised AFTER the
+// normalisation (fixed scale; gamma / beta stay folded into the packed weights / bias, so its consumer is a plain GF_BIAS GEMM); the
+// attention output gets a calibrated scale.
+
+// Stage 1: GroupNorm + proj_in -> y (with the LayerNorm-1 statistics), q/k/v (LN1 folded), self-attention -> a
+static int self_attention(Builder& b, const T& x, const XfW& w, T& y, T& a) {
+  const int C = x.C, S = x.H * x.W;
+  const bool fold_gn = b.gn_linear_supported(x, w.proj_in);  // levels 0-1: the GroupNorm becomes per-sample proj_in weights (Builder::gn_linear)
+  RowStats st1;
   RC(b.alloc_stats(x.rows(), C, st1));
-  if (b.gn_linear_supported(x, w.proj_in)) {  // levels 0-1: the GroupNorm becomes per-sample proj_in weights (Builder::gn_linear)
+  if (fold_gn) {
     RC(b.gn_linear(x, w.gn, 1e-6f, w.proj_in, y, &st1));
   } else {
+    T t;
     RC(b.gn(x, w.gn, 1e-6f, false, t));
     RC(b.linear(t, w.proj_in, nullptr, 0, y, &st1));
     b.release(t);
   }
-  // option fp8_operands: q/k/v, to_out and FF1 with K >= DTP_FP8_OPERANDS_MIN_K (the C = 1280 blocks; no de-duplicated prefix reaches them)
-  // contract two e4m3 operands (gemm_f8f8.hip).  A LayerNorm'd operand is quantised AFTER the normalisation (fixed scale; gamma / beta stay
-  // folded into the packed weights / bias, so its consumer is a plain GF_BIAS GEMM); the attention output gets a calibrated scale.
-  const bool f8 = b.f8ops;
-  if (f8 && w.qkv.K >= DTP_FP8_OPERANDS_MIN_K && w.qkv.w8) {
-    T8 y8 = b.alloc8(y, C, false, DTP_FP8_LN_A_SCALE);
-    RC(b.quant8(y, y8, true, &st1));
-    RC(b.linear8(y8, w.qkv, nullptr, 0, qkv, nullptr));
-    b.release8(y8);
-  } else {
-    RC(b.linear(y, w.qkv, nullptr, 0, qkv, nullptr, &st1));  // LN1 folded
-  }
+  T qkv;
+  RC(b.linear_f8ops(y, w.qkv, nullptr, 0, qkv, nullptr, &st1, false));  // LN1 folded (e4m3: quantised after LN1)
   b.release_stats(st1);
   T q = qkv, k = qkv, v = qkv;
   q.C = k.C = v.C = C;
@@ -221,52 +245,44 @@ static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up,
   RC(b.attention(q, k, v, 8, S, S, x.B, a));
   b.release(qkv);
   a.B = x.B; a.H = x.H; a.W = x.W;
+  return DTP_OK;
+}
+
+// Stage 2: to_out (+ y), LayerNorm-2 and the cross-attention over the 14 context tokens (+ its residual) -> y3 with the LayerNorm-3
+// statistics st3, for all N samples.  a and y go back to the pool.
+static int cross_attention(Builder& b, const T& x, const XfW& w, const UNetProg& up, const Dup* dup, const T& a, const T& y, T& y3, RowStats& st3) {
+  const int dB = dup ? dup->B : 0;
+  const int C = x.C, S = x.H * x.W, N = x.B + dB, i = w.kv_index, Cp = (C + 127) / 128 * 128;  // x holds the samples evaluated so far
+  // Round 6: at level 0 (C = 320) the output projection, its residual, LayerNorm-2 and the whole fused cross-attention run as ONE
+  // register-chained launch (xchain.hip): y2 and its row statistics never reach memory.  With a de-duplicated prefix the uncond samples
+  // read the cond samples' rows of a and y (the kernel's `dup`): their y2 is recomputed instead of copied.  The launch has one workgroup
+  // per 128 rows: it is used where that is at least a quarter of the CUs (512^2: 96 at batch 1; not the 24 of a 256^2 stamp, where the
+  // two well-parallelised launches it replaces are faster: +2 % per stamp measured).  (Ctx::xchain off: the two launches, A/B.)
+  XchainParams xc = {};
+  xc.A = a.p; xc.lda = a.ld; xc.Wo = w.out1.w; xc.ldwo = w.out1.ldw; xc.bo = w.out1.b; xc.Y = y.p; xc.ldy = y.ld;
+  xc.W1 = up.xW1[i]; xc.w1_bs = (long long)128 * C; xc.b1 = up.xb1[i]; xc.lns1 = up.xl1[i];
+  xc.W2 = up.xW2[i]; xc.w2_bs = (long long)Cp * 128; xc.b2 = w.out2.b;
+  xc.S = S; xc.C = C; xc.N = N; xc.sm_valid = 14; xc.ln_eps = 1e-5f; xc.dup = dB;
+  xc.Y3 = a.p; xc.ldy3 = C;  // (placeholder for the support check)
+  const bool chain = b.c->xchain && b.c->fuse_xattn && !b.fp8 && w.out1.K == C && w.out1.cout == C && !w.out1.lns &&
+                     (long long)(S / 128) * N >= b.c->num_cu / 4 && dtp_xchain_supported(xc);
+  RowStats st2;
   RC(b.alloc_stats((long long)N * S, C, st2));
-  T xin = x;  // the block input for all N samples (residual of the last GEMM)
-  bool chained = false;  // out1 + cross-attention done by xchain_kernel
-  {
-    // Round 6: at level 0 (C = 320) the output projection, its residual, LayerNorm-2 and the whole fused cross-attention run as ONE
-    // register-chained launch (xchain.hip): y2 and its row statistics never reach memory.  With a de-duplicated prefix the uncond samples
-    // read the cond samples' rows of a and y (the kernel's `dup`): their y2 is recomputed instead of copied.  The launch has one workgroup
-    // per 128 rows: it is used where that is at least ~a third of the CUs (512^2: 96 at batch 1; not the 24 of a 256^2 stamp, where the
-    // two well-parallelised launches it replaces are faster: +2 % per stamp measured).  ($DTP_NO_XCHAIN=1: the two launches, A/B.)
-    static const bool xc_off = [] { const char* e = getenv("DTP_NO_XCHAIN"); return e && e[0] && e[0] != '0'; }();
-    XchainParams xc = {};
-    const int i = w.kv_index;
-    xc.A = a.p; xc.lda = a.ld; xc.Wo = w.out1.w; xc.ldwo = w.out1.ldw; xc.bo = w.out1.b; xc.Y = y.p; xc.ldy = y.ld;
-    xc.W1 = up.xW1[i]; xc.w1_bs = (long long)128 * C; xc.b1 = up.xb1[i]; xc.lns1 = up.xl1[i];
-    xc.W2 = up.xW2[i]; xc.w2_bs = (long long)((C + 127) / 128 * 128) * 128; xc.b2 = w.out2.b;
-    xc.S = S; xc.C = C; xc.N = N; xc.sm_valid = 14; xc.ln_eps = 1e-5f; xc.dup = dB;
-    xc.Y3 = a.p; xc.ldy3 = C;  // (placeholder for the support check)
-    if (!xc_off && b.c->fuse_xattn && !b.fp8 && w.out1.K == C && w.out1.cout == C && !w.out1.lns && (long long)(S / 128) * N >= b.c->num_cu / 4 &&
-        dtp_xchain_supported(xc)) {
-      b.release_stats(st2);
-      RC(b.alloc_stats((long long)N * S, C, st3));
-      y3 = b.alloc(N, x.H, x.W, C);
-      if (!y3.p) return DTP_ERR_HIP;
-      xc.Y3 = y3.p; xc.ldy3 = y3.ld; xc.st_out = st3.buf;
-      st3.parts = 1; st3.M = N * S;
-      b.push(PK_XATTN, 2.0 * N * S * ((double)C * C + 2.0 * 128.0 * C), 2.0 * N * (3.0 * S * C + (double)C * C + 2.0 * 128 * C),
-             [=](hipStream_t s, int) { return dtp_launch_xchain(xc, s); }, "xchain M=" + std::to_string(S) + " C=" + std::to_string(C) + " x" + std::to_string(N));
-      chained = true;
-      if (dB > 0) {  // the other two tensors the branches share still get their uncond rows by ONE row-copy launch
-        CopySegs cs = {};
-        const long long rB = (long long)dB * S;
-        const T &sk = dup->skip_full, &xf = dup->x_full;
-        cs.src[0] = (const char*)(sk.p + rB * sk.ld); cs.dst[0] = (char*)sk.p; cs.rows[0] = rB; cs.row_bytes[0] = (long long)sk.C * 2;
-        cs.src_stride[0] = cs.dst_stride[0] = (long long)sk.ld * 2;
-        cs.src[1] = (const char*)(xf.p + rB * xf.ld); cs.dst[1] = (char*)xf.p; cs.rows[1] = rB; cs.row_bytes[1] = (long long)xf.C * 2;
-        cs.src_stride[1] = cs.dst_stride[1] = (long long)xf.ld * 2;
-        cs.n = 2;
-        double bytes = 0;
-        for (int k = 0; k < cs.n; ++k) bytes += 2.0 * cs.rows[k] * cs.row_bytes[k];
-        b.push(PK_ELEM, 0.0, bytes, [=](hipStream_t s, int) { return dtp_launch_copy_rows(cs, s); }, "dup uncond<-cond rows=" + std::to_string(rB));
-        xin = dup->x_full;
-      }
-    }
+  if (chain) {
+    b.release_stats(st2);
+    RC(b.alloc_stats((long long)N * S, C, st3));
+    y3 = b.alloc(N, x.H, x.W, C);
+    if (!y3.p) return DTP_ERR_HIP;
+    xc.Y3 = y3.p; xc.ldy3 = y3.ld; xc.st_out = st3.buf;
+    st3.parts = 1; st3.M = N * S;
+    b.push(PK_XATTN, 2.0 * N * S * ((double)C * C + 2.0 * 128.0 * C), 2.0 * N * (3.0 * S * C + (double)C * C + 2.0 * 128 * C),
+           [=](hipStream_t s, int) { return dtp_launch_xchain(xc, s); }, "xchain M=" + std::to_string(S) + " C=" + std::to_string(C) + " x" + std::to_string(N));
+    if (dB > 0) push_dup_copy(b, *dup, S);  // the other two tensors the branches share
+    b.release(a); b.release(y);
+    return DTP_OK;
   }
-  if (chained) {
-  } else if (dB > 0) {
+  T y2;
+  if (dB > 0) {  // to_out over the evaluated samples, then the uncond rows of everything the branches share by one row copy
     y2 = b.alloc(N, x.H, x.W, C);
     if (!y2.p) return DTP_ERR_HIP;
     const T y2s = samples(y2, dB, x.B);
@@ -274,56 +290,31 @@ static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up,
     T y2v;
     RC(b.linear(a, w.out1, &y, 0, y2v, &st2, nullptr, &y2s));
     st2.M = N * S;
-    // one launch: uncond rows <- cond rows of the skip, the block input, the self-attention output and its row statistics
-    CopySegs cs = {};
-    auto seg = [&](const void* src, void* dstp, long long rows, long long row_bytes, long long sstride, long long dstride) {
-      cs.src[cs.n] = (const char*)src; cs.dst[cs.n] = (char*)dstp; cs.rows[cs.n] = rows; cs.row_bytes[cs.n] = row_bytes;
-      cs.src_stride[cs.n] = sstride; cs.dst_stride[cs.n] = dstride; ++cs.n;
-    };
-    const long long rB = (long long)dB * S;
-    const T &sk = dup->skip_full, &xf = dup->x_full;
-    seg(sk.p + rB * sk.ld, sk.p, rB, (long long)sk.C * 2, (long long)sk.ld * 2, (long long)sk.ld * 2);
-    seg(xf.p + rB * xf.ld, xf.p, rB, (long long)xf.C * 2, (long long)xf.ld * 2, (long long)xf.ld * 2);
-    seg(y2.p + rB * y2.ld, y2.p, rB, (long long)C * 2, (long long)y2.ld * 2, (long long)y2.ld * 2);
-    seg(st2.buf + rB * 2, st2.buf, st2.parts, rB * 8, (long long)N * S * 8, (long long)N * S * 8);
-    double bytes = 0;
-    for (int i = 0; i < cs.n; ++i) bytes += 2.0 * cs.rows[i] * cs.row_bytes[i];
-    b.push(PK_ELEM, 0.0, bytes, [=](hipStream_t s, int) { return dtp_launch_copy_rows(cs, s); }, "dup uncond<-cond rows=" + std::to_string(rB));
-    xin = dup->x_full;
-  } else if (f8 && w.out1.K >= DTP_FP8_OPERANDS_MIN_K && w.out1.w8) {
-    T8 a8 = b.alloc8(a, C, true);  // the attention output: calibrated
-    RC(b.quant8(a, a8, false, nullptr));
-    RC(b.linear8(a8, w.out1, &y, 0, y2, &st2));
-    b.release8(a8);
+    push_dup_copy(b, *dup, S, &y2, &st2);
   } else {
-    RC(b.linear(a, w.out1, &y, 0, y2, &st2));
+    RC(b.linear_f8ops(a, w.out1, &y, 0, y2, &st2, nullptr, false));  // (e4m3: the attention output, calibrated)
   }
   b.release(a); b.release(y);
-  if (!chained) {
   // Cross-attention over 14 context tokens: softmax_j(LN2(y2) Wq'^T K^T) V Wo^T collapses to two grouped GEMMs against
   // per-sample matrices prepared once per stamp (UNetProg::xW1 / xW2): scores + group softmax, then the value-output product.
   XattnParams xp = {};
-  {
-    const int i = w.kv_index, Cp = (C + 127) / 128 * 128;
-    xp.X = y2.p; xp.ldx = y2.ld; xp.W1 = up.xW1[i]; xp.w1_bs = (long long)128 * C; xp.b1 = up.xb1[i]; xp.lns1 = up.xl1[i];
-    xp.st_in = st2.buf; xp.st_parts = st2.parts; xp.st_rows = N * S; xp.ln_eps = 1e-5f;
-    xp.W2 = up.xW2[i]; xp.w2_bs = (long long)Cp * 128; xp.b2 = w.out2.b; xp.R = y2.p; xp.ldr = y2.ld;
-    xp.S = S; xp.C = C; xp.N = N; xp.sm_valid = 14; xp.zero = b.c->zero;
-  }
+  xp.X = y2.p; xp.ldx = y2.ld; xp.W1 = up.xW1[i]; xp.w1_bs = (long long)128 * C; xp.b1 = up.xb1[i]; xp.lns1 = up.xl1[i];
+  xp.st_in = st2.buf; xp.st_parts = st2.parts; xp.st_rows = N * S; xp.ln_eps = 1e-5f;
+  xp.W2 = up.xW2[i]; xp.w2_bs = (long long)Cp * 128; xp.b2 = w.out2.b; xp.R = y2.p; xp.ldr = y2.ld;
+  xp.S = S; xp.C = C; xp.N = N; xp.sm_valid = 14; xp.zero = b.c->zero;
   // The fused kernel recomputes the score tile once per 128-column tile of the output: it pays where the pair is launch-bound (few
   // workgroups: levels 1-3 of a batch-1 stamp, every level at 256^2) and loses where the grid already fills the chip several times
   // (level 0 at 512^2: +1.3 ms per stamp; batch 8: +17 ms per batch with everything fused -- same-box A/B).
   // Round 5: a workgroup may take several column tiles (one probability tile, no recomputation) -- taken when the whole launch is then a
   // single round of workgroups (level 0 at batch 1: 64 row blocks x 3 samples x all three tiles = 192 workgroups, one launch instead of
-  // two grouped GEMMs); otherwise one tile per workgroup under the old gate.
+  // two grouped GEMMs); otherwise one tile per workgroup under the old gate (and always with Ctx::xattn_tiles off, A/B).
   const int nt = (C + 127) / 128;
   int ct = dtp_xattn_tiles_per_wg(S, C, N);
-  if ((long long)((S + 63) / 64) * ((nt + ct - 1) / ct) * N > b.c->num_cu) ct = 1;
-  static const bool ct_off = [] { const char* e = getenv("DTP_XATTN_CT1"); return e && e[0] && e[0] != '0'; }();  // A/B: one tile per workgroup as in round 4
-  if (ct_off) ct = 1;
+  if (!b.c->xattn_tiles || (long long)((S + 63) / 64) * ((nt + ct - 1) / ct) * N > b.c->num_cu) ct = 1;
   xp.ct = ct;
   const long long xa_wgs = (long long)((S + 63) / 64) * ((nt + ct - 1) / ct) * N;
-  if (b.c->fuse_xattn && xa_wgs <= 2LL * b.c->num_cu && st2.buf && st2.parts > 0 && st2.M == N * S && dtp_xattn_supported(xp)) {
+  const bool fused = b.c->fuse_xattn && xa_wgs <= 2LL * b.c->num_cu && st2.buf && st2.parts > 0 && st2.M == N * S && dtp_xattn_supported(xp);
+  if (fused) {
     // one launch: scores + group softmax + value-output product + residual (xattn.hip); the probabilities never leave LDS
     RC(b.alloc_stats((long long)N * S, C, st3));
     y3 = b.alloc(N, x.H, x.W, C);
@@ -335,105 +326,101 @@ static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up,
            [=](hipStream_t s, int) { return dtp_launch_xattn(xp, s); }, "xattn M=" + std::to_string(S) + " C=" + std::to_string(C) + " x" + std::to_string(N) + (ct > 1 ? " ct=" + std::to_string(ct) : ""));
     b.release_stats(st2);
     b.release(y2);
-  } else {
-    const int i = w.kv_index, Cp = (C + 127) / 128 * 128;
-    T pm = b.alloc(N, x.H, x.W, 128);  // probabilities [rows][8 heads x 16 (14 valid)]
-    if (!pm.p) return DTP_ERR_HIP;
-    GemmParams g = {};
-    g.A = y2.p; g.W = up.xW1[i]; g.C = pm.p;
-    g.M = S; g.N = 128; g.K = C; g.lda = y2.ld; g.ldw = C; g.ldc = pm.ld; g.nkb = C / 64;
-    g.bias = up.xb1[i]; g.lns = up.xl1[i]; g.ln_eps = 1e-5f;
-    g.flags = GF_BIAS | GF_LNFOLD | GF_SOFTMAX16; g.sm_valid = 14;
-    g.batch = N; g.a_bs = (long long)S * y2.ld; g.w_bs = (long long)128 * C; g.c_bs = (long long)S * pm.ld; g.bias_bs = 128; g.lns_bs = 128;
-    if (st2.buf && st2.parts > 0 && st2.M == N * S) { g.st_in = st2.buf; g.st_parts = st2.parts; g.st_rows = N * S; }
-    RC(push_gemm(b.c, b.prog, g, -1, (double)C, nullptr));
-    b.release_stats(st2);
-    RC(b.alloc_stats((long long)N * S, C, st3));
-    y3 = b.alloc(N, x.H, x.W, C);
-    if (!y3.p) return DTP_ERR_HIP;
-    GemmParams h = {};
-    h.A = pm.p; h.W = up.xW2[i]; h.C = y3.p;
-    h.M = S; h.N = C; h.K = 128; h.lda = pm.ld; h.ldw = 128; h.ldc = y3.ld; h.nkb = 2;
-    h.bias = w.out2.b; h.R = y2.p; h.ldr = y2.ld;
-    h.flags = (w.out2.b ? GF_BIAS : 0) | GF_RESID | (st3.buf ? GF_ROWSTATS : 0);
-    h.st_out = st3.buf; h.st_rows = N * S;
-    h.batch = N; h.a_bs = (long long)S * pm.ld; h.w_bs = (long long)Cp * 128; h.c_bs = (long long)S * y3.ld; h.r_bs = (long long)S * y2.ld;
-    RC(push_gemm(b.c, b.prog, h, -1, 128.0, st3.buf ? &st3 : nullptr));
-    b.release(pm); b.release(y2);
+    return DTP_OK;
   }
-  }  // !chained
-  {
-    // Round 6: at level 0 (C = 320) with enough rows to give every CU several 128-row workgroups (batched stamps), FF1 (GEGLU), FF2 and
-    // proj_out run as ONE register-chained launch (ffchain.hip): the [rows][1280] hidden tensor is never written.  At batch 1 its 96
-    // workgroups (one per CU, ~400 registers) tie the two launches they replace, so the gate is the row count; $DTP_FFCHAIN=0 / 1 forces it
-    // off / on (A/B).
-    static const int fc_env = [] { const char* e = getenv("DTP_FFCHAIN"); return e ? atoi(e) : -1; }();
-    const ConvW& wm = w.ff2_proj;
-    FfchainParams fc = {};
-    fc.X = y3.p; fc.ldx = y3.ld; fc.W1 = w.ff1.w; fc.ldw1 = w.ff1.ldw; fc.lns1 = w.ff1.lns; fc.b1 = w.ff1.b;
-    fc.Wm = wm.w; fc.ldwm = wm.ldw; fc.bm = wm.b; fc.R = xin.p; fc.ldr = xin.ld;
-    fc.M = N * S; fc.C = C; fc.ln_eps = 1e-5f;
-    fc.Out = y3.p; fc.ldo = C;  // (placeholder for the support check)
-    const bool want = fc_env >= 0 ? fc_env != 0 : (long long)N * S / 128 >= 2LL * b.c->num_cu;
-    if (want && !b.fp8 && wm.K == 5 * C && wm.cout == C && w.ff1.cout == 8 * C && w.ff1.K == C && w.ff1.lns && dtp_ffchain_supported(fc)) {
-      if (dst) {
-        if (dst->C != C || dst->rows() != (long long)N * S) { dtp_set_error("transformer: destination view mismatch"); return DTP_ERR_ARG; }
-        out = *dst;
-      } else {
-        out = b.alloc(N, x.H, x.W, C);
-        if (!out.p) return DTP_ERR_HIP;
-      }
-      fc.Out = out.p; fc.ldo = out.ld;
-      b.release_stats(st3);
-      b.push(PK_LNLIN, 2.0 * N * S * (8.0 * C * C + 5.0 * C * C), 2.0 * (3.0 * N * S * C + 13.0 * C * C),
-             [=](hipStream_t s, int) { return dtp_launch_ffchain(fc, s); }, "ffchain M=" + std::to_string(N * S) + " C=" + std::to_string(C));
-      b.release(y3);
-      return DTP_OK;
-    }
-  }
-  if (f8 && w.ff1.K >= DTP_FP8_OPERANDS_MIN_K && w.ff1.w8) {  // FF1 (C = 1280) on the LayerNorm-3'd e4m3 copy of y3
-    const T8 y3n = b.alloc8(y3, C, false, DTP_FP8_LN_A_SCALE);
-    RC(b.quant8(y3, y3n, true, &st3));
+  T pm = b.alloc(N, x.H, x.W, 128);  // probabilities [rows][8 heads x 16 (14 valid)]
+  if (!pm.p) return DTP_ERR_HIP;
+  GemmParams g = {};
+  g.A = y2.p; g.W = up.xW1[i]; g.C = pm.p;
+  g.M = S; g.N = 128; g.K = C; g.lda = y2.ld; g.ldw = C; g.ldc = pm.ld; g.nkb = C / 64;
+  g.bias = up.xb1[i]; g.lns = up.xl1[i]; g.ln_eps = 1e-5f;
+  g.flags = GF_BIAS | GF_LNFOLD | GF_SOFTMAX16; g.sm_valid = 14;
+  g.batch = N; g.a_bs = (long long)S * y2.ld; g.w_bs = (long long)128 * C; g.c_bs = (long long)S * pm.ld; g.bias_bs = 128; g.lns_bs = 128;
+  if (st2.buf && st2.parts > 0 && st2.M == N * S) { g.st_in = st2.buf; g.st_parts = st2.parts; g.st_rows = N * S; }
+  RC(push_gemm(b.c, b.prog, g, -1, (double)C, nullptr));
+  b.release_stats(st2);
+  RC(b.alloc_stats((long long)N * S, C, st3));
+  y3 = b.alloc(N, x.H, x.W, C);
+  if (!y3.p) return DTP_ERR_HIP;
+  GemmParams h = {};
+  h.A = pm.p; h.W = up.xW2[i]; h.C = y3.p;
+  h.M = S; h.N = C; h.K = 128; h.lda = pm.ld; h.ldw = 128; h.ldc = y3.ld; h.nkb = 2;
+  h.bias = w.out2.b; h.R = y2.p; h.ldr = y2.ld;
+  h.flags = (w.out2.b ? GF_BIAS : 0) | GF_RESID | (st3.buf ? GF_ROWSTATS : 0);
+  h.st_out = st3.buf; h.st_rows = N * S;
+  h.batch = N; h.a_bs = (long long)S * pm.ld; h.w_bs = (long long)Cp * 128; h.c_bs = (long long)S * y3.ld; h.r_bs = (long long)S * y2.ld;
+  RC(push_gemm(b.c, b.prog, h, -1, 128.0, st3.buf ? &st3 : nullptr));
+  b.release(pm); b.release(y2);
+  return DTP_OK;
+}
+
+// Stage 3: the feed-forward (LN3 folded, GEGLU), ff.net.2 and proj_out with their residuals -> out.  y3 and st3 go back to the pool.
+static int feed_forward(Builder& b, const XfW& w, const T& y3, RowStats& st3, const T& xin, T& out, const T* dst) {
+  const int C = y3.C, N = y3.B, S = y3.H * y3.W;
+  const ConvW& wm = w.ff2_proj;
+  // Round 6: at level 0 (C = 320) with enough rows to give every CU several 128-row workgroups (batched stamps), FF1 (GEGLU), FF2 and
+  // proj_out run as ONE register-chained launch (ffchain.hip): the [rows][1280] hidden tensor is never written.  At batch 1 its 96
+  // workgroups (one per CU, ~400 registers) tie the two launches they replace, so the gate is the row count; Ctx::ffchain forces it
+  // off / on (A/B).
+  FfchainParams fc = {};
+  fc.X = y3.p; fc.ldx = y3.ld; fc.W1 = w.ff1.w; fc.ldw1 = w.ff1.ldw; fc.lns1 = w.ff1.lns; fc.b1 = w.ff1.b;
+  fc.Wm = wm.w; fc.ldwm = wm.ldw; fc.bm = wm.b; fc.R = xin.p; fc.ldr = xin.ld;
+  fc.M = N * S; fc.C = C; fc.ln_eps = 1e-5f;
+  fc.Out = y3.p; fc.ldo = C;  // (placeholder for the support check)
+  const bool want = b.c->ffchain >= 0 ? b.c->ffchain != 0 : (long long)N * S / 128 >= 2LL * b.c->num_cu;
+  const bool chain = want && !b.fp8 && wm.K == 5 * C && wm.cout == C && w.ff1.cout == 8 * C && w.ff1.K == C && w.ff1.lns && dtp_ffchain_supported(fc);
+  if (chain) {
+    RC(block_out(b, dst, y3, out));
+    fc.Out = out.p; fc.ldo = out.ld;
     b.release_stats(st3);
-    RC(b.linear8(y3n, w.ff1, nullptr, GF_GEGLU, f, nullptr));
-    b.release8(y3n);
-  } else {
-    RC(b.linear(y3, w.ff1, nullptr, GF_GEGLU, f, nullptr, &st3));  // LN3 folded
-    b.release_stats(st3);
+    b.push(PK_LNLIN, 2.0 * N * S * (8.0 * C * C + 5.0 * C * C), 2.0 * (3.0 * N * S * C + 13.0 * C * C),
+           [=](hipStream_t s, int) { return dtp_launch_ffchain(fc, s); }, "ffchain M=" + std::to_string(N * S) + " C=" + std::to_string(C));
+    b.release(y3);
+    return DTP_OK;
   }
+  T f;
+  RC(b.linear_f8ops(y3, w.ff1, nullptr, GF_GEGLU, f, nullptr, &st3, true));  // LN3 folded (e4m3: st3 released before the GEMM)
   // (fp8_operands leaves the merged GEMM below in fp16 although its K is 1600 .. 6400: its A2 operand y3 is the residual stream, and
   // rounding THAT to e4m3 costs 2.6e-2 of pixel error on its own -- measured by emulation in the fp32 oracle)
   // ff.net.2 (+ y3) and proj_out (+ x) are two Linears with only a residual add between them: one GEMM over [f | y3]
   // with the merged weights [Wp W2 | Wp] (load_linear_pair) -- no y4 tensor, one launch fewer per block
-  {
-    const ConvW& wm = w.ff2_proj;
-    if (wm.K != f.C + y3.C || wm.cout != C) { dtp_set_error("transformer: merged ff2/proj_out weight mismatch"); return DTP_ERR_ARG; }
-    if (dst) {
-      if (dst->C != C || dst->rows() != (long long)N * S) { dtp_set_error("transformer: destination view mismatch"); return DTP_ERR_ARG; }
-      out = *dst;
-    } else {
-      out = b.alloc(N, x.H, x.W, C);
-      if (!out.p) return DTP_ERR_HIP;
+  if (wm.K != f.C + y3.C || wm.cout != C) { dtp_set_error("transformer: merged ff2/proj_out weight mismatch"); return DTP_ERR_ARG; }
+  RC(block_out(b, dst, y3, out));
+  GemmParams g = {};
+  g.A = f.p; g.lda = f.ld; g.A2 = y3.p; g.lda2 = y3.ld; g.Cin2 = y3.C;
+  g.W = wm.w; g.Wfr = wm.wfr; g.ldw = wm.ldw; g.nkb = wm.ldw / 64;
+  g.M = N * S; g.N = C; g.K = wm.K;
+  g.C = out.p; g.ldc = out.ld;
+  g.bias = wm.b; g.R = xin.p; g.ldr = xin.ld;
+  g.flags = GF_BIAS | GF_RESID;
+  if (b.fp8 && wm.w8) {
+    GemmParams q = g;
+    q.W8 = wm.w8; q.ldw8 = wm.ldw8; q.w_scale = wm.w8_scale; q.a_scale = DTP_FP8_LN_A_SCALE * 8.0f; q.splits = 1;
+    if (dtp_gemm_fp8_supported(q)) {  // [GEGLU output | residual stream]: un-normalised operands, calibrated scale (fp8_calibrate)
+      q.a_scale_host = fp8_new_linear_scale(b.c, &q.amax_slot1);
+      g = q;
     }
-    GemmParams g = {};
-    g.A = f.p; g.lda = f.ld; g.A2 = y3.p; g.lda2 = y3.ld; g.Cin2 = y3.C;
-    g.W = wm.w; g.Wfr = wm.wfr; g.ldw = wm.ldw; g.nkb = wm.ldw / 64;
-    g.M = N * S; g.N = C; g.K = wm.K;
-    g.C = out.p; g.ldc = out.ld;
-    g.bias = wm.b; g.R = xin.p; g.ldr = xin.ld;
-    g.flags = GF_BIAS | GF_RESID;
-    if (b.fp8 && wm.w8) {
-      GemmParams q = g;
-      q.W8 = wm.w8; q.ldw8 = wm.ldw8; q.w_scale = wm.w8_scale; q.a_scale = DTP_FP8_LN_A_SCALE * 8.0f; q.splits = 1;
-      if (dtp_gemm_fp8_supported(q)) {  // [GEGLU output | residual stream]: un-normalised operands, calibrated scale (fp8_calibrate)
-        q.a_scale_host = fp8_new_linear_scale(b.c, &q.amax_slot1);
-        g = q;
-      }
-    }
-    RC(push_gemm(b.c, b.prog, g, -1, (double)wm.K, nullptr));
-    b.release(f); b.release(y3);
   }
+  RC(push_gemm(b.c, b.prog, g, -1, (double)wm.K, nullptr));
+  b.release(f); b.release(y3);
   return DTP_OK;
+}
+
+static int transformer(Builder& b, const T& x, const XfW& w, const UNetProg& up, T& out, const T* dst = nullptr, const Dup* dup = nullptr) {
+  const T& xin = dup && dup->B > 0 ? dup->x_full : x;  // the block input for all N samples (residual of the last GEMM)
+  T y, a, y3; RowStats st3;
+  RC(self_attention(b, x, w, y, a));
+  RC(cross_attention(b, x, w, up, dup, a, y, y3, st3));
+  return feed_forward(b, w, y3, st3, xin, out, dst);
+}
+
+// the 16 transformer blocks in kv_index order (the order load_unet_weights numbers them)
+static std::vector<XfW*> xf_blocks(UNetW& u) {
+  std::vector<XfW*> all;
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j) all.push_back(&u.down_xf[i][j]);
+  all.push_back(&u.mid_xf);
+  for (int i = 1; i < 4; ++i) for (int j = 0; j < 3; ++j) all.push_back(&u.up_xf[i][j]);
+  return all;
 }
 
 int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
@@ -445,10 +432,7 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
   RC(ctx_persistent(c, (size_t)N * 14 * 768 * 2, &p, true)); up.ctx16 = (f16*)p;
   RC(ctx_persistent(c, (size_t)N * h * h * 4 * 4, &p, true)); up.out32 = (float*)p;
   // ---- cross-attention K/V of the 16 transformer blocks (depends only on the conditioning)
-  std::vector<const XfW*> xfs;
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j) xfs.push_back(&u.down_xf[i][j]);
-  xfs.push_back(&u.mid_xf);
-  for (int i = 1; i < 4; ++i) for (int j = 0; j < 3; ++j) xfs.push_back(&u.up_xf[i][j]);
+  const std::vector<XfW*> xfs = xf_blocks(c->unet);
   up.kvbuf.assign(xfs.size(), nullptr);
   up.xW1.assign(xfs.size(), nullptr); up.xW2.assign(xfs.size(), nullptr);
   up.xb1.assign(xfs.size(), nullptr); up.xl1.assign(xfs.size(), nullptr);
@@ -498,23 +482,13 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
   }
   // ---- main program
   if (c->fp8_linear) {  // e4m3 copies of the transformer Linears (once per context)
-    UNetW& uw = c->unet;
-    std::vector<XfW*> all;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j) all.push_back(&uw.down_xf[i][j]);
-    all.push_back(&uw.mid_xf);
-    for (int i = 1; i < 4; ++i) for (int j = 0; j < 3; ++j) all.push_back(&uw.up_xf[i][j]);
-    for (XfW* x : all)
+    for (XfW* x : xfs)
       for (ConvW* w : {&x->proj_in, &x->qkv, &x->out1, &x->ff1, &x->ff2_proj}) RC(ensure_w8(c, *w));
     // the quantise kernels run on the null stream, the program on the caller's (non-blocking) stream: order them once, here
     HIP_CHECK(hipDeviceSynchronize());
   }
   if (c->fp8_operands) {  // e4m3 copies of the Linears fp8_operands covers (transformer(): q/k/v, to_out, FF1 with K >= DTP_FP8_OPERANDS_MIN_K)
-    UNetW& uw = c->unet;
-    std::vector<XfW*> all;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j) all.push_back(&uw.down_xf[i][j]);
-    all.push_back(&uw.mid_xf);
-    for (int i = 1; i < 4; ++i) for (int j = 0; j < 3; ++j) all.push_back(&uw.up_xf[i][j]);
-    for (XfW* x : all)
+    for (XfW* x : xfs)
       for (ConvW* w : {&x->qkv, &x->out1, &x->ff1})
         if (w->K >= DTP_FP8_OPERANDS_MIN_K) RC(ensure_w8(c, *w));
     HIP_CHECK(hipDeviceSynchronize());  // (null-stream quantise kernels before the caller's stream, as above)

@@ -54,6 +54,37 @@ def test_unet_engine_vs_oracle(env, n, t):
     assert e < 1e-2
 
 
+def test_unet_register_chains_vs_oracle(monkeypatch, tmp_path):
+    """Both register-chained transformer launches in one engine-level evaluation, against the fp32 oracle.  At 256^2 level 0 has 1024
+    rows per sample: n = 8 gives 8 x 8 = 64 xchain workgroups, a quarter of the 256 CUs (its gate); ffchain is forced on by DTP_FFCHAIN,
+    which a context reads when it is created."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from diffusiontexturepainting_amd import weights as W
+    from diffusiontexturepainting_amd.inpainter import MI355ConditionalInpainter
+    from oracle import nets
+    monkeypatch.setenv("DTP_FFCHAIN", "1")
+    sd = dict(unet=W.synthetic_unet(1), lora=W.synthetic_lora(1), vae=W.synthetic_vae(1), clip=W.synthetic_clip(1),
+              penc=W.synthetic_patch_encoder(1))
+    model = MI355ConditionalInpainter(256, device=0, weights=sd, max_batch=3)
+    n, t, h = 8, 301.0, 256 // 8
+    g = torch.Generator().manual_seed(n)
+    sample = torch.randn(n, 9, h, h, generator=g)
+    ctx = torch.randn(n, 14, 768, generator=g).half()
+    model.profile(True)
+    got = model.unet(sample, t, ctx)
+    dump = tmp_path / "launches.csv"
+    model.profile_dump(dump)
+    model.profile(False)
+    labels = [ln.split(",", 4)[4] for ln in dump.read_text().splitlines()[1:]]
+    assert any(lb.startswith("xchain") for lb in labels)
+    assert any(lb.startswith("ffchain") for lb in labels)
+    ref = nets.unet_forward(nets.merge_lora(sd["unet"], sd["lora"]), sample, torch.tensor(t), ctx.float())
+    e = rel_err(got, ref)
+    print("unet (xchain + ffchain) rel err", e)
+    assert e < 1e-2
+
+
 def test_vae_encode_vs_oracle(env):
     from oracle import nets
     g = torch.Generator().manual_seed(5)
