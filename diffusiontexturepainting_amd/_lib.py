@@ -131,6 +131,9 @@ SYMBOLS = {
     "dtp_op_dilate_pads": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(_i), _vp]),
     "dtp_scheduler_tables": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_f)]),
     "dtp_op_sched_step": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "dtp_stamp_strength": (_i, [_vp, _vp, C.POINTER(Settings), _vp, _vp, _vp, C.c_double, _vp, _i, C.POINTER(_i), _vp]),
+    "dtp_strength_schedule": (_i, [_i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f)]),
+    "dtp_op_strength_init": (_i, [_vp, _vp, _f, _f, _vp, C.c_longlong, _vp]),
 }
 
 

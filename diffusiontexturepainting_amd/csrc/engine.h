@@ -204,6 +204,7 @@ struct VaeDecProg {
 
 struct StampBufs {  // per-batch persistent staging of dtp_stamp
   float *masks = nullptr, *ml = nullptr, *lat = nullptr, *eps = nullptr;
+  bool three = false;  // ml / eps hold three slabs (the init-image rows of a strength < 1 stamp), not two
 };
 struct IencBufs {  // brush-encoder program + buffers (built on the first dtp_set_brush)
   float* img224 = nullptr;
@@ -219,7 +220,7 @@ struct StampGraph {
   int nodes = 0;
   unsigned long long used = 0;  // Ctx::graph_clock at the last replay (LRU of the denoise-loop graphs)
 };
-// Captured denoise-loop graphs kept per context.  A loop graph is keyed by (B, steps, scheduler, the sorted per-stamp tg_evals profile), and
+// Captured denoise-loop graphs kept per context.  A loop graph is keyed by (B, steps, scheduler, start row, the sorted per-stamp tg_evals profile), and
 // batches of stamps with different guidance settings produce many profiles: the least recently replayed one is destroyed beyond this.
 constexpr int DTP_LOOP_GRAPH_CAP = 16;
 
@@ -231,8 +232,15 @@ struct StampCoefs {
   int order[DTP_STAMP_MAXB];  // the UNet's texture-guided row 2B + j belongs to stamp order[j] (stamps by descending tg_evals)
   int rank[DTP_STAMP_MAXB];   // inverse of order: stamp b owns tg row 2B + rank[b] while rank[b] < k (k = tg rows of the program)
 };
+// the start point of a strength < 1 stamp (dtp_stamp_strength): x = a z0 + b latents, then scale_model_input of row `row`
+struct StampStrength {
+  float a, b;
+  int row;  // start row in the schedule tables: t_start - steps_offset
+  int pad_;
+};
 struct StampParams {
   StampCoefs coef;
+  StampStrength strength;
   float sched[DTP_SCHED_ROW * 1000];  // per evaluation: the scheduler's coefficient row (dtp_scheduler_tables, include/dtp.h)
   float in_scale[1001];               // per evaluation: scale_model_input of the latent channels (entry E: 1)
   float init_sigma;                   // init_noise_sigma: the initial latent is latents * init_sigma

@@ -38,7 +38,7 @@ struct RoctxRange {
 int get_unet_prog(Ctx* c, int N, int dupB, UNetProg** out);
 int get_enc_prog(Ctx* c, int B, VaeEncProg** out);
 int get_dec_prog(Ctx* c, int B, VaeDecProg** out);
-int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s);
+int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s, const float* eps3, int n_eps);
 int launch_post_quant(Ctx* c, const float* z, int nhwc, float in_scale, f16* out, int B, hipStream_t s);
 int load_imgenc_weights(Ctx* c);
 void dtp_gemm_init();
@@ -198,6 +198,39 @@ extern "C" int dtp_scheduler_tables(int scheduler, int steps, int* evals, float*
   return DTP_OK;
 }
 
+// initialize_timesteps (stable_diffusion_pipeline.py:348-355) in double, as Python evaluates it, and the add_noise pair of the sampler at
+// t_start (utilities.py:363-366 LMSD, :524-529 DDIM on the gathered table, :1000-1008 DPM on the full table at timesteps[t_start]).
+extern "C" int dtp_strength_schedule(int scheduler, int steps, double strength, int* t_start, int* evals, float* noise_coefs) {
+  if (!(strength > 0.0 && strength <= 1.0)) {  // (NaN fails both)
+    dtp_set_error("strength schedule: strength %g outside (0, 1]", strength);
+    return DTP_ERR_ARG;
+  }
+  const int E_full = (scheduler == DTP_SCHED_DDIM || scheduler == DTP_SCHED_DPM || scheduler == DTP_SCHED_LMSD) ? sched_evals(scheduler, steps) : 0;
+  std::vector<float> k((size_t)std::max(E_full, 1) * DTP_SCHED_ROW);
+  int ne;
+  float sig0;
+  RC(dtp_scheduler_tables(scheduler, steps, &ne, &sig0, nullptr, nullptr, k.data()));  // (its checks: scheduler, steps)
+  const int offset = scheduler == DTP_SCHED_DDIM ? 1 : 0;  // steps_offset (utilities.py:379, :274, :664)
+  const int init = std::min((int)((double)steps * strength) + offset, steps);
+  const int ts = std::max(steps - init + offset, 0);
+  const int E = steps - ts;
+  if (E < 1) {
+    dtp_set_error("strength schedule: strength %g leaves no evaluation at %d steps (int(steps * strength) = 0)", strength, steps);
+    return DTP_ERR_ARG;
+  }
+  float a = 0.0f, b = sig0;  // strength 1: latents * init_noise_sigma
+  if (strength < 1.0) {
+    const float* r = &k[(size_t)DTP_SCHED_ROW * (ts - offset)];
+    if (scheduler == DTP_SCHED_DDIM) { a = r[1]; b = r[0]; }        // sqrt(a_t), sqrt(1 - a_t) of the gathered alphas_cumprod[t_start]
+    else if (scheduler == DTP_SCHED_DPM) { a = r[0]; b = r[1]; }    // alpha_s, sigma_s at timesteps[t_start]
+    else { a = 1.0f; b = r[0]; }                                     // z0 + sigma[t_start] eps
+  }
+  if (t_start) *t_start = ts;
+  if (evals) *evals = E;
+  if (noise_coefs) { noise_coefs[0] = a; noise_coefs[1] = b; }
+  return DTP_OK;
+}
+
 // ---------------------------------------------------------------- kernels
 namespace {
 
@@ -232,9 +265,10 @@ __global__ void dilate_col_kernel(const float* __restrict__ tmp, float* __restri
 }
 
 // trt_model.py:103-109 + handler.py:25-33: canvas -> VAE-encoder inputs (NHWC f16, 8 channels,
-// batch [masked x B | context x B]) and the two latent-resolution masks (nearest, 1 = paint).
+// batch [masked x B | context x B]) and the two latent-resolution masks (nearest, 1 = paint).  `init` (strength < 1): a third slab
+// [canvas x B] holds the unmasked canvas RGB * 2 - 1, the init image whose latents the stamp starts from.
 __global__ void prep_kernel(const float* __restrict__ canvas, const float* __restrict__ brush_slots, const int* __restrict__ slot_map,
-                            const float* __restrict__ dil, f16* __restrict__ enc_in, float* __restrict__ masks, int B, int R) {
+                            const float* __restrict__ dil, f16* __restrict__ enc_in, float* __restrict__ masks, int B, int R, int init) {
   const int HW = R * R, h = R / 8;
   const long long total = (long long)B * HW;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -243,7 +277,7 @@ __global__ void prep_kernel(const float* __restrict__ canvas, const float* __res
     const float* brush = brush_slots + (size_t)slot_map[b] * 3 * HW;  // this stamp's brush (hint image source)
     const float a = cb[3 * HW + pix];
     const float hint = 1.0f - dil[i];
-    f16x8 m8, c8;
+    f16x8 m8, c8, i8;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const float img = cb[ch * HW + pix] * 2.0f - 1.0f;
@@ -251,11 +285,13 @@ __global__ void prep_kernel(const float* __restrict__ canvas, const float* __res
       const float src = brush[ch * HW + pix] * 2.0f - 1.0f;
       m8[ch] = (f16)masked;
       c8[ch] = (f16)(masked + src * hint);
+      i8[ch] = (f16)img;
     }
 #pragma unroll
-    for (int ch = 3; ch < 8; ++ch) m8[ch] = c8[ch] = (f16)0.f;
+    for (int ch = 3; ch < 8; ++ch) m8[ch] = c8[ch] = i8[ch] = (f16)0.f;
     *(f16x8*)(enc_in + i * 8) = m8;
     *(f16x8*)(enc_in + ((size_t)B * HW + i) * 8) = c8;
+    if (init) *(f16x8*)(enc_in + ((size_t)2 * B * HW + i) * 8) = i8;
     const int y = pix / R, x = pix - y * R;
     if ((y & 7) == 0 && (x & 7) == 0) {  // F.interpolate(size=(h,w)) default 'nearest': src = dst * 8
       const size_t o = (size_t)b * h * h + (size_t)(y >> 3) * h + (x >> 3);
@@ -265,22 +301,34 @@ __global__ void prep_kernel(const float* __restrict__ canvas, const float* __res
   }
 }
 
+// scheduler.add_noise(z0, eps, t_start, timesteps[t_start]) of every sampler as x = a z0 + b eps (utilities.py:363-366, :524-529,
+// :1000-1008): both products rounded to fp32 before the sum, as torch evaluates them
+__device__ __forceinline__ float strength_init_value(float a, float b, float z0, float e) {
+  float p = a * z0, q = b * e;
+  asm volatile("" : "+v"(p));
+  asm volatile("" : "+v"(q));
+  return p + q;
+}
+
 // UNet input assembly (inpaint_pipeline.py:116,136; sdp:423-427): branch-major [uncond x B | cond x B | tg x k]; stamp b has the
 // texture-guided row 2B + rank[b] while rank[b] < k (StampCoefs).  At stage 0 (lat_nchw set) the running latent starts as
-// latents * init_noise_sigma (sdp:345); the latent channels of the input are scaled by scale_model_input of evaluation `eval_index`
-// (sdp:424; the mask and masked-latent channels are concatenated after scaling, :426-427).
-__global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float* __restrict__ masks,
+// latents * init_noise_sigma (sdp:345), or, with the init-image latents z0 (strength < 1), as add_noise(z0, latents) with the pair
+// and start row of params->strength; the latent channels of the input are scaled by scale_model_input of evaluation `eval_index`
+// (with z0: of the start row; sdp:424; the mask and masked-latent channels are concatenated after scaling, :426-427).
+__global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float* __restrict__ z0, const float* __restrict__ masks,
                                 const float* __restrict__ ml, const int* __restrict__ rank, f16* __restrict__ in16,
                                 float* __restrict__ x32, const StampParams* __restrict__ params, int eval_index, int B, int HWl, int k) {
   const long long total = (long long)B * HWl;
-  const float sig0 = params->init_sigma, scale = params->in_scale[eval_index];
+  const float sig0 = params->init_sigma, scale = params->in_scale[z0 ? params->strength.row : eval_index];
+  const float na = params->strength.a, nb = params->strength.b;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int b = (int)(i / HWl), p = (int)(i - (long long)b * HWl);
     float x[4];
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch) {
       if (lat_nchw) {
-        x[ch] = lat_nchw[((size_t)b * 4 + ch) * HWl + p] * sig0;
+        const size_t o = ((size_t)b * 4 + ch) * HWl + p;
+        x[ch] = z0 ? strength_init_value(na, nb, z0[o], lat_nchw[o]) : lat_nchw[o] * sig0;
         x32[i * 4 + ch] = x[ch];
       } else {
         x[ch] = x32[i * 4 + ch];  // mid-loop switch to a program with fewer tg rows: keep the running latent
@@ -313,7 +361,8 @@ __global__ void assemble_kernel(const float* __restrict__ lat_nchw, const float*
 // guidance combine + one sampler update + refresh of the latent channels of the UNet input (sdp:419-420,449-455).  Stamp b uses its
 // own cfg / tg; its texture-guided branch is row 2B + rank[b] of a program with k tg rows, present while rank[b] < k, i.e. while
 // step_index < its tg_evals (the stamps are ordered by descending tg_evals).  `kc`: this evaluation's coefficient row
-// (dtp_scheduler_tables); `hist`: [3][B][HWl][4] sampler history.  One instantiation per sampler:
+// (dtp_scheduler_tables); `hist`: [3][B][HWl][4] sampler history; `step_index`: the evaluation's index within the stamp's loop (0 =
+// its first evaluation).  One instantiation per sampler:
 //   DDIM  eta = 0 step (utilities.py:463-503)
 //   DPM   DPM-Solver++ first order / multistep second order, midpoint (utilities.py:838-852,873-880,888-931,953-994)
 //   LMSD  linear multistep in sigma space (utilities.py:345-362)
@@ -342,7 +391,9 @@ __global__ void step_kernel(const float* __restrict__ eps_out, float* __restrict
     } else if constexpr (S == DTP_SCHED_DPM) {
       const float m0 = (x - kc[1] * e) / kc[0];  // convert_model_output: the data prediction x0
       xn = kc[3] * x - kc[4] * m0;
-      if (kc[2] > 1.5f) xn = xn - kc[5] * (kc[6] * (m0 - hist[i]));  // second order: D1 = (1 / r0) (m0 - m_prev)
+      // second order: D1 = (1 / r0) (m0 - m_prev).  The first evaluation of a stamp is first order whatever its row says: a stamp
+      // that starts at row t_start > 0 (strength < 1) has no previous x0 (lower_order_nums restarts at 0, utilities.py:805,979)
+      if (kc[2] > 1.5f && step_index > 0) xn = xn - kc[5] * (kc[6] * (m0 - hist[i]));
       hist[i] = m0;
     } else {
       const float sigma = kc[0];
@@ -414,6 +465,18 @@ __global__ void set_header_kernel(StampCoefs* __restrict__ dst, StampCoefs a) {
   for (int t = threadIdx.x; t < words; t += blockDim.x) ((int*)dst)[t] = ((const int*)&a)[t];
 }
 
+// the strength < 1 start point (add_noise pair, start row) into the parameter block, as set_header_kernel writes the header
+__global__ void set_strength_kernel(StampStrength* __restrict__ dst, StampStrength a) {
+  if (threadIdx.x == 0) *dst = a;
+}
+
+// dtp_op_strength_init: the stage-0 combine of assemble_kernel on its own, elementwise over n values
+__global__ void strength_init_kernel(const float* __restrict__ z0, const float* __restrict__ eps, float a, float b, float* __restrict__ x,
+                                     long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    x[i] = strength_init_value(a, b, z0[i], eps[i]);
+}
+
 // post-loop finiteness guard (the reference asserts `not isnan` after every step, stable_diffusion_pipeline.py:415, at the
 // price of a host sync per step; here ONE pass over the final latents and the decoded image, debug option "check_finite")
 __global__ void finite_check_kernel(const float* __restrict__ a, long long na, const float* __restrict__ b, long long nb,
@@ -466,6 +529,24 @@ static int get_bufs(Ctx* c, int B, StampBufs** out) {
 static void destroy_graph(StampGraph& g) {
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (g.graph) (void)hipGraphDestroy(g.graph);
+}
+
+// the first strength < 1 stamp of batch B: masked latents and VAE draws get a third slab (the init image).  The captured stages of B
+// hold the two-slab buffers: they are dropped (a one-time wait, like building the 3B encoder program) and recaptured on the new ones,
+// which every later stamp of B, strength 1 or not, uses.
+static int grow_bufs_three(Ctx* c, int B, StampBufs* sb) {
+  if (sb->three) return DTP_OK;
+  HIP_CHECK(hipDeviceSynchronize());  // a captured stage may still be replaying on the old buffers
+  for (auto g = c->graphs.begin(); g != c->graphs.end();) {
+    if (((g->first[0] >> 32) & 0xff) == B) { destroy_graph(g->second); g = c->graphs.erase(g); }
+    else ++g;
+  }
+  void* p;
+  const size_t hw = (size_t)c->h * c->h;
+  RC(ctx_persistent(c, 3 * B * 4 * hw * 4, &p, true)); sb->ml = (float*)p;
+  RC(ctx_persistent(c, 3 * B * 4 * hw * 4, &p, true)); sb->eps = (float*)p;
+  sb->three = true;
+  return DTP_OK;
 }
 
 // run `body` on stream s, replaying a captured hipGraph when possible.  `loop`: a denoise-loop graph, of which the context keeps the
@@ -554,6 +635,12 @@ int dtp_op_sched_step(int scheduler, const float* eps_out, float* x, float* hist
   return launch_step(scheduler, eps_out, x, (f16*)in16, hist, row, next_scale, cfg, tg, rank, step_index, B, hw, k, (hipStream_t)s);
 }
 
+int dtp_op_strength_init(const float* z0, const float* eps, float a, float b, float* x, long long n, dtp_stream s) {
+  if (!z0 || !eps || !x || n < 1) { dtp_set_error("dtp_op_strength_init: bad argument (n=%lld)", n); return DTP_ERR_ARG; }
+  hipLaunchKernelGGL(strength_init_kernel, dim3(nblk(n)), dim3(256), 0, (hipStream_t)s, z0, eps, a, b, x, n);
+  return LAUNCH_OK();
+}
+
 int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s) {
   if (!canvas || !tmp || !out || B < 1 || R < 1 || pad < 1) { dtp_set_error("dtp_op_dilate: bad argument"); return DTP_ERR_ARG; }
   const std::vector<int> pads(DTP_STAMP_MAXB, pad);
@@ -637,8 +724,48 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   return dtp_stamp_mixed(ctx, canvas, each, latents, vae_eps, out, B, slots, s);
 }
 
+// a strength < 1 stamp (dtp_stamp_strength): its loop runs rows [row, row + evals) of the (scheduler, steps) tables from the init image
+struct StrengthPlan {
+  int row, evals;
+  float a, b;
+  const float* init_eps;
+};
+
+static int stamp_run(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                     void* out, int B, const int* slots, dtp_stream s_, const StrengthPlan* sp);
+
 int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
-                    void* out, int B, const int* slots, dtp_stream s_) {
+                    void* out, int B, const int* slots, dtp_stream s) {
+  return stamp_run(ctx, canvas, st, latents, vae_eps, out, B, slots, s, nullptr);
+}
+
+int dtp_stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                       const float* init_eps, double strength, void* out, int B, const int* slots, dtp_stream s) {
+  Ctx* c = (Ctx*)ctx;
+  if (!(strength > 0.0 && strength <= 1.0)) { dtp_set_error("dtp_stamp_strength: strength %g outside (0, 1]", strength); return DTP_ERR_ARG; }
+  if (strength == 1.0) return dtp_stamp_mixed(ctx, canvas, st, latents, vae_eps, out, B, slots, s);  // today's path, init_eps unused
+  if (!c || !c->finalized) { dtp_set_error("dtp_stamp: weights not finalized"); return DTP_ERR_STATE; }
+  if (!st || B < 1 || B > c->maxB) { dtp_set_error("dtp_stamp: bad argument (B=%d, max %d)", B, c->maxB); return DTP_ERR_ARG; }
+  if (c->fp8_linear || c->fp8_attention || c->fp8_operands) {
+    dtp_set_error("dtp_stamp_strength: strength < 1 is not offered under the fp8 options (parity-only, calibrated per program)");
+    return DTP_ERR_STATE;
+  }
+  const int sched = c->scheduler;
+  StrengthPlan sp;
+  int t_start;
+  float ab[2];
+  if (st[0].steps < 2 || st[0].steps > 999) { dtp_set_error("dtp_stamp: steps=%d of stamp 0 outside 2..999", st[0].steps); return DTP_ERR_ARG; }
+  const int rc = dtp_strength_schedule(sched, st[0].steps, strength, &t_start, &sp.evals, ab);
+  if (rc) { dtp_set_error("dtp_stamp_strength: strength %g leaves no evaluation at %d steps", strength, st[0].steps); return rc; }
+  sp.row = t_start - (sched == DTP_SCHED_DDIM ? 1 : 0);
+  sp.a = ab[0];
+  sp.b = ab[1];
+  sp.init_eps = init_eps;
+  return stamp_run(ctx, canvas, st, latents, vae_eps, out, B, slots, s, &sp);
+}
+
+static int stamp_run(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                     void* out, int B, const int* slots, dtp_stream s_, const StrengthPlan* sp) {
   Ctx* c = (Ctx*)ctx;
   hipStream_t s = (hipStream_t)s_;
   if (!c || !c->finalized) { dtp_set_error("dtp_stamp: weights not finalized"); return DTP_ERR_STATE; }
@@ -660,7 +787,9 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     }
   }
   const int R = c->R, h = c->h, HW = R * R, HWl = h * h;
-  const int steps = st[0].steps, sched = c->scheduler, E = sched_evals(sched, steps);
+  const int steps = st[0].steps, sched = c->scheduler, E_full = sched_evals(sched, steps);
+  // strength < 1: the loop runs rows [row0, row0 + E) of the tables (the reference index t_start + i, minus steps_offset)
+  const int row0 = sp ? sp->row : 0, E = sp ? sp->evals : E_full;
   // Per stamp: the third (texture-guided) branch contributes nothing once its coefficient is 0: skip it (bit-identical).  The stamps are
   // ordered by descending tg_evals (a stable order: a uniform batch keeps the identity), and evaluation i runs the UNet on
   // [uncond x B | cond x B | tg x k_i] with k_i = #{b : tg_evals_b > i}: finished stamps leave the batch.
@@ -673,7 +802,8 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     coef.order[b] = b;
   }
   std::stable_sort(coef.order, coef.order + B, [&](int x, int y) { return tg_evals[x] > tg_evals[y]; });
-  std::vector<long long> loop_key = {((long long)B << 32) | ((long long)sched << 40) | ((long long)steps << 12) | (2LL << 60)};
+  std::vector<long long> loop_key = {((long long)B << 32) | ((long long)sched << 40) | ((long long)steps << 12) | ((long long)row0 << 44) |
+                                     (2LL << 60)};
   for (int j = 0; j < B; ++j) { coef.rank[coef.order[j]] = j; loop_key.push_back(tg_evals[coef.order[j]]); }
   std::vector<int> ks(E);  // k_i
   for (int i = 0; i < E; ++i) {
@@ -696,14 +826,15 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   // branches 0 (uncond) and 1 (cond) see identical samples: the programs evaluate the UNet prefix once for both (unet.hip, struct Dup)
   for (int i = 0; i < E; ++i)
     if (!prog[ks[i]]) RC(get_unet_prog(c, 2 * B + ks[i], B, &prog[ks[i]]));
-  RC(get_enc_prog(c, 2 * B, &enc));
+  RC(get_enc_prog(c, (sp ? 3 : 2) * B, &enc));  // strength < 1: the init image's rows join the one batched encode
   RC(get_dec_prog(c, B, &dec));
   RC(get_bufs(c, B, &sb));
+  if (sp) RC(grow_bufs_three(c, B, sb));
 
   // ---- schedule tables (update_infer_settings, inpaint_pipeline.py:39-50): rebuilt when the step count or the scheduler changes
   if (c->sched_steps != steps || c->sched_kind != sched) {  // rare (a settings change): the only host-blocking part of dtp_stamp
     HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<float> ts(E), sc(E + 1), k((size_t)DTP_SCHED_ROW * E);
+    std::vector<float> ts(E_full), sc(E_full + 1), k((size_t)DTP_SCHED_ROW * E_full);
     int ne;
     float sig0;
     RC(dtp_scheduler_tables(sched, steps, &ne, &sig0, ts.data(), sc.data(), k.data()));
@@ -716,6 +847,7 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   }
   hipLaunchKernelGGL(set_header_kernel, dim3(1), dim3(256), 0, s, &c->stamp_params->coef, coef);
   hipLaunchKernelGGL(set_slots_kernel, dim3(1), dim3(64), 0, s, c->slot_map, sa, B);
+  if (sp) hipLaunchKernelGGL(set_strength_kernel, dim3(1), dim3(64), 0, s, &c->stamp_params->strength, StampStrength{sp->a, sp->b, row0, 0});
 
   // ---- cross-attention K/V for the current brushes
   for (int k = 0; k <= B; ++k) {
@@ -749,6 +881,9 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
   RoctxRange r0("dtp_stamp: pre-processing + vae_encoder x2");
   HIP_CHECK(hipMemcpyAsync(sb->lat, latents, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
   if (vae_eps) HIP_CHECK(hipMemcpyAsync(sb->eps, vae_eps, (size_t)2 * B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
+  const float* init_eps = sp ? sp->init_eps : nullptr;
+  float* eps3 = sb->eps + (size_t)2 * B * 4 * HWl;  // (third slab: only with sp)
+  if (init_eps) HIP_CHECK(hipMemcpyAsync(eps3, init_eps, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(c->canvas32, canvas, (size_t)B * 4 * HW * 4, hipMemcpyDeviceToDevice, s));
   int pads[DTP_STAMP_MAXB];
   for (int b = 0; b < B; ++b) pads[b] = st[b].context_pad;
@@ -758,13 +893,17 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
                      c->alpha_tmp + (size_t)c->maxB * HW, B, R, pa);
   const int k0 = ks[0];
   UNetProg* first = prog[k0];
-  RC(run_stage(c, {((long long)B << 32) | ((long long)k0 << 4) | (vae_eps ? 2 : 0) | (k0 > 0 ? 1 : 0) | (1LL << 60)}, false, s,
+  // keyed by "init image on/off" (and its draw), not by the strength: the add_noise pair and start row are read from the parameter block
+  const long long init_bits = sp ? ((1LL << 20) | (init_eps ? 1LL << 21 : 0)) : 0;
+  RC(run_stage(c, {((long long)B << 32) | ((long long)k0 << 4) | (vae_eps ? 2 : 0) | (k0 > 0 ? 1 : 0) | init_bits | (1LL << 60)}, false, s,
                [&](hipStream_t q) -> int {
     hipLaunchKernelGGL(prep_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, q, c->canvas32, c->brush32, c->slot_map,
-                       c->alpha_tmp + (size_t)c->maxB * HW, enc->in8, sb->masks, B, R);
+                       c->alpha_tmp + (size_t)c->maxB * HW, enc->in8, sb->masks, B, R, sp ? 1 : 0);
     RC(enc->main.run(q, 0));
-    RC(launch_vae_sample(c, enc->moments, vae_eps ? sb->eps : nullptr, sb->ml, 2 * B, VAE_SCALE, q));
-    hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, sb->lat, sb->masks, sb->ml, rank, first->in16,
+    RC(launch_vae_sample(c, enc->moments, vae_eps ? sb->eps : nullptr, sb->ml, (sp ? 3 : 2) * B, VAE_SCALE, q, init_eps ? eps3 : nullptr,
+                         2 * B));
+    const float* z0 = sp ? sb->ml + (size_t)2 * B * 4 * HWl : nullptr;  // 0.18215 * sample(VAE_enc(canvas)): the init-image latents
+    hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, sb->lat, z0, sb->masks, sb->ml, rank, first->in16,
                        c->x32, c->stamp_params, 0, B, HWl, k0);
     return LAUNCH_OK();
   }));
@@ -777,8 +916,8 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
     if (u3 && !u3->fp8_calibrated) RC(fp8_calibrate(c, u3, s, 0));
     if (u2 && !u2->fp8_calibrated) {
       if (ks[0] > 0)  // (u2 is not the first program:) its input is normally assembled where the loop switches programs: do it now, from the initial latents
-        hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, s, (const float*)nullptr, sb->masks, sb->ml, rank,
-                           u2->in16, c->x32, c->stamp_params, 0, B, HWl, 0);
+        hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, s, (const float*)nullptr, (const float*)nullptr,
+                           sb->masks, sb->ml, rank, u2->in16, c->x32, c->stamp_params, 0, B, HWl, 0);
       RC(fp8_calibrate(c, u2, s, 0));
     }
   }
@@ -790,13 +929,14 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
       UNetProg* up = prog[ks[i]];
       if (i > 0 && ks[i] != ks[i - 1]) {
         // switching to a program with fewer tg rows: its input needs mask/masked-latent channels + current x
-        hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, (const float*)nullptr, sb->masks,
-                           sb->ml, rank, up->in16, c->x32, c->stamp_params, i, B, HWl, ks[i]);
+        hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, (const float*)nullptr, (const float*)nullptr,
+                           sb->masks, sb->ml, rank, up->in16, c->x32, c->stamp_params, row0 + i, B, HWl, ks[i]);
       }
-      RC(up->main.run(q, i));
-      StampParams* sp = c->stamp_params;
-      RC(launch_step(sched, up->out32, c->x32, up->in16, c->hist32, sp->sched + DTP_SCHED_ROW * i, sp->in_scale + i + 1, sp->coef.cfg,
-                     sp->coef.tg, sp->coef.rank, i, B, HWl, ks[i], q));
+      const int r = row0 + i;  // the table row (temb, in_scale, sched) of loop index i
+      RC(up->main.run(q, r));
+      StampParams* pb = c->stamp_params;
+      RC(launch_step(sched, up->out32, c->x32, up->in16, c->hist32, pb->sched + DTP_SCHED_ROW * r, pb->in_scale + r + 1, pb->coef.cfg,
+                     pb->coef.tg, pb->coef.rank, i, B, HWl, ks[i], q));
     }
     return LAUNCH_OK();
   }));

@@ -220,8 +220,10 @@ int build_vae_dec_prog(Ctx* c, int B, VaeDecProg& pr) {
 
 // moments [B][hw][8] (conv_out) -> quant_conv (8x8) -> mean/logvar -> latent NCHW f32 [B][4][hw] * scale
 // (DiagonalGaussianDistribution.sample with the normal draw as an input; logvar clamped to [-30, 20])
+// (the rows b >= n_eps draw from eps3 instead: the init-image rows of a strength < 1 stamp, eps3 indexed from its own row 0)
 __global__ void vae_sample_kernel(const float* __restrict__ mom, const float* __restrict__ qw, const float* __restrict__ qb,
-                                  const float* __restrict__ eps, float* __restrict__ out, int B, int HW, float scale) {
+                                  const float* __restrict__ eps, int n_eps, const float* __restrict__ eps3, float* __restrict__ out, int B,
+                                  int HW, float scale) {
   const long long total = (long long)B * HW;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int b = (int)(i / HW), hw = (int)(i - (long long)b * HW);
@@ -235,16 +237,21 @@ __global__ void vae_sample_kernel(const float* __restrict__ mom, const float* __
       for (int k = 0; k < 8; ++k) { mean += qw[ch * 8 + k] * m[k]; lv += qw[(4 + ch) * 8 + k] * m[k]; }
       lv = fminf(fmaxf(lv, -30.f), 20.f);
       const size_t o = ((size_t)b * 4 + ch) * HW + hw;
-      const float e = eps ? eps[o] : 0.f;
+      const float* es = b < n_eps ? eps : eps3;
+      const size_t eo = b < n_eps ? o : o - (size_t)n_eps * 4 * HW;
+      const float e = es ? es[eo] : 0.f;
       out[o] = (mean + expf(0.5f * lv) * e) * scale;
     }
   }
 }
 
-int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s) {
+int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s, const float* eps3 = nullptr,
+                      int n_eps = -1) {
   const int HW = c->h * c->h;
   const int blocks = std::min((B * HW + 255) / 256, 2048);
-  hipLaunchKernelGGL(vae_sample_kernel, dim3(blocks), dim3(256), 0, s, mom, c->vae.quant_w, c->vae.quant_b, eps, out, B, HW, scale);
+  if (n_eps < 0) n_eps = B;
+  hipLaunchKernelGGL(vae_sample_kernel, dim3(blocks), dim3(256), 0, s, mom, c->vae.quant_w, c->vae.quant_b, eps, n_eps, eps3, out, B, HW,
+                     scale);
   return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
 }
 

@@ -19,6 +19,18 @@ from .model_base import ConditionalInpainterBase
 DEFAULT_SETTINGS = dict(steps=20, context_pad=150, tg_steps=20, cfg_weight=2.0, tg_weight=1.0)  # Kit defaults, manager.py:104-110
 
 
+def check_strength_args(strength, init_eps, B, h):
+    """The `strength` / `init_eps` arguments of the generate calls: strength in (0, 1] (ValueError otherwise, NaN included); below 1,
+    init_eps None, False or one [B,4,h,h] draw per stamp (at 1 it is ignored, as dtp_stamp_strength ignores it).  Returns strength as a
+    float."""
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:  # (NaN fails too)
+        raise ValueError(f"strength must be in (0, 1], got {strength}")
+    if strength < 1.0 and init_eps is not None and init_eps is not False and tuple(init_eps.shape) != (B, 4, h, h):
+        raise ValueError(f"init_eps must be {B} x 4 x {h} x {h} (one draw per stamp), got {tuple(init_eps.shape)}")
+    return strength
+
+
 class MI355ConditionalInpainter(ConditionalInpainterBase):
     def __init__(self, resolution, device=0, weights="synthetic", max_batch=1, seed=42, use_graph=True, fp8_attention=None, fp8_linear=None,
                  fp8_operands=None, scheduler="DDIM"):
@@ -154,7 +166,8 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             self.image = img.unsqueeze(0)
             self.conditioning = (ce.unsqueeze(0), ue.unsqueeze(0))
 
-    def _stamp(self, canvas, settings, composite, latents=None, vae_eps=None, output_u8=False, slots=None, per_stamp=None):
+    def _stamp(self, canvas, settings, composite, latents=None, vae_eps=None, output_u8=False, slots=None, per_stamp=None, strength=1.0,
+               init_eps=None):
         if not self._slots:
             raise _lib.DtpError("no brush set: call set_brush() first")
         R, h = self._resolution, self._resolution // 8
@@ -162,6 +175,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         B = canvas.shape[0]
         if canvas.shape != (B, 4, R, R):
             raise ValueError(f"canvas must be B x 4 x {R} x {R}, got {tuple(canvas.shape)}")
+        strength = check_strength_args(strength, init_eps, B, h)
         s = {**DEFAULT_SETTINGS, **{k: v for k, v in settings.items() if k in DEFAULT_SETTINGS}}
         st = Settings(int(s["steps"]), int(s["context_pad"]), int(s["tg_steps"]), float(s["cfg_weight"]), float(s["tg_weight"]),
                       int(composite), int(output_u8))  # numpy scalars are cast here (server_io.py:104-119)
@@ -175,14 +189,22 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             latents = torch.randn((B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
         if vae_eps is None:
             vae_eps = torch.randn((2, B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
+        if strength < 1.0 and init_eps is None:  # the third draw, after the two of today's path
+            init_eps = torch.randn((B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
         latents = latents.to(self._device, torch.float32).contiguous()
         vae_eps = vae_eps.to(self._device, torch.float32).contiguous() if vae_eps is not False else None
+        init_eps = init_eps.to(self._device, torch.float32).contiguous() if strength < 1.0 and init_eps is not False else None
         out = (torch.empty(B, R, R, 3, dtype=torch.uint8, device=self._device) if output_u8
                else torch.empty(B, 3, R, R, dtype=torch.float32, device=self._device))
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
         if slots is not None and len(slots) != B:
             raise ValueError(f"{len(slots)} slots for {B} stamps")
-        if per_stamp is not None:
+        if strength < 1.0:  # strength is per call: one settings array (per_stamp's, or `settings` for every stamp)
+            each = st if per_stamp is not None else (Settings * B)(*([st] * B))
+            arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
+            check(self._lib.dtp_stamp_strength(self._h, ptr(canvas), each, ptr(latents), ptr(vae_eps), ptr(init_eps), C.c_double(strength),
+                                               ptr(out), B, arr, self._s()), "dtp_stamp_strength")
+        elif per_stamp is not None:
             arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
             check(self._lib.dtp_stamp_mixed(self._h, ptr(canvas), st, ptr(latents), ptr(vae_eps), ptr(out), B, arr, self._s()),
                   "dtp_stamp_mixed")
@@ -194,28 +216,36 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
                   "dtp_stamp_slots")
         torch.cuda.current_stream(self._device).wait_stream(self.stream)
         # keep the inputs alive until the stream has consumed them
-        for t in (canvas, latents, vae_eps, out):
+        for t in (canvas, latents, vae_eps, init_eps, out):
             if t is not None:
                 t.record_stream(self.stream)
         if self._check_finite and not self.last_stamp_finite():  # debug option: one sync per stamp, like the reference's assert
             raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
         return out
 
-    def generate_raw(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, **settings):
+    def generate_raw(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, strength=1.0, init_eps=None, **settings):
         """canvas B x 4 x R x R 0..1 -> B x 3 x R x R 0..1 (trt_model.py:90-121).  `latents`
         ([B,4,h,w]) / `vae_eps` ([2,B,4,h,w]; False = use the latent mean) override the internal
         generator -- the parity tests feed CPU-generated noise through them.  `per_stamp`: one dict of setting overrides per stamp
-        (context_pad, tg_steps, cfg_weight, tg_weight), merged over `settings` and the defaults; `steps` must agree across the batch."""
-        return self._stamp(canvas, settings, composite=False, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp)
+        (context_pad, tg_steps, cfg_weight, tg_weight), merged over `settings` and the defaults; `steps` must agree across the batch.
+        `strength` in (0, 1] (the whole call; inpaint_pipeline.py:63): below 1 the stamp starts from the canvas's own latents noised to
+        the sampler's t_start and runs only the last evaluations of the schedule (dtp_stamp_strength); 1 is today's
+        stamp from pure noise.  `init_eps` ([B,4,h,w]; False = the latent mean; drawn after `vae_eps` when None): the normal draw of the
+        canvas's VAE encode, used only below strength 1."""
+        return self._stamp(canvas, settings, composite=False, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp,
+                           strength=strength, init_eps=init_eps)
 
-    def generate(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, **settings):
+    def generate(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, strength=1.0, init_eps=None, **settings):
         """generate_raw + alpha composite (model_base.py:51-58), fused into the final kernel.  `slots`: one conditioning slot per
-        stamp of the batch (stamps of different clients / brushes in one call); None = slot 0 for all.  `per_stamp`: see generate_raw."""
-        return self._stamp(canvas, settings, composite=True, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp)
+        stamp of the batch (stamps of different clients / brushes in one call); None = slot 0 for all.  `per_stamp`, `strength`,
+        `init_eps`: see generate_raw."""
+        return self._stamp(canvas, settings, composite=True, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp,
+                           strength=strength, init_eps=init_eps)
 
-    def generate_u8(self, canvas, composite=True, slots=None, per_stamp=None, **settings):
+    def generate_u8(self, canvas, composite=True, slots=None, per_stamp=None, strength=1.0, init_eps=None, **settings):
         """Same as generate() but returns the handler's wire image: uint8 HWC, truncated (handler.py:55-56)."""
-        return self._stamp(canvas, settings, composite=composite, output_u8=True, slots=slots, per_stamp=per_stamp)
+        return self._stamp(canvas, settings, composite=composite, output_u8=True, slots=slots, per_stamp=per_stamp, strength=strength,
+                           init_eps=init_eps)
 
     def stage_times_ms(self):
         """[vae_encoder x2 + pre, denoise loop, vae + post] GPU ms of the last stamp (print_summary, sdp:486-503)."""

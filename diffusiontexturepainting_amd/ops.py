@@ -461,3 +461,27 @@ def sched_step(scheduler, row, next_scale, eps_out, x, hist, cfg, tg, rank, k, s
                                 int(step_index), b, h * w, int(k), _stream()), "sched_step")
     x.copy_(xs.permute(0, 3, 1, 2))
     return in16[..., :4].permute(0, 3, 1, 2)
+
+
+def strength_schedule(scheduler, steps, strength):
+    """Host-only initialize_timesteps of a sampler ("DDIM" | "DPM" | "LMSD" or its id) at `strength` (dtp_strength_schedule):
+    dict(t_start, evals, noise_coefs=(a, b)) -- the stamp's start point is a * z0 + b * latents and its loop runs table rows
+    t_start - steps_offset .. + evals - 1."""
+    lib = _lib.load()
+    sid = _lib.scheduler_id(scheduler) if isinstance(scheduler, str) else int(scheduler)
+    ts, ev, nc = C.c_int(), C.c_int(), (C.c_float * 2)()
+    check(lib.dtp_strength_schedule(sid, int(steps), C.c_double(float(strength)), C.byref(ts), C.byref(ev), nc), "dtp_strength_schedule")
+    return dict(t_start=ts.value, evals=ev.value, noise_coefs=(nc[0], nc[1]))
+
+
+def strength_init(z0, eps, a, b):
+    """The stamp's strength < 1 start point a * z0 + b * eps (dtp_op_strength_init) of two f32 device tensors of one shape."""
+    if z0.shape != eps.shape:
+        raise ValueError(f"z0 {tuple(z0.shape)} and eps {tuple(eps.shape)} differ")
+    lib = _lib.load()
+    z = z0.float().contiguous()
+    e = eps.float().contiguous()
+    out = torch.empty_like(z)
+    check(lib.dtp_op_strength_init(ptr(z), ptr(e), C.c_float(float(a)), C.c_float(float(b)), ptr(out), C.c_longlong(z.numel()), _stream()),
+          "strength_init")
+    return out

@@ -120,6 +120,21 @@ int dtp_stamp_slots(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
 int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
                     void* out, int B, const int* slots, dtp_stream s);
 
+/* Strength (inpaint_pipeline.py:63, the "repaint strength" of a stamp): dtp_stamp_mixed plus a start point other than pure noise.
+ *   init_eps  f32 [B,4,h,w] normal draw of the init image's VAE encode; NULL = its distribution mean
+ *   strength  in (0, 1] for the whole call.  The loop runs the reference's initialize_timesteps (stable_diffusion_pipeline.py:348-355):
+ *             evaluations t_start .. steps - 1 of the full schedule (dtp_strength_schedule), from
+ *             x = add_noise(z0, latents) = a z0 + b latents, z0 = 0.18215 sample(VAE_enc(canvas[:, :3] * 2 - 1)) of the FULL canvas
+ *             (not the alpha-masked image).  The masked / context latents, masks, dilation and composite are dtp_stamp_mixed's.
+ *             Texture guidance runs for clamp(tg_steps, 0, E) of the E evaluations; no sampler history carries over (DPM's first
+ *             evaluation is first order).
+ * strength == 1 is dtp_stamp_mixed exactly (init_eps ignored).  DTP_ERR_ARG for a strength outside (0, 1], NaN, or one that leaves no
+ * evaluation; DTP_ERR_STATE under any fp8 option.  A change of strength between calls rebuilds no table and never waits for the
+ * stream: the denoise loop is captured per start row, the pre-processing stage once with and once without the init image.  The first
+ * strength < 1 call of a batch size builds its 3B-row VAE-encoder program and re-captures that batch size's stages once. */
+int dtp_stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                       const float* init_eps, double strength, void* out, int B, const int* slots, dtp_stream s);
+
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
  * (DDIMScheduler.set_timesteps/configure, utilities.py:408-439).  Any pointer may be NULL. */
@@ -147,6 +162,14 @@ int dtp_ddim_tables(int steps, int64_t* timesteps, float* alphas, float* final_a
  *           sigma_{i-j} on sigma_i .. sigma_{i-order+1})          d_i = (x - x0) / sigma_i, x0 = x - sigma_i e;  x' = x + sum c_j d_{i-j}
  * The DDIM rows are the values dtp_stamp has always used (from dtp_ddim_tables).  DTP_ERR_ARG for an unknown scheduler or steps. */
 int dtp_scheduler_tables(int scheduler, int steps, int* evals, float* init_sigma, float* timesteps, float* in_scale, float* coefs);
+
+/* Host-only: initialize_timesteps of (scheduler, steps) at `strength`, in double as Python computes it:
+ *   init = min(int(steps * strength) + offset, steps), t_start = max(steps - init + offset, 0), evals = steps - t_start
+ * (offset = steps_offset: 1 for DDIM, 0 for DPM / LMSD); noise_coefs[2] = (a, b) of the start point x = a z0 + b latents: the sampler's
+ * add_noise at t_start (DDIM: sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod) at timesteps[t_start]; DPM: the same; LMSD: 1, sigma[t_start]),
+ * and (0, init_sigma) at strength 1.  Evaluation i of the stamp uses row t_start - offset + i of dtp_scheduler_tables.  DTP_ERR_ARG
+ * (naming "strength") for a strength outside (0, 1], NaN, or evals == 0; the dtp_scheduler_tables errors otherwise.  Any output may be NULL. */
+int dtp_strength_schedule(int scheduler, int steps, double strength, int* t_start, int* evals, float* noise_coefs);
 
 /* per-stage GPU time of the last dtp_stamp on this handle, ms (print_summary,
  * stable_diffusion_pipeline.py:486-503): [0]=pre+vae_encoder x2, [1]=denoise loop, [2]=vae decode+post.
@@ -375,6 +398,9 @@ int dtp_op_attention_fp8(const void* Q, const void* K, const void* V, void* O, i
                          int Sq, int Skv, int D, int64_t qbs, int64_t kbs, int64_t vbs, int64_t obs, float scale, float q_scale,
                          float v_scale, dtp_stream s);
 int dtp_op_softmax_rows(const void* x, int ldx, void* y, int ldy, int rows, int cols, float scale, dtp_stream s);
+/* The start point of a strength < 1 stamp as its pre-processing stage computes it (the same device function): x[i] = a z0[i] + b eps[i]
+ * over n f32 values, both products rounded before the sum (dtp_strength_schedule gives a, b). */
+int dtp_op_strength_init(const float* z0, const float* eps, float a, float b, float* x, long long n, dtp_stream s);
 /* kornia.morphology.dilation(alpha, ones(pad,pad)) of add_extra_context (handler.py:28-29) as the stamp runs it: canvas f32
  * [B,4,R,R] (the alpha plane is read), tmp / out f32 [B,R,R]; window rows/cols [i - pad/2, i + pad - pad/2 - 1], clipped */
 int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int pad, dtp_stream s);
@@ -387,7 +413,9 @@ int dtp_op_dilate_pads(const float* canvas, float* tmp, float* out, int B, int R
  *   hist    f32 [3][B][h*w][4]    the sampler history (DPM: previous x0 in slot 0; LMSD: derivatives d_{i-1..i-3} in slot i % 3)
  *   in16    f16 [2B + k][h*w][16] channels 0-3 of every row receive x' * next_scale[0] (the next evaluation's input)
  *   row     f32 [DTP_SCHED_ROW] (device) a row of dtp_scheduler_tables' coefs; next_scale f32 [1] (device)
- *   cfg, tg f32 [B], rank int [B] (device): stamp b's texture-guided row is 2B + rank[b] while rank[b] < k.  B <= 64, 0 <= k <= B. */
+ *   cfg, tg f32 [B], rank int [B] (device): stamp b's texture-guided row is 2B + rank[b] while rank[b] < k.  B <= 64, 0 <= k <= B.
+ *   step_index  the evaluation's index within the stamp's loop: DPM runs first order at step_index 0 whatever the row's order says (a
+ *               strength < 1 stamp starts mid-table without a previous x0); LMSD's history ring is indexed by it. */
 int dtp_op_sched_step(int scheduler, const float* eps_out, float* x, float* hist, void* in16, const float* row, const float* next_scale,
                       const float* cfg, const float* tg, const int* rank, int step_index, int B, int hw, int k, dtp_stream s);
 
