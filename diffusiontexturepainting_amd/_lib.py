@@ -134,6 +134,9 @@ SYMBOLS = {
     "dtp_stamp_strength": (_i, [_vp, _vp, C.POINTER(Settings), _vp, _vp, _vp, C.c_double, _vp, _i, C.POINTER(_i), _vp]),
     "dtp_strength_schedule": (_i, [_i, _i, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f)]),
     "dtp_op_strength_init": (_i, [_vp, _vp, _f, _f, _vp, C.c_longlong, _vp]),
+    "dtp_stamp_seeded": (_i, [_vp, _vp, C.POINTER(Settings), C.POINTER(C.c_uint64), _i, C.c_double, _vp, _i, C.POINTER(_i), _vp]),
+    "dtp_op_stamp_noise": (_i, [C.c_uint64, _i, _vp, C.c_longlong, _vp]),
+    "dtp_philox4x32": (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
 

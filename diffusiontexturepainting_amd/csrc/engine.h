@@ -430,3 +430,12 @@ int ensure_temb(Ctx* c, const std::vector<float>& timesteps);  // fills temb_tab
 
 // ---- stamp.hip
 int stamp_init(Ctx* c);
+
+// ---- noise.hip: the draws of a seeded stamp call (dtp_stamp_seeded).  Job j < nd writes draw `draw[j]` of every stamp b < B, generated
+// from seed[b], to dst[j] + b * 4 Q (Q = h w counters of four floats each); the seeds travel as a kernel argument, like PadArgs.
+struct NoiseArgs {
+  uint64_t seed[DTP_STAMP_MAXB];
+  float* dst[4];
+  int draw[4];
+};
+int dtp_launch_stamp_noise(const NoiseArgs& a, int nd, int B, long long Q, hipStream_t s);

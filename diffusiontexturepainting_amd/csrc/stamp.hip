@@ -731,19 +731,26 @@ struct StrengthPlan {
   const float* init_eps;
 };
 
+// a seeded stamp (dtp_stamp_seeded): the call's draws are generated into the staging buffers (noise.hip) instead of copied from the caller
+struct SeedPlan {
+  const uint64_t* seeds;  // host, [B]
+  bool sample_vae;        // draws 1, 2 (and 3 below strength 1) are used; false = the distribution means
+};
+
 static int stamp_run(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
-                     void* out, int B, const int* slots, dtp_stream s_, const StrengthPlan* sp);
+                     void* out, int B, const int* slots, dtp_stream s_, const StrengthPlan* sp, const SeedPlan* seeded = nullptr);
 
 int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
                     void* out, int B, const int* slots, dtp_stream s) {
   return stamp_run(ctx, canvas, st, latents, vae_eps, out, B, slots, s, nullptr);
 }
 
-int dtp_stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
-                       const float* init_eps, double strength, void* out, int B, const int* slots, dtp_stream s) {
+// dtp_stamp_strength, and dtp_stamp_seeded with `seeded` in place of the three noise pointers
+static int stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                          const float* init_eps, double strength, void* out, int B, const int* slots, dtp_stream s, const SeedPlan* seeded) {
   Ctx* c = (Ctx*)ctx;
   if (!(strength > 0.0 && strength <= 1.0)) { dtp_set_error("dtp_stamp_strength: strength %g outside (0, 1]", strength); return DTP_ERR_ARG; }
-  if (strength == 1.0) return dtp_stamp_mixed(ctx, canvas, st, latents, vae_eps, out, B, slots, s);  // today's path, init_eps unused
+  if (strength == 1.0) return stamp_run(ctx, canvas, st, latents, vae_eps, out, B, slots, s, nullptr, seeded);  // dtp_stamp_mixed, init_eps unused
   if (!c || !c->finalized) { dtp_set_error("dtp_stamp: weights not finalized"); return DTP_ERR_STATE; }
   if (!st || B < 1 || B > c->maxB) { dtp_set_error("dtp_stamp: bad argument (B=%d, max %d)", B, c->maxB); return DTP_ERR_ARG; }
   if (c->fp8_linear || c->fp8_attention || c->fp8_operands) {
@@ -761,15 +768,27 @@ int dtp_stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st
   sp.a = ab[0];
   sp.b = ab[1];
   sp.init_eps = init_eps;
-  return stamp_run(ctx, canvas, st, latents, vae_eps, out, B, slots, s, &sp);
+  return stamp_run(ctx, canvas, st, latents, vae_eps, out, B, slots, s, &sp, seeded);
+}
+
+int dtp_stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
+                       const float* init_eps, double strength, void* out, int B, const int* slots, dtp_stream s) {
+  return stamp_strength(ctx, canvas, st, latents, vae_eps, init_eps, strength, out, B, slots, s, nullptr);
+}
+
+int dtp_stamp_seeded(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const uint64_t* seeds, int sample_vae, double strength,
+                     void* out, int B, const int* slots, dtp_stream s) {
+  if (!seeds) { dtp_set_error("dtp_stamp_seeded: seeds is NULL (one uint64 per stamp, host memory)"); return DTP_ERR_ARG; }
+  const SeedPlan seeded = {seeds, sample_vae != 0};
+  return stamp_strength(ctx, canvas, st, nullptr, nullptr, nullptr, strength, out, B, slots, s, &seeded);
 }
 
 static int stamp_run(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
-                     void* out, int B, const int* slots, dtp_stream s_, const StrengthPlan* sp) {
+                     void* out, int B, const int* slots, dtp_stream s_, const StrengthPlan* sp, const SeedPlan* seeded) {
   Ctx* c = (Ctx*)ctx;
   hipStream_t s = (hipStream_t)s_;
   if (!c || !c->finalized) { dtp_set_error("dtp_stamp: weights not finalized"); return DTP_ERR_STATE; }
-  if (!canvas || !st || !latents || !out || B < 1 || B > c->maxB) { dtp_set_error("dtp_stamp: bad argument (B=%d, max %d)", B, c->maxB); return DTP_ERR_ARG; }
+  if (!canvas || !st || (!latents && !seeded) || !out || B < 1 || B > c->maxB) { dtp_set_error("dtp_stamp: bad argument (B=%d, max %d)", B, c->maxB); return DTP_ERR_ARG; }
   SlotArgs sa = {};
   for (int b = 0; b < B; ++b) {
     const int sl = slots ? slots[b] : 0;
@@ -879,11 +898,26 @@ static int stamp_run(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, 
   // ---- stage 0: pre-processing + both VAE encodes (one batch-2B pass)
   {
   RoctxRange r0("dtp_stamp: pre-processing + vae_encoder x2");
-  HIP_CHECK(hipMemcpyAsync(sb->lat, latents, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
-  if (vae_eps) HIP_CHECK(hipMemcpyAsync(sb->eps, vae_eps, (size_t)2 * B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
-  const float* init_eps = sp ? sp->init_eps : nullptr;
   float* eps3 = sb->eps + (size_t)2 * B * 4 * HWl;  // (third slab: only with sp)
-  if (init_eps) HIP_CHECK(hipMemcpyAsync(eps3, init_eps, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
+  // which VAE draws the stage consumes: the caller's pointers, or the seeded call's one switch
+  const bool use_eps = seeded ? seeded->sample_vae : vae_eps != nullptr;
+  const bool use_init = sp && (seeded ? seeded->sample_vae : sp->init_eps != nullptr);
+  if (seeded) {  // one launch draws what the copies below deliver: latents (draw 0), the two VAE draws (1, 2), the init image's (3)
+    NoiseArgs na = {};
+    for (int b = 0; b < B; ++b) na.seed[b] = seeded->seeds[b];
+    int nd = 0;
+    na.dst[nd] = sb->lat; na.draw[nd++] = 0;
+    if (use_eps) {
+      na.dst[nd] = sb->eps; na.draw[nd++] = 1;
+      na.dst[nd] = sb->eps + (size_t)B * 4 * HWl; na.draw[nd++] = 2;
+    }
+    if (use_init) { na.dst[nd] = eps3; na.draw[nd++] = 3; }
+    RC(dtp_launch_stamp_noise(na, nd, B, HWl, s));
+  } else {
+    HIP_CHECK(hipMemcpyAsync(sb->lat, latents, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
+    if (use_eps) HIP_CHECK(hipMemcpyAsync(sb->eps, vae_eps, (size_t)2 * B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
+    if (use_init) HIP_CHECK(hipMemcpyAsync(eps3, sp->init_eps, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
+  }
   HIP_CHECK(hipMemcpyAsync(c->canvas32, canvas, (size_t)B * 4 * HW * 4, hipMemcpyDeviceToDevice, s));
   int pads[DTP_STAMP_MAXB];
   for (int b = 0; b < B; ++b) pads[b] = st[b].context_pad;
@@ -894,13 +928,13 @@ static int stamp_run(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, 
   const int k0 = ks[0];
   UNetProg* first = prog[k0];
   // keyed by "init image on/off" (and its draw), not by the strength: the add_noise pair and start row are read from the parameter block
-  const long long init_bits = sp ? ((1LL << 20) | (init_eps ? 1LL << 21 : 0)) : 0;
-  RC(run_stage(c, {((long long)B << 32) | ((long long)k0 << 4) | (vae_eps ? 2 : 0) | (k0 > 0 ? 1 : 0) | init_bits | (1LL << 60)}, false, s,
+  const long long init_bits = sp ? ((1LL << 20) | (use_init ? 1LL << 21 : 0)) : 0;
+  RC(run_stage(c, {((long long)B << 32) | ((long long)k0 << 4) | (use_eps ? 2 : 0) | (k0 > 0 ? 1 : 0) | init_bits | (1LL << 60)}, false, s,
                [&](hipStream_t q) -> int {
     hipLaunchKernelGGL(prep_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, q, c->canvas32, c->brush32, c->slot_map,
                        c->alpha_tmp + (size_t)c->maxB * HW, enc->in8, sb->masks, B, R, sp ? 1 : 0);
     RC(enc->main.run(q, 0));
-    RC(launch_vae_sample(c, enc->moments, vae_eps ? sb->eps : nullptr, sb->ml, (sp ? 3 : 2) * B, VAE_SCALE, q, init_eps ? eps3 : nullptr,
+    RC(launch_vae_sample(c, enc->moments, use_eps ? sb->eps : nullptr, sb->ml, (sp ? 3 : 2) * B, VAE_SCALE, q, use_init ? eps3 : nullptr,
                          2 * B));
     const float* z0 = sp ? sb->ml + (size_t)2 * B * 4 * HWl : nullptr;  // 0.18215 * sample(VAE_enc(canvas)): the init-image latents
     hipLaunchKernelGGL(assemble_kernel, dim3(nblk((long long)B * HWl)), dim3(256), 0, q, sb->lat, z0, sb->masks, sb->ml, rank, first->in16,

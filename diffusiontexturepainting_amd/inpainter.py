@@ -8,6 +8,7 @@ the stream and the noise generator; all arithmetic runs in the HIP library, and 
 library or a failing call raises (there is no fallback path).
 """
 import ctypes as C
+import operator
 import os
 
 import torch
@@ -29,6 +30,44 @@ def check_strength_args(strength, init_eps, B, h):
     if strength < 1.0 and init_eps is not None and init_eps is not False and tuple(init_eps.shape) != (B, 4, h, h):
         raise ValueError(f"init_eps must be {B} x 4 x {h} x {h} (one draw per stamp), got {tuple(init_eps.shape)}")
     return strength
+
+
+def check_seed_args(seeds, B, latents=None, vae_eps=None, init_eps=None, strength=1.0):
+    """The `seeds` argument of the generate calls.  None: returns None (the unseeded path).  An int s: stamp b gets (s + b) mod 2^64; a
+    sequence: B ints.  Every seed is an int in 0 .. 2^64 - 1 (ValueError otherwise).  The seeded call draws its own noise, so a
+    `latents`, `vae_eps` or `init_eps` tensor next to `seeds` is a ValueError; vae_eps=False / init_eps=False (the distribution mean)
+    stay valid, and below strength 1 the two must agree, since dtp_stamp_seeded has one switch for all VAE draws.
+    Returns (list of B seeds, sample_vae)."""
+    if seeds is None:
+        return None
+    for name, t in (("latents", latents), ("vae_eps", vae_eps), ("init_eps", init_eps)):
+        if t is not None and t is not False:
+            raise ValueError(f"seeds and {name} are exclusive: a seeded stamp draws its own noise (dtp_stamp_seeded)")
+    if latents is False:
+        raise ValueError("seeds with latents=False: the initial latents are always drawn")
+    if float(strength) < 1.0 and (vae_eps is False) != (init_eps is False):
+        raise ValueError("seeds below strength 1: pass vae_eps=False and init_eps=False together (one switch for all VAE draws)")
+    try:
+        if isinstance(seeds, (bool, str, bytes)):
+            raise TypeError
+        try:
+            base = operator.index(seeds)  # an int (numpy integers included)
+        except TypeError:
+            if any(isinstance(v, bool) for v in seeds):
+                raise
+            out = [operator.index(v) for v in seeds]
+        else:
+            if not 0 <= base < 1 << 64:
+                raise ValueError(f"seeds must be in 0 .. 2^64 - 1, got {base}")
+            out = [(base + b) & ((1 << 64) - 1) for b in range(B)]
+    except TypeError:
+        raise ValueError(f"seeds must be an int or a sequence of {B} ints, got {seeds!r}") from None
+    if len(out) != B:
+        raise ValueError(f"{len(out)} seeds for {B} stamps")
+    for v in out:
+        if not 0 <= v < 1 << 64:
+            raise ValueError(f"seeds must be in 0 .. 2^64 - 1, got {v}")
+    return out, vae_eps is not False
 
 
 class MI355ConditionalInpainter(ConditionalInpainterBase):
@@ -167,7 +206,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             self.conditioning = (ce.unsqueeze(0), ue.unsqueeze(0))
 
     def _stamp(self, canvas, settings, composite, latents=None, vae_eps=None, output_u8=False, slots=None, per_stamp=None, strength=1.0,
-               init_eps=None):
+               init_eps=None, seeds=None):
         if not self._slots:
             raise _lib.DtpError("no brush set: call set_brush() first")
         R, h = self._resolution, self._resolution // 8
@@ -176,6 +215,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         if canvas.shape != (B, 4, R, R):
             raise ValueError(f"canvas must be B x 4 x {R} x {R}, got {tuple(canvas.shape)}")
         strength = check_strength_args(strength, init_eps, B, h)
+        seeded = check_seed_args(seeds, B, latents, vae_eps, init_eps, strength)
         s = {**DEFAULT_SETTINGS, **{k: v for k, v in settings.items() if k in DEFAULT_SETTINGS}}
         st = Settings(int(s["steps"]), int(s["context_pad"]), int(s["tg_steps"]), float(s["cfg_weight"]), float(s["tg_weight"]),
                       int(composite), int(output_u8))  # numpy scalars are cast here (server_io.py:104-119)
@@ -185,13 +225,15 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             each = [{**s, **{k: v for k, v in d.items() if k in DEFAULT_SETTINGS}} for d in per_stamp]
             st = (Settings * B)(*[Settings(int(e["steps"]), int(e["context_pad"]), int(e["tg_steps"]), float(e["cfg_weight"]),
                                            float(e["tg_weight"]), int(composite), int(output_u8)) for e in each])
-        if latents is None:
+        if seeded is not None:  # the library draws: self.generator is not touched
+            latents, vae_eps, init_eps = None, False, False
+        if latents is None and seeded is None:
             latents = torch.randn((B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
         if vae_eps is None:
             vae_eps = torch.randn((2, B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
         if strength < 1.0 and init_eps is None:  # the third draw, after the two of today's path
             init_eps = torch.randn((B, 4, h, h), device=self._device, dtype=torch.float32, generator=self.generator)
-        latents = latents.to(self._device, torch.float32).contiguous()
+        latents = latents.to(self._device, torch.float32).contiguous() if latents is not None else None
         vae_eps = vae_eps.to(self._device, torch.float32).contiguous() if vae_eps is not False else None
         init_eps = init_eps.to(self._device, torch.float32).contiguous() if strength < 1.0 and init_eps is not False else None
         out = (torch.empty(B, R, R, 3, dtype=torch.uint8, device=self._device) if output_u8
@@ -199,7 +241,12 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
         if slots is not None and len(slots) != B:
             raise ValueError(f"{len(slots)} slots for {B} stamps")
-        if strength < 1.0:  # strength is per call: one settings array (per_stamp's, or `settings` for every stamp)
+        if seeded is not None:  # one settings array, like strength: dtp_stamp_seeded is dtp_stamp_strength with the library's own draws
+            each = st if per_stamp is not None else (Settings * B)(*([st] * B))
+            arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
+            check(self._lib.dtp_stamp_seeded(self._h, ptr(canvas), each, (C.c_uint64 * B)(*seeded[0]), int(seeded[1]), C.c_double(strength),
+                                             ptr(out), B, arr, self._s()), "dtp_stamp_seeded")
+        elif strength < 1.0:  # strength is per call: one settings array (per_stamp's, or `settings` for every stamp)
             each = st if per_stamp is not None else (Settings * B)(*([st] * B))
             arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
             check(self._lib.dtp_stamp_strength(self._h, ptr(canvas), each, ptr(latents), ptr(vae_eps), ptr(init_eps), C.c_double(strength),
@@ -223,7 +270,8 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
         return out
 
-    def generate_raw(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, strength=1.0, init_eps=None, **settings):
+    def generate_raw(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, strength=1.0, init_eps=None, seeds=None,
+                     **settings):
         """canvas B x 4 x R x R 0..1 -> B x 3 x R x R 0..1 (trt_model.py:90-121).  `latents`
         ([B,4,h,w]) / `vae_eps` ([2,B,4,h,w]; False = use the latent mean) override the internal
         generator -- the parity tests feed CPU-generated noise through them.  `per_stamp`: one dict of setting overrides per stamp
@@ -231,21 +279,25 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         `strength` in (0, 1] (the whole call; inpaint_pipeline.py:63): below 1 the stamp starts from the canvas's own latents noised to
         the sampler's t_start and runs only the last evaluations of the schedule (dtp_stamp_strength); 1 is today's
         stamp from pure noise.  `init_eps` ([B,4,h,w]; False = the latent mean; drawn after `vae_eps` when None): the normal draw of the
-        canvas's VAE encode, used only below strength 1."""
+        canvas's VAE encode, used only below strength 1.
+        `seeds` (an int s: stamp b gets s + b; or B ints, each 0 .. 2^64 - 1): the stamp's noise is drawn on the device from its own
+        seed (dtp_stamp_seeded), the same numbers in any batch, slot order or replica; exclusive with `latents` / `vae_eps` / `init_eps`
+        tensors (vae_eps=False and init_eps=False still select the means), and the internal generator is left alone."""
         return self._stamp(canvas, settings, composite=False, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp,
-                           strength=strength, init_eps=init_eps)
+                           strength=strength, init_eps=init_eps, seeds=seeds)
 
-    def generate(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, strength=1.0, init_eps=None, **settings):
+    def generate(self, canvas, latents=None, vae_eps=None, slots=None, per_stamp=None, strength=1.0, init_eps=None, seeds=None,
+                 **settings):
         """generate_raw + alpha composite (model_base.py:51-58), fused into the final kernel.  `slots`: one conditioning slot per
         stamp of the batch (stamps of different clients / brushes in one call); None = slot 0 for all.  `per_stamp`, `strength`,
-        `init_eps`: see generate_raw."""
+        `init_eps`, `seeds`: see generate_raw."""
         return self._stamp(canvas, settings, composite=True, latents=latents, vae_eps=vae_eps, slots=slots, per_stamp=per_stamp,
-                           strength=strength, init_eps=init_eps)
+                           strength=strength, init_eps=init_eps, seeds=seeds)
 
-    def generate_u8(self, canvas, composite=True, slots=None, per_stamp=None, strength=1.0, init_eps=None, **settings):
+    def generate_u8(self, canvas, composite=True, slots=None, per_stamp=None, strength=1.0, init_eps=None, seeds=None, **settings):
         """Same as generate() but returns the handler's wire image: uint8 HWC, truncated (handler.py:55-56)."""
         return self._stamp(canvas, settings, composite=composite, output_u8=True, slots=slots, per_stamp=per_stamp, strength=strength,
-                           init_eps=init_eps)
+                           init_eps=init_eps, seeds=seeds)
 
     def stage_times_ms(self):
         """[vae_encoder x2 + pre, denoise loop, vae + post] GPU ms of the last stamp (print_summary, sdp:486-503)."""

@@ -485,3 +485,21 @@ def strength_init(z0, eps, a, b):
     check(lib.dtp_op_strength_init(ptr(z), ptr(e), C.c_float(float(a)), C.c_float(float(b)), ptr(out), C.c_longlong(z.numel()), _stream()),
           "strength_init")
     return out
+
+
+def philox4x32(counter, key):
+    """Host-only: Philox4x32-10 of one (counter: 4 uint32, key: 2 uint32) -> 4 uint32, the bit generator of the seeded stamps
+    (dtp_philox4x32: the function the noise kernel runs)."""
+    lib = _lib.load()
+    ctr, k, out = (C.c_uint32 * 4)(*[int(v) for v in counter]), (C.c_uint32 * 2)(*[int(v) for v in key]), (C.c_uint32 * 4)()
+    check(lib.dtp_philox4x32(ctr, k, out), "dtp_philox4x32")
+    return tuple(out)
+
+
+def stamp_noise(seed, draw, n, device=None):
+    """The n = 4 h w normals of draw `draw` (0 latents, 1 / 2 the VAE draws of the masked / context image, 3 init_eps) of a stamp
+    seeded `seed` (0 .. 2^64 - 1), as dtp_stamp_seeded draws them (dtp_op_stamp_noise: the same device function): f32 [n]."""
+    lib = _lib.load()
+    out = torch.empty(max(int(n), 0), dtype=torch.float32, device=device if device is not None else torch.cuda.current_device())
+    check(lib.dtp_op_stamp_noise(C.c_uint64(int(seed)), int(draw), ptr(out), C.c_longlong(int(n)), _stream()), "stamp_noise")
+    return out

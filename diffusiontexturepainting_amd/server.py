@@ -17,6 +17,11 @@ things a multi-client deployment needs:
     cfg_weight, tg_weight and tg_steps (dtp_stamp_mixed), so clients who moved their sliders still share a batch.  Gathering
     still stops at a brush change, a slot release, a stamp with other `steps` or a second stamp of a client already in the
     batch.  Off by default: the grouping is then exactly the equal-settings rule.
+    With `seeded=True` (and a model whose generate() takes `seeds`) every stamp runs with a seed of its own,
+    splitmix64(base_seed ^ (client id << 32) ^ n) for the n-th stamp of a client since it attached, and the model draws that stamp's
+    noise from it (dtp_stamp_seeded): a client's n-th stamp is the same image however the queue batched it, in whichever slot order
+    and on whichever replica.  The seed is derived here and logged at debug level; it does not travel, the wire format is unchanged.
+    Brush previews are not stamps and stay on the model's own generator.  Off by default: the calls carry no `seeds`.
   * `StampServer` -- routes every new client to the least-loaded replica (one model / process-local GPU each) and keeps it
     there (its brush lives in that replica's slot table).
   * error replies -- the reference logs an exception and sends nothing (handler.py:83-89), which leaves the Kit client waiting
@@ -27,6 +32,7 @@ Nothing here touches the GPU directly: the model only has to provide resolution(
 slot_image(slot) / generate(canvas, slots=[...], **settings) -- MI355ConditionalInpainter does, and so do the CPU fakes of the
 tests.
 """
+import hashlib
 import inspect
 import logging
 import queue
@@ -89,6 +95,7 @@ class _Job:
     done: threading.Event = field(default_factory=threading.Event)
     delivered: threading.Event = field(default_factory=threading.Event)  # the reply bytes have been written (see StampQueue._send)
     error: str = None
+    seed: int = None               # seeded queues: the stamp's own noise seed (stamp_seed)
 
 
 def _settings_key(s):
@@ -107,12 +114,48 @@ def _takes_per_stamp(model):
         return False
 
 
+def _takes_seeds(model):
+    """Whether model.generate accepts per-stamp noise seeds (MI355ConditionalInpainter does)."""
+    try:
+        return "seeds" in inspect.signature(model.generate).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(x):
+    """The splitmix64 output function (Steele, Lea, Flood: "Fast splittable pseudorandom number generators", 2014) of a 64-bit state."""
+    z = (x + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _client_number(client_id):
+    """A client id as an integer: an int is itself; anything else is hashed by its text (stable across processes, unlike hash())."""
+    if isinstance(client_id, int) and not isinstance(client_id, bool):
+        return client_id
+    return int.from_bytes(hashlib.blake2b(str(client_id).encode("utf-8"), digest_size=8).digest(), "little")
+
+
+def stamp_seed(base_seed, client_id, n):
+    """Noise seed of the n-th stamp (from 0) of a client: splitmix64(base_seed ^ (client id << 32) ^ n), all in 64 bits."""
+    return splitmix64((int(base_seed) ^ (_client_number(client_id) << 32) ^ int(n)) & _M64)
+
+
 class StampQueue:
     """Work queue of ONE replica (one model on one GPU).  A worker thread drains it: brush changes run alone (they re-encode
     a slot), stamps pending at the same time are grouped by settings and batched."""
 
-    def __init__(self, model, max_batch=8, error_replies=False, gather_window_s=0.002, n_slots=16, post=None, mixed_settings=False):
+    def __init__(self, model, max_batch=8, error_replies=False, gather_window_s=0.002, n_slots=16, post=None, mixed_settings=False,
+                 seeded=False, base_seed=0):
         self.model, self.max_batch, self.error_replies, self.window = model, int(max_batch), error_replies, gather_window_s
+        if seeded and not _takes_seeds(model):
+            raise TypeError(f"seeded=True needs a model whose generate() takes `seeds`; {type(model).__name__}.generate does not")
+        self.seeded, self.base_seed = bool(seeded), int(base_seed)
+        self.stamp_counts = {}         # client id -> stamps submitted since it attached (seeded queues)
         self.mixed = bool(mixed_settings) and _takes_per_stamp(model)  # batch stamps whose settings differ (all but `steps`)
         self.post = post               # post(reply_fn, data): how a reply leaves the worker thread (None: call reply_fn here)
         self.q = queue.Queue()
@@ -141,12 +184,24 @@ class StampQueue:
         client that is handed the slot at once would otherwise re-encode it under a stamp that is still waiting for it."""
         with self.lock:
             slot = self.clients.pop(client_id, None)
+            self.stamp_counts.pop(client_id, None)  # a client that comes back starts at stamp 0 again
         if slot is not None:
             self.q.put(_Job("release", slot, {}, None, lambda _b: None))
 
     def load(self):
         with self.lock:
             return len(self.clients)
+
+    def next_stamp_seed(self, client_id):
+        """Seed of this client's next stamp (None on an unseeded queue); counts the stamp."""
+        if not self.seeded:
+            return None
+        with self.lock:
+            n = self.stamp_counts.get(client_id, 0)
+            self.stamp_counts[client_id] = n + 1
+        seed = stamp_seed(self.base_seed, client_id, n)
+        logger.debug("client %r stamp %d: seed %#018x", client_id, n, seed)
+        return seed
 
     def submit(self, job):
         with self.lock:  # the same lock close() holds while it raises `stopping`: a job is either queued before the drain or refused
@@ -232,11 +287,12 @@ class StampQueue:
         try:
             m = self.model
             canvas = torch.stack([j.payload for j in jobs]).to(m.device())            # handler.py:106, batched
+            kw = dict(seeds=[j.seed for j in jobs]) if self.seeded else {}
             if any(_settings_key(j.settings) != _settings_key(jobs[0].settings) for j in jobs):  # (mixed_settings only)
-                result = m.generate(canvas, slots=[j.slot for j in jobs], per_stamp=[dict(j.settings) for j in jobs],
+                result = m.generate(canvas, slots=[j.slot for j in jobs], per_stamp=[dict(j.settings) for j in jobs], **kw,
                                     **jobs[0].settings).cpu()
             else:
-                result = m.generate(canvas, slots=[j.slot for j in jobs], **jobs[0].settings).cpu()  # :107
+                result = m.generate(canvas, slots=[j.slot for j in jobs], **kw, **jobs[0].settings).cpu()  # :107
             self.batch_sizes.append(len(jobs))
         except Exception as e:
             if len(jobs) == 1:
@@ -303,10 +359,13 @@ class StampServer:
     """Front of N replicas.  `on_message(client_id, message, write_message)` is the whole per-connection protocol
     (handler.py:78-123); `close_client` frees the client's slot."""
 
-    def __init__(self, models, max_batch=8, error_replies=False, gather_window_s=0.002, post=None, mixed_settings=False):
-        """mixed_settings: batch stamps whose guidance settings differ (see the module docstring); off = equal settings only."""
+    def __init__(self, models, max_batch=8, error_replies=False, gather_window_s=0.002, post=None, mixed_settings=False, seeded=False,
+                 base_seed=0):
+        """mixed_settings: batch stamps whose guidance settings differ (see the module docstring); off = equal settings only.
+        seeded: every stamp draws its noise from a seed derived from (base_seed, client id, the client's stamp count), so its image
+        does not depend on how it was batched (module docstring); TypeError if a model's generate() takes no `seeds`."""
         self.queues = [StampQueue(m, max_batch=max_batch, error_replies=error_replies, gather_window_s=gather_window_s, post=post,
-                                  mixed_settings=mixed_settings) for m in models]
+                                  mixed_settings=mixed_settings, seeded=seeded, base_seed=base_seed) for m in models]
         self.post = post
         self.route = {}  # client id -> queue index
         self.error_replies = error_replies
@@ -347,7 +406,7 @@ class StampServer:
                 canvas = np_to_torch(sio.binary_to_image(message, off))
                 if tuple(canvas.shape) != (4, res, res):
                     raise ValueError(f"stamp canvas must be {res}x{res} RGBA, got {tuple(canvas.shape)}")
-                job = _Job("stamp", slot, settings, canvas, write_message)
+                job = _Job("stamp", slot, settings, canvas, write_message, seed=q.next_stamp_seed(client_id))
             else:
                 raise NotImplementedError(f"Unknown binary request type {meta['type']}")  # :123
         except Exception as e:

@@ -20,6 +20,8 @@
 extern "C" {
 #endif
 
+/* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32) are additions; nothing that existed
+ * at version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
 /* error codes (every entry point returns one; dtp_last_error() has the text) */
@@ -134,6 +136,28 @@ int dtp_stamp_mixed(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, c
  * strength < 1 call of a batch size builds its 3B-row VAE-encoder program and re-captures that batch size's stages once. */
 int dtp_stamp_strength(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const float* latents, const float* vae_eps,
                        const float* init_eps, double strength, void* out, int B, const int* slots, dtp_stream s);
+
+/* Seeded stamps: dtp_stamp_strength with its three noise pointers replaced by draws the library makes on the device, each a pure
+ * function of (the stamp's seed, which draw, element) -- not of the batch index, the batch size, the slot order or the GPU it runs on,
+ * so a stamp can be replayed alone, in any batch and on any replica with the same numbers.
+ *   seeds       host uint64_t[B], one per stamp; read before the call returns
+ *   sample_vae  1: the VAE encodes are sampled (draws 1, 2 and, below strength 1, 3); 0: their distribution means, i.e. vae_eps = NULL
+ *               and init_eps = NULL, and only draw 0 is used
+ *   strength    as dtp_stamp_strength; 1 is dtp_stamp_mixed
+ * Generator (fixed: part of the ABI): Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and counter = (q & 0xffffffff, q >> 32,
+ * draw, 0), q = e >> 2 for element e of ONE stamp's [4,h,w] tensor (NCHW), draw = 0 initial latents, 1 vae_eps of the masked image,
+ * 2 vae_eps of the context image, 3 init_eps.  With u(w) = ((w >> 8) + 0.5) 2^-24, words (0,1) of a counter give elements 4q, 4q+1 =
+ * r cos t, r sin t (r = sqrt(-2 ln u(w0)), t = 2 pi u(w1)) and words (2,3) give 4q+2, 4q+3; |z| <= 5.9.
+ * Every check, error code and asynchrony guarantee of dtp_stamp_strength carries over: one kernel launch writes the draws into the
+ * staging buffers in place of the three copies, outside the captured stages, so a change of seeds re-captures nothing and the host never
+ * waits.  DTP_ERR_ARG naming "seeds" when seeds is NULL. */
+int dtp_stamp_seeded(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, const uint64_t* seeds, int sample_vae, double strength,
+                     void* out, int B, const int* slots, dtp_stream s);
+/* The n floats of draw `draw` (0..3) of a stamp seeded `seed`, through the same device function: out f32 [n] (device, 16-byte aligned),
+ * n = 4 h w.  DTP_ERR_ARG unless n > 0, n % 4 == 0 and draw in 0..3. */
+int dtp_op_stamp_noise(uint64_t seed, int draw, float* out, long long n, dtp_stream s);
+/* Host-only: Philox4x32-10 of one (counter, key), compiled from the function the kernel runs (Random123's known answers hold). */
+int dtp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
