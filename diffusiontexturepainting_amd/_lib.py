@@ -137,6 +137,10 @@ SYMBOLS = {
     "dtp_stamp_seeded": (_i, [_vp, _vp, C.POINTER(Settings), C.POINTER(C.c_uint64), _i, C.c_double, _vp, _i, C.POINTER(_i), _vp]),
     "dtp_op_stamp_noise": (_i, [C.c_uint64, _i, _vp, C.c_longlong, _vp]),
     "dtp_philox4x32": (_i, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dtp_refit_stage": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(_i64), _i]),
+    "dtp_refit_lora": (_i, [_vp, _f]),
+    "dtp_last_refit_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f)]),
+    "dtp_op_lora_refit": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 

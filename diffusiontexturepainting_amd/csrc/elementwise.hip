@@ -1,5 +1,6 @@
 // Layout / packing / elementwise kernels (HBM-bound; 16-byte accesses where the layout allows).
 #include "common.h"
+#include "weight_math.h"
 
 namespace {
 
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void pack_linear_kernel(const float* __restric
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int k = (int)(i % K), n = (int)(i / K);
     const int r = row_map ? row_map[n] : n;
-    out[(size_t)r * ldw + k] = (f16)w[i];
+    out[(size_t)r * ldw + k] = pack_weight_f16(w[i]);
   }
 }
 
@@ -83,9 +84,7 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(float* __restrict__ w, 
   const long long total = (long long)N * K;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int k = (int)(i % K), n = (int)(i / K);
-    float acc = 0.f;
-    for (int r = 0; r < rank; ++r) acc += up[(size_t)n * rank + r] * down[(size_t)r * K + k];
-    w[i] += scale * acc;
+    w[i] = lora_merged(w[i], scale, lora_accumulate(0.f, up + (size_t)n * rank, down + k, K, rank));  // (weight_math.h: shared with the refit)
   }
 }
 
@@ -104,23 +103,18 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ w
                                                       int N, int K) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= N) return;
-  float acc = 0.f;
-  for (int k = lane; k < K; k += 64) acc += w[(size_t)row * K + k] * v[k];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  const float* wr = w + (size_t)row * K;
+  const float acc = wave_rowdot([&](int k) { return wr[k]; }, v, K, lane);
   if (lane == 0) out[row] = acc;
 }
 __global__ __launch_bounds__(256) void scale_cols_kernel(float* __restrict__ w, const float* __restrict__ g, int N, int K) {
   const long long total = (long long)N * K;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) w[i] *= g[i % K];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) w[i] = ln_fold_gamma(w[i], g[i % K]);
 }
 __global__ __launch_bounds__(256) void rowsum_f16_kernel(const f16* __restrict__ w, int ld, int K, float* __restrict__ out, int rows) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
-  float acc = 0.f;
-  for (int k = lane; k < K; k += 64) acc += (float)w[(size_t)row * ld + k];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  const float acc = wave_rowsum_f16(w + (size_t)row * ld, K, lane);
   if (lane == 0) out[row] = acc;
 }
 
@@ -160,12 +154,7 @@ __global__ __launch_bounds__(256) void expand_kv_kernel(const f16* __restrict__ 
 __global__ __launch_bounds__(256) void transpose_f16_kernel(const f16* __restrict__ src, int lds_, f16* __restrict__ dst, int ldd, int rows,
                                                             int cols) {
   __shared__ f16 t[32][33];
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int r = ty; r < 32; r += 8)
-    t[r][tx] = (by + r < rows && bx + tx < cols) ? src[(size_t)(by + r) * lds_ + bx + tx] : (f16)0.f;
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8)
-    if (bx + r < cols && by + tx < rows) dst[(size_t)(bx + r) * ldd + by + tx] = t[tx][r];
+  transpose_tile_f16(t, src, lds_, dst, ldd, rows, cols, blockIdx.x * 32, blockIdx.y * 32);
 }
 
 // out[r] = sum_k a[r][k] * v[k]  (fp16 rows, fp32 vector), one wave per row

@@ -109,6 +109,22 @@ struct VaeAttnW {
   float* bv = nullptr;
 };
 
+// ---- LoRA refit (lora_refit.hip).  The three job records are what the grouped kernels read from a device table.
+struct LoraRefitJob {  // one target matrix: dst rows [row0, row0 + N) x columns [0, K) = f16((base + scale * up @ down) * gamma[k])
+  const float *base, *up, *down;  // f32 [N][K], [N][rank], [rank][K]; rank == 0: up / down unused (the matrix becomes its base)
+  const float* gamma;             // LayerNorm gain folded into the columns, or null
+  const float* beta;              // LayerNorm bias: wbeta[n] = 0 + sum_k (base + scale * up @ down)[n][k] * beta[k] (the folded bias b'), or null
+  float* wbeta;                   // [N], the rows of the stacked bias this matrix owns
+  f16* dst;                       // the packed buffer [>= roundup(row0 + N, 128)][ldw]
+  int rank, N, K, row0, ldw;
+};
+struct RowsumJob { const f16* w; float* out; int ld, K, rows; };                    // out[r] = sum_k w[r][k] (`lns`)
+struct TransposeJob { const f16* src; f16* dst; int lds, ldd, rows, cols; };        // dst[c][r] = src[r][c] (`q2T`)
+struct RefitTarget {  // host side: a LoRA-targetable matrix and where every program reads it from
+  std::string name;   // staged name of its weight, "unet.<module>.<proj>.weight"
+  LoraRefitJob job;   // base / gamma / beta / wbeta / dst / N / K / row0 / ldw filled at finalize; up / down / rank per refit
+};
+
 struct UNetW {
   ConvW conv_in, conv_out, t1, t2, tproj;  // tproj: all 22 time_emb_proj stacked
   NormW norm_out;
@@ -340,6 +356,18 @@ struct Ctx {
   void* tune_thrash = nullptr;     // 512 MiB scratch written before every timed tuning launch (cold weights)
   std::string tune_cache_path;     // $DTP_TUNE_CACHE: persisted (shape -> tile, splits) table
   size_t tune_saved = 0;
+
+  // LoRA refit: the fp32 pre-merge copy of the 128 attention matrices (taken before merge_lora, ~0.37 GB), every packed buffer derived
+  // from them, and the tensors staged for the next dtp_refit_lora
+  std::unordered_map<std::string, float*> refit_base;  // staged weight name -> base copy (arena)
+  std::vector<RefitTarget> refit_targets;
+  std::vector<RowsumJob> refit_rowsums;                // qkv.lns, q2.lns of every block
+  std::vector<TransposeJob> refit_transposes;          // q2T of every block
+  std::unordered_map<std::string, Staged> refit_staged;
+  void* refit_tables = nullptr;                        // device copy of the three job tables
+  hipEvent_t refit_ev[2] = {nullptr, nullptr};
+  int refit_matrices = -1, refit_launches = 0;         // of the last successful refit (-1: none yet)
+  float refit_ms = 0.f;
 };
 
 // ---- engine.hip
@@ -362,6 +390,14 @@ int load_linear_pair(Ctx* c, const std::string& first, const std::string& second
 int load_linear(Ctx* c, const std::vector<std::string>& names, ConvW& w, bool bias, bool geglu = false,
                 const std::string& fold_ln = std::string());  // fold_ln: name of the LayerNorm feeding this Linear
 int load_plain_f16(Ctx* c, const std::string& name, f16** out);  // unpadded fp16 copy of a matrix
+
+// ---- lora_refit.hip
+// jobs: device table of njobs records.  One launch rewrites every job's rows of its packed buffer; the second writes the folded bias
+// rows of the jobs that carry a beta; max_n / max_k: the largest N / K of the table (grid size)
+int dtp_launch_lora_refit(const LoraRefitJob* jobs, int njobs, int max_n, int max_k, float scale, hipStream_t s);
+int dtp_launch_lora_wbeta(const LoraRefitJob* jobs, int njobs, int max_n, float scale, hipStream_t s);
+int dtp_launch_rowsum_f16_grouped(const RowsumJob* jobs, int njobs, int max_rows, hipStream_t s);
+int dtp_launch_transpose_f16_grouped(const TransposeJob* jobs, int njobs, int max_rows, int max_cols, hipStream_t s);
 
 // per-row (sum, sumsq) partials handed from a producer GEMM (GF_ROWSTATS) to the LayerNorm-folded consumer
 struct RowStats {

@@ -1323,6 +1323,8 @@ void dtp_destroy(dtp_ctx* ctx) {
     if (g.second.graph) (void)hipGraphDestroy(g.second.graph);
   }
   for (auto& s : c->staged) (void)hipFree(s.second.d);
+  for (auto& s : c->refit_staged) (void)hipFree(s.second.d);
+  for (int i = 0; i < 2; ++i) if (c->refit_ev[i]) (void)hipEventDestroy(c->refit_ev[i]);
   for (void* p : c->chunks) (void)hipFree(p);
   for (auto& b : c->pool.blocks) (void)hipFree(b.p);
   for (void* p : c->persistent) (void)hipFree(p);

@@ -46,6 +46,53 @@ static int load_xf(Ctx* c, const std::string& p, XfW& w, int& kv_counter) {
     HIP_CHECK(hipMemsetAsync(pq, 0, (size_t)rows * ld * 2, 0));
     w.q2T = (f16*)pq;
     RC(dtp_launch_transpose_f16(w.q2.w, w.q2.ldw, w.q2T, ld, w.q2.cout, C, 0));
+    c->refit_transposes.push_back({w.q2.w, w.q2T, w.q2.ldw, ld, w.q2.cout, C});
+  }
+  // LoRA refit targets (lora_refit.hip): the eight attention matrices, each with the packed buffer, the row offset inside a stack and the
+  // LayerNorm fold it was loaded with above -- every copy a program reads (xchain_kernel reads out1.w itself; q2T, lns and the folded
+  // biases are derived from the rewritten rows by the kernels that made them here)
+  auto target = [&](const std::string& name, ConvW& cw, int row0, const NormW* fold) -> int {
+    const std::string key = name + ".weight";
+    auto it = c->refit_base.find(key);
+    const Staged* s = ctx_find(c, key);
+    if (it == c->refit_base.end() || !s) { dtp_set_error("LoRA refit: no base copy of '%s'", key.c_str()); return DTP_ERR_MISSING; }
+    RefitTarget rt;
+    rt.name = key;
+    rt.job = LoraRefitJob{};
+    rt.job.base = it->second; rt.job.N = (int)s->shape[0]; rt.job.K = (int)s->shape[1];
+    rt.job.dst = cw.w; rt.job.ldw = cw.ldw; rt.job.row0 = row0;
+    if (fold) { rt.job.gamma = fold->g; rt.job.beta = fold->b; rt.job.wbeta = cw.b + row0; }
+    c->refit_targets.push_back(rt);
+    return DTP_OK;
+  };
+  const int C = w.q2.K;
+  RC(target(t + ".attn1.to_q", w.qkv, 0, &w.ln1));
+  RC(target(t + ".attn1.to_k", w.qkv, C, &w.ln1));
+  RC(target(t + ".attn1.to_v", w.qkv, 2 * C, &w.ln1));
+  RC(target(t + ".attn1.to_out.0", w.out1, 0, nullptr));
+  RC(target(t + ".attn2.to_q", w.q2, 0, &w.ln2));
+  RC(target(t + ".attn2.to_k", w.kv2, 0, nullptr));
+  RC(target(t + ".attn2.to_v", w.kv2, C, nullptr));
+  RC(target(t + ".attn2.to_out.0", w.out2, 0, nullptr));
+  c->refit_rowsums.push_back({w.qkv.w, w.qkv.lns, w.qkv.ldw, w.qkv.K, (w.qkv.cout + 127) / 128 * 128});
+  c->refit_rowsums.push_back({w.q2.w, w.q2.lns, w.q2.ldw, w.q2.K, (w.q2.cout + 127) / 128 * 128});
+  return DTP_OK;
+}
+
+// fp32 copies of the LoRA-targetable matrices as staged, i.e. BEFORE merge_lora adds to them: what dtp_refit_lora rebuilds from
+static int keep_refit_bases(Ctx* c) {
+  for (auto& kv : c->staged) {
+    const std::string& k = kv.first;
+    if (k.rfind("unet.", 0) != 0 || k.find(".transformer_blocks.0.attn") == std::string::npos || kv.second.shape.size() != 2) continue;
+    const size_t n = k.size();
+    const bool proj = (n > 12 && (k.compare(n - 12, 12, ".to_q.weight") == 0 || k.compare(n - 12, 12, ".to_k.weight") == 0 ||
+                                  k.compare(n - 12, 12, ".to_v.weight") == 0)) ||
+                      (n > 16 && k.compare(n - 16, 16, ".to_out.0.weight") == 0);
+    if (!proj) continue;
+    void* p;
+    RC(ctx_arena_alloc(c, kv.second.n * 4, &p));
+    HIP_CHECK(hipMemcpy(p, kv.second.d, kv.second.n * 4, hipMemcpyDeviceToDevice));
+    c->refit_base[k] = (float*)p;
   }
   return DTP_OK;
 }
@@ -79,6 +126,7 @@ static int merge_lora(Ctx* c) {
 }
 
 int load_unet_weights(Ctx* c) {
+  RC(keep_refit_bases(c));
   RC(merge_lora(c));
   struct WsScope {  // the UNet's 3x3 convs also get the fragment-order packing (conv_ws.hip)
     Ctx* c;

@@ -134,6 +134,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self._slots = {}  # conditioning slot -> (image [1,3,R,R], (cond, uncond))
         self.last_times_ms = None
         self._check_finite = False
+        self.lora_scale = 1.0  # of the LoRA the handle holds (set_lora)
 
     # ------------------------------------------------------------------ weights
     def _load(self, nets):
@@ -150,6 +151,39 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
                 check(self._lib.dtp_load_tensor(self._h, f"{net}.{key}".encode(), ptr(t), int(t.is_cuda), shape, t.dim()),
                       f"dtp_load_tensor({net}.{key})")
         check(self._lib.dtp_finalize_weights(self._h), "dtp_finalize_weights")
+
+    def set_lora(self, lora, scale=1.0):
+        """Replace the LoRA of the live handle (the reference's Engine.refit, utilities.py:88-189, with the lora_scale of
+        models.py:1034,1083): every attention projection becomes base + scale * up @ down.  `lora`: a state dict in the key scheme of
+        pytorch_lora_weights.bin, a path for weights.load_checkpoint_file, or None for the base model.  A partial dict is allowed (the
+        modules it leaves out go back to the base model) and its rank may differ from the one the handle was built with; keys and shapes
+        are checked against weights.lora_spec first (ValueError naming the tensor).  Programs, captured graphs, conditioning slots and
+        settings survive; the call blocks until the handle's queued work and the refit have finished (dtp_refit_lora).  Sets
+        `.lora_scale`.  Returns refit_info()."""
+        if isinstance(lora, (str, os.PathLike)):
+            lora = W.load_checkpoint_file(os.fspath(lora))
+        lora = dict(lora) if lora is not None else {}
+        scale = float(scale)
+        W.check_lora_for_refit(lora)
+        self.stream.synchronize()
+        try:
+            for key, t in lora.items():
+                t = t.detach().to(torch.float32).contiguous()
+                shape = (C.c_int64 * t.dim())(*t.shape)
+                check(self._lib.dtp_refit_stage(self._h, f"lora.{key}".encode(), ptr(t), int(t.is_cuda), shape, t.dim()),
+                      f"dtp_refit_stage(lora.{key})")
+        except Exception:
+            self._lib.dtp_refit_lora(self._h, C.c_float(float("nan")))  # drops what was staged; writes nothing
+            raise
+        check(self._lib.dtp_refit_lora(self._h, C.c_float(scale)), "dtp_refit_lora")
+        self.lora_scale = scale
+        return self.refit_info()
+
+    def refit_info(self):
+        """Of the last set_lora: matrices rewritten, kernel launches enqueued, device milliseconds (dtp_last_refit_info)."""
+        m, n, ms = C.c_int(), C.c_int(), C.c_float()
+        check(self._lib.dtp_last_refit_info(self._h, C.byref(m), C.byref(n), C.byref(ms)), "dtp_last_refit_info")
+        return dict(matrices=m.value, launches=n.value, ms=ms.value)
 
     def __del__(self):
         try:

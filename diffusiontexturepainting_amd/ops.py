@@ -72,6 +72,27 @@ def pack_linear_ws(wp, n, k):
     return out
 
 
+def lora_refit(w0, up, down, scale=1.0, gamma=None, out=None, row0=0):
+    """One matrix through the refit kernel: rows row0 .. row0 + N - 1 of `out` = f16((w0 + scale * up @ down) * gamma) in the packed
+    layout.  w0 f32 [N,K], up f32 [N,rank], down f32 [rank,K] (up = down = None: no LoRA), gamma f32 [K] or None; out f16
+    [>= roundup(row0 + N, 128), ldw] (default: a zeroed [roundup(row0 + N, 128), roundup(K, 64)]); rows outside and columns >= K are not
+    written.  Returns out."""
+    lib = _lib.load()
+    n, k = w0.shape
+    if out is None:
+        out = torch.zeros(_up(row0 + n, 128), _up(k, 64), dtype=torch.float16, device=w0.device)
+    if out.dim() != 2 or out.dtype != torch.float16 or out.stride(1) != 1 or out.shape[0] < row0 + n:
+        raise ValueError(f"lora_refit: out must be f16 [>= {row0 + n}, ldw] with unit column stride, got {tuple(out.shape)}")
+    w0 = w0.contiguous().float()
+    rank = 0 if up is None else up.shape[1]
+    up = up.contiguous().float() if up is not None else None
+    down = down.contiguous().float() if down is not None else None
+    gamma = gamma.contiguous().float() if gamma is not None else None
+    check(lib.dtp_op_lora_refit(ptr(w0), ptr(up), ptr(down), rank, float(scale), ptr(gamma), ptr(out), int(row0), n, k, out.stride(0),
+                                _stream()), "lora_refit")
+    return out
+
+
 def rowsum(wp, k):
     """fp32 row sums of packed fp16 weights over the first k columns (the `lns` vector of a LayerNorm-folded GEMM)."""
     lib = _lib.load()

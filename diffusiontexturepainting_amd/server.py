@@ -87,7 +87,7 @@ def torch_to_np(img):
 
 @dataclass
 class _Job:
-    kind: str                      # "brush" | "stamp" | "release" (the slot goes back to the pool)
+    kind: str                      # "brush" | "stamp" | "release" (the slot goes back to the pool) | "refit" (payload = (lora, scale))
     slot: int
     settings: dict
     payload: object                # brush image [3,H,W] f32 / canvas [4,R,R] f32
@@ -247,6 +247,9 @@ class StampQueue:
                 continue
             if job.kind == "release":  # internal bookkeeping of detach(): nothing to answer, nothing to log
                 job.done.set()
+            elif job.kind == "refit":
+                job.error = "RuntimeError: server is shutting down"
+                job.done.set()
             else:
                 self._fail(job, RuntimeError("server is shutting down"))
 
@@ -307,6 +310,27 @@ class StampQueue:
                 logger.error("reply failed: %s", e)
             j.done.set()
 
+    def refit(self, lora, scale=1.0, wait=True):
+        """Replace the model's LoRA (model.set_lora(lora, scale)) on the worker thread, in queue order: stamps submitted before it run
+        on the old weights, stamps after it on the new ones, and no batch straddles it (a refit ends a batch gather like a brush
+        change).  Nothing travels: the wire format is unchanged.  wait=True blocks until it has run and raises RuntimeError with the
+        model's message if it failed; returns the job."""
+        job = self.submit(_Job("refit", -1, {}, (lora, float(scale)), lambda _b: None))
+        if wait:
+            job.done.wait()
+            if job.error:
+                raise RuntimeError(job.error)
+        return job
+
+    def _run_refit(self, job):
+        try:
+            self.model.set_lora(*job.payload)
+            job.done.set()
+        except Exception as e:
+            job.error = f"{type(e).__name__}: {e}"
+            logger.error("LoRA refit failed: %s", job.error)
+            job.done.set()
+
     def _release(self, job):
         with self.lock:
             self.brush_slots.discard(job.slot)
@@ -332,6 +356,9 @@ class StampQueue:
                 continue
             if job.kind == "brush":
                 self._run_brush(job)
+                continue
+            if job.kind == "refit":
+                self._run_refit(job)
                 continue
             # Gather the stamps that are pending right now (plus a short window for stamps that are about to arrive).  Gathering
             # stops at the FIRST request that does not belong to the batch, of any kind: a stamp with other settings, a brush
@@ -387,6 +414,16 @@ class StampServer:
     def close(self):
         for q in self.queues:
             q.close()
+
+    def refit(self, lora, scale=1.0):
+        """Replace the LoRA of EVERY replica (StampQueue.refit): each replica switches between two of its batches.  Blocks until all
+        have; RuntimeError naming the replicas that failed (those keep their old LoRA)."""
+        jobs = [q.refit(lora, scale, wait=False) for q in self.queues]
+        for j in jobs:
+            j.done.wait()
+        bad = [f"replica {i}: {j.error}" for i, j in enumerate(jobs) if j.error]
+        if bad:
+            raise RuntimeError("LoRA refit failed on " + "; ".join(bad))
 
     def on_message(self, client_id, message, write_message, wait=False):
         """Decode one websocket message and enqueue the work; the reply leaves the replica's WORKER thread through `post`

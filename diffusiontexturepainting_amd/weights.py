@@ -421,6 +421,21 @@ def lora_rank_of(lora_sd):
     raise ValueError("no '*_lora.down.weight' tensor in the LoRA file")
 
 
+def check_lora_for_refit(lora_sd):
+    """A LoRA state dict for `MI355ConditionalInpainter.set_lora`: every key must be one of lora_spec()'s (ValueError naming the first
+    strangers) and every tensor must have the spec's shape at the dict's own rank (check_against_spec, naming the first misfits).  A
+    partial dict is allowed: modules it leaves out go back to the base model.  Returns the rank (None for an empty dict)."""
+    if not lora_sd:
+        return None
+    rank = lora_rank_of(lora_sd)
+    spec = lora_spec(rank)
+    unknown = [k for k in lora_sd if k not in spec]
+    if unknown:
+        raise ValueError(f"lora: {len(unknown)} keys that are no LoRA tensor of the UNet (first: {unknown[:3]})")
+    check_against_spec(lora_sd, {k: spec[k] for k in lora_sd}, "lora")
+    return rank
+
+
 def check_against_spec(sd, spec, what):
     missing = [k for k in spec if k not in sd]
     bad = [k for k in spec if k in sd and tuple(sd[k].shape) != tuple(spec[k])]

@@ -20,8 +20,9 @@
 extern "C" {
 #endif
 
-/* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32) are additions; nothing that existed
- * at version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
+/* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32) and the LoRA refit (dtp_refit_stage,
+ * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) are additions; nothing that existed at version 3 changed its signature or
+ * behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
 /* error codes (every entry point returns one; dtp_last_error() has the text) */
@@ -50,6 +51,39 @@ void dtp_destroy(dtp_ctx* ctx);
  * packs everything to the fp16 kernel layouts and builds the launch programs. */
 int dtp_load_tensor(dtp_ctx* ctx, const char* name, const float* data, int is_device, const int64_t* shape, int ndim);
 int dtp_finalize_weights(dtp_ctx* ctx);
+
+/* ---------------------------------------------------------------- LoRA refit of a finalized handle
+ * replaces: Engine.refit (utilities.py:88-189, enable_refit / onnx_refit_dir of stable_diffusion_pipeline.py:203-206,312-327) for the
+ * one set of weights a server swaps at run time, and the lora_scale of the reference's merge, W + lora_scale * up @ down
+ * (models.py:1034,1083).  dtp_load_tensor keeps answering DTP_ERR_STATE after finalize; these two calls are the way in afterwards.
+ *
+ * dtp_refit_stage: stage one tensor of the LoRA to refit with; name = "lora.<module>.processor.<proj>_lora.{down,up}.weight" as for
+ *   dtp_load_tensor; fp32, host or device; only on a finalized handle.  Staging changes nothing a stamp can see.
+ * dtp_refit_lora: replace the handle's LoRA by the staged set at `scale`: every target matrix (q / k / v / out of attn1 and attn2 in the
+ *   16 transformer blocks, 128 matrices) becomes base + scale * up @ down; a target without staged tensors becomes its base; an empty
+ *   staged set = no LoRA.  Clears the staging area, whether the call succeeds or fails.
+ *
+ * Result.  After dtp_refit_lora the handle computes bit for bit what a handle created from (the same base weights, that LoRA with `up`
+ *   pre-multiplied by `scale`) computes, given the same tile choices on both -- through every entry point: stamps of every kind, dtp_unet,
+ *   the fp16 paths at every level.  (Exact when scale * up is: a power of two always is.  Both paths run the same device functions.)
+ * What survives.  Launch programs, tune entries, captured graphs, conditioning slots, schedule tables and options.  The packed buffers are
+ *   overwritten in place, so the pointers inside captured graphs stay valid; the call runs no tuner, builds no program and captures
+ *   nothing.  The per-stamp cross-attention matrices (cached per batch layout, slots and slot versions) are invalidated: the next stamp
+ *   rebuilds them without the caller touching its slots.
+ * Blocking.  The call waits for the work already enqueued on the handle (on any stream), enqueues the refit and waits for it: it is
+ *   host-blocking, like a change of `steps`.
+ * Validation.  Everything is checked before anything is written; a failed call leaves the handle exactly as it was and keeps nothing
+ *   staged.  DTP_ERR_MISSING, naming the tensor, for an `up` without its `down` or a `down` without its `up`; DTP_ERR_ARG, naming the
+ *   tensor, for a name that is no LoRA tensor's, a target that does not exist or a shape that does not fit its target (down [rank, K],
+ *   up [N, rank] for a target [N, K]); DTP_ERR_ARG for a non-finite scale.  The rank may differ from the original LoRA's and from matrix
+ *   to matrix.
+ * State.  DTP_ERR_STATE before dtp_finalize_weights; under any fp8 option (parity-only, calibrated per program: the precedent of
+ *   dtp_stamp_strength); and while the opt-in DTP_GEMMWS fragment-order packing of the Linears is active (that copy is not rebuilt). */
+int dtp_refit_stage(dtp_ctx* ctx, const char* name, const float* data, int is_device, const int64_t* shape, int ndim);
+int dtp_refit_lora(dtp_ctx* ctx, float scale);
+/* of the last successful refit: matrices rewritten, kernel launches it enqueued, device milliseconds (the refit has finished when
+ * dtp_refit_lora returns).  DTP_ERR_STATE when no refit has run on the handle.  Any pointer may be NULL. */
+int dtp_last_refit_info(dtp_ctx* ctx, int* matrices, int* launches, float* ms);
 
 /* ---------------------------------------------------------------- engines (inner boundary)
  * replaces: Engine.infer(feed_dict, stream) for the three TensorRT engines (utilities.py:252-264,
@@ -334,6 +368,12 @@ int dtp_op_quant_e4m3(const void* x, int ldx, void* y, int ldy, int K, float sca
                       int K2, float scale2, int ln2, int M, const float* st_in, int st_parts, float eps, dtp_stream s);
 /* w f32 [N][K] -> out f16 [rows][ldw] (caller zero-fills out); geglu=1 applies the [a|gate] tile packing */
 int dtp_op_pack_linear(const float* w, void* out, int N, int K, int ldw, int geglu, dtp_stream s);
+/* one matrix through lora_refit_kernel (dtp_refit_lora's kernel): out f16 [>= roundup(row0 + N, 128)][ldw], rows row0 .. row0 + N - 1 =
+ * f16((w0 + scale * up @ down) * gamma[k]) (gamma NULL = 1; rank 0 = no LoRA, up / down unused); w0 f32 [N][K], up f32 [N][rank], down
+ * f32 [rank][K]; rows outside and columns >= K are not written.  K % 8 == 0, ldw % 8 == 0, ldw >= K; w0, down, gamma and out 16-byte
+ * aligned.  Waits for the stream once (the launch reads a job record the next call reuses). */
+int dtp_op_lora_refit(const float* w0, const float* up, const float* down, int rank, float scale, const float* gamma, void* out, int row0,
+                      int N, int K, int ldw, dtp_stream s);
 /* w f32 [Cout][Cin][3][3] (or 1x1) -> out f16 [rows][ldw], k = tap*Cin_pad + ci (caller zero-fills out) */
 /* out[r] = sum_k w[r][k] over packed fp16 rows (the `lns` vector of a LayerNorm-folded GEMM) */
 int dtp_op_rowsum(const void* w, int ld, int K, float* out, int rows, dtp_stream s);
