@@ -359,6 +359,7 @@ static __device__ __forceinline__ void dtp_xcd_split(int id, int tiles, int spli
 
 // gemm_kernel tile ids only (dtp_tile(tile).fam == TF_GEMM); dtp_launch_tile takes every family
 int dtp_launch_gemm(const GemmParams& p, int tile, hipStream_t s);
+void dtp_gemm_init();  // raises the dynamic-LDS limit once, outside any stream capture
 int dtp_launch_tile(const GemmParams& p, int tile, hipStream_t s);
 int dtp_launch_splitk_reduce(const GemmParams& p, hipStream_t s);
 size_t dtp_gemm_workspace_bytes(const GemmParams& p);

@@ -5,6 +5,7 @@
 #include <functional>
 #include <map>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -236,8 +237,22 @@ struct StampGraph {
   int nodes = 0;
   unsigned long long used = 0;  // Ctx::graph_clock at the last replay (LRU of the denoise-loop graphs)
 };
-// Captured denoise-loop graphs kept per context.  A loop graph is keyed by (B, steps, scheduler, start row, the sorted per-stamp tg_evals profile), and
-// batches of stamps with different guidance settings produce many profiles: the least recently replayed one is destroyed beyond this.
+// What a captured stage of a stamp depends on: two calls replay the same graph exactly when every field agrees.  The encode key carries
+// neither the strength value nor the scheduler (read from the parameter block); the fields a stage does not use stay 0.
+struct StageKey {
+  int stage = 0;  // 1 = encode, 2 = denoise loop, 3 = decode
+  int B = 0;
+  int k0 = 0;                                                   // encode: tg rows of the first program
+  bool vae_eps = false, init_image = false, init_eps = false;   // encode: VAE draws used, init-image slab (strength < 1) and its draw
+  int sched = 0, steps = 0, row0 = 0;                           // loop
+  std::vector<int> tg_profile;                                  // loop: tg_evals by rank
+  bool operator<(const StageKey& o) const {
+    return std::tie(stage, B, k0, vae_eps, init_image, init_eps, sched, steps, row0, tg_profile) <
+           std::tie(o.stage, o.B, o.k0, o.vae_eps, o.init_image, o.init_eps, o.sched, o.steps, o.row0, o.tg_profile);
+  }
+};
+// Batches of stamps with different guidance settings produce many loop profiles: beyond this many captured loop graphs per context the
+// least recently replayed one is destroyed.
 constexpr int DTP_LOOP_GRAPH_CAP = 16;
 
 // Device parameter block the captured stamp kernels read.  The per-stamp part is written by a kernel whose ARGUMENTS carry the
@@ -340,7 +355,7 @@ struct Ctx {
   int fp8_nslots = 0;
   bool calibrating = false;
   bool finite_pending = false;    // the last stamp ran the check; dtp_last_stamp_finite reads the flag
-  std::map<std::vector<long long>, StampGraph> graphs;  // key[0]: stage and batch; the loop stage appends the tg_evals profile
+  std::map<StageKey, StampGraph> graphs;  // captured stamp stages (graph_run / graphs_drop below)
   unsigned long long graph_clock = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   int last_evals = 0, last_nodes = 0, last_unet_rows = 0;
@@ -408,6 +423,7 @@ struct RowStats {
 };
 
 // ---- builder helpers (engine.hip): every function appends ops to `prog` and returns planned buffers
+void prog_push(Ctx* c, Prog* prog, int kind, double flops, double bytes, Op fn, const std::string& label);
 int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg, RowStats* emit = nullptr);
 
 struct Builder {
@@ -455,6 +471,14 @@ int build_vae_enc_prog(Ctx* c, int B, VaeEncProg& p);
 int build_vae_dec_prog(Ctx* c, int B, VaeDecProg& p);
 int load_unet_weights(Ctx* c);
 int load_vae_weights(Ctx* c);
+int load_imgenc_weights(Ctx* c);
+// the cached program of a batch, built on first use (unet.hip, vae.hip)
+int get_unet_prog(Ctx* c, int N, int dupB, UNetProg** out);
+int get_enc_prog(Ctx* c, int B, VaeEncProg** out);
+int get_dec_prog(Ctx* c, int B, VaeDecProg** out);
+int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s, const float* eps3 = nullptr,
+                      int n_eps = -1);
+int launch_post_quant(Ctx* c, const float* z, int nhwc, float in_scale, f16* out, int B, hipStream_t s);
 int ensure_ws(Ctx* c);
 int ensure_w8(Ctx* c, ConvW& w);
 // fp8 calibration: new scale / amax-slot pair for a Linear (returns the scale's address, sets *slot1), and the pass itself
@@ -464,8 +488,62 @@ void tune_cache_load(Ctx* c);
 void tune_cache_save(Ctx* c);
 int ensure_temb(Ctx* c, const std::vector<float>& timesteps);  // fills temb_table rows 0..n-1
 
-// ---- stamp.hip
+// ---- context.hip
 int stamp_init(Ctx* c);
+
+// ---- schedule.hip
+int sched_evals(int scheduler, int steps);  // UNet evaluations of a full (strength 1) stamp
+
+// ---- the captured stages of a stamp (Ctx::graphs).  Neither drop waits for the device: a caller whose graphs may still be replaying
+// synchronises first.
+template <class P>
+void graphs_drop(Ctx* c, P pred) {
+  for (auto g = c->graphs.begin(); g != c->graphs.end();) {
+    if (!pred(g->first)) { ++g; continue; }
+    if (g->second.exec) (void)hipGraphExecDestroy(g->second.exec);
+    if (g->second.graph) (void)hipGraphDestroy(g->second.graph);
+    g = c->graphs.erase(g);
+  }
+}
+inline void graphs_drop_all(Ctx* c) { graphs_drop(c, [](const StageKey&) { return true; }); }
+
+// run `body` on stream s, replaying a captured hipGraph when possible.  Of the denoise-loop graphs the context keeps the
+// DTP_LOOP_GRAPH_CAP most recently replayed
+template <class F>
+int graph_run(Ctx* c, const StageKey& key, hipStream_t s, F body) {
+  if (!c->use_graph || c->profile || s == nullptr) return body(s);
+  auto it = c->graphs.find(key);
+  if (it == c->graphs.end()) {
+    if (key.stage == 2) {
+      int n = 0;
+      const std::pair<const StageKey, StampGraph>* lru = nullptr;
+      for (const auto& g : c->graphs) {
+        if (g.first.stage != 2) continue;
+        ++n;
+        if (!lru || g.second.used < lru->second.used) lru = &g;
+      }
+      if (n >= DTP_LOOP_GRAPH_CAP) {  // (rare: a new profile; its capture costs far more than this wait)
+        HIP_CHECK(hipDeviceSynchronize());  // the evicted graph may still be replaying
+        graphs_drop(c, [lru](const StageKey& k) { return &k == &lru->first; });
+      }
+    }
+    StampGraph g;
+    HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = body(s);
+    hipError_t e = hipStreamEndCapture(s, &g.graph);
+    if (rc != DTP_OK) { if (g.graph) (void)hipGraphDestroy(g.graph); return rc; }
+    if (e != hipSuccess) { dtp_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return DTP_ERR_HIP; }
+    size_t n = 0;
+    (void)hipGraphGetNodes(g.graph, nullptr, &n);
+    g.nodes = (int)n;
+    HIP_CHECK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+    it = c->graphs.emplace(key, g).first;
+  }
+  it->second.used = ++c->graph_clock;
+  c->last_nodes += it->second.nodes;
+  HIP_CHECK(hipGraphLaunch(it->second.exec, s));
+  return DTP_OK;
+}
 
 // ---- noise.hip: the draws of a seeded stamp call (dtp_stamp_seeded).  Job j < nd writes draw `draw[j]` of every stamp b < B, generated
 // from seed[b], to dst[j] + b * 4 Q (Q = h w counters of four floats each); the seeds travel as a kernel argument, like PadArgs.

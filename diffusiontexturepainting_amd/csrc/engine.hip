@@ -1,4 +1,4 @@
-// Engine core: context lifecycle, weight staging + packing, static buffer planning, op builder.
+// Engine core: weight staging + packing, static buffer planning, op builder.
 #include "engine.h"
 
 #include <math.h>
@@ -11,7 +11,6 @@
 
 static size_t up_to(size_t x, size_t m) { return (x + m - 1) / m * m; }
 static Op make_gemm_op(Ctx* c, GemmParams p, int tile, int bias_step_off);
-void prog_push(Ctx* c, Prog* prog, int kind, double flops, double bytes, Op fn, const std::string& label);
 
 // ---------------------------------------------------------------- memory
 int ctx_arena_alloc(Ctx* c, size_t bytes, void** out) {
@@ -325,11 +324,7 @@ int ensure_ws(Ctx* c) {
   HIP_CHECK(hipMalloc(&c->ws, c->ws_need));
   c->ws_bytes = c->ws_need;
   // captured graphs hold the old workspace pointer: drop them, they are re-captured on next use
-  for (auto& g : c->graphs) {
-    if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    if (g.second.graph) (void)hipGraphDestroy(g.second.graph);
-  }
-  c->graphs.clear();
+  graphs_drop_all(c);
   return DTP_OK;
 }
 
@@ -640,7 +635,6 @@ int Builder::ln(const T& x, const NormW& n, T& y) {
   return DTP_OK;
 }
 
-void prog_push(Ctx* c, Prog* prog, int kind, double flops, double bytes, Op fn, const std::string& label);
 static void tune_read_file(Ctx* c, const char* path) {
   FILE* f = fopen(path, "r");
   if (!f) return;
@@ -1276,79 +1270,3 @@ int Builder::resnet(const T& x, const ResW& w, float eps, bool temb, T& y, const
   release(h);
   return DTP_OK;
 }
-
-// ---------------------------------------------------------------- C ABI: lifecycle + weights
-extern "C" {
-
-int dtp_create(int device, int resolution, int max_batch, dtp_ctx** out) {
-  if (!out || resolution < 64 || resolution % 8 || max_batch < 1 || max_batch > 64) {
-    dtp_set_error("dtp_create: resolution must be a multiple of 8 and at least 64, 1 <= max_batch <= 64 (got resolution %d, max_batch %d)", resolution, max_batch);
-    return DTP_ERR_ARG;
-  }
-  HIP_CHECK(hipSetDevice(device));
-  Ctx* c = new Ctx();
-  c->device = device; c->R = resolution; c->h = resolution / 8; c->maxB = max_batch;
-  hipDeviceProp_t prop;
-  HIP_CHECK(hipGetDeviceProperties(&prop, device));
-  c->num_cu = prop.multiProcessorCount;
-  void* z;
-  HIP_CHECK(hipMalloc(&z, 4096));
-  HIP_CHECK(hipMemset(z, 0, 4096));
-  c->zero = (f16*)z;
-  for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventCreate(&c->ev[i]));
-  tune_cache_load(c);
-  // the switches that shape a launch program (engine.h), read per context: set, and not "0"
-  auto on = [](const char* name) { const char* e = getenv(name); return e && e[0] && e[0] != '0'; };
-  c->fuse_reduce_gn = !on("DTP_NO_FUSE_REDUCE_GN"); c->dedupe_prefix = !on("DTP_NO_DEDUPE");
-#ifdef DTP_EXPERIMENTAL
-  c->fuse_gn_conv = on("DTP_GN_CONV");
-#endif
-  c->fuse_xattn = !on("DTP_NO_XATTN"); c->fold_gn_linear = !on("DTP_NO_FOLD_GN");
-  c->conv_ws = !on("DTP_NO_WS"); c->conv_ws_vae = !on("DTP_NO_WS_VAE"); c->gemm_ws = on("DTP_GEMMWS");
-  c->gn_epilogue = !on("DTP_NO_GN_EPILOGUE"); c->reduce_in_concat_gn = !on("DTP_NO_REDUCE_IN_CONCAT_GN"); c->gna_lnlin = !on("DTP_NO_GNA_LNLIN");
-  c->tune_lnlin = !on("DTP_NO_LNLIN"); c->tune_halo3 = !on("DTP_NO_HALO3");
-  c->xchain = !on("DTP_NO_XCHAIN"); c->xattn_tiles = !on("DTP_XATTN_CT1");
-  if (const char* e = getenv("DTP_FFCHAIN")) c->ffchain = atoi(e);
-  *out = (dtp_ctx*)c;
-  return DTP_OK;
-}
-
-void dtp_destroy(dtp_ctx* ctx) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  (void)hipDeviceSynchronize();
-  for (auto& g : c->graphs) {
-    if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
-    if (g.second.graph) (void)hipGraphDestroy(g.second.graph);
-  }
-  for (auto& s : c->staged) (void)hipFree(s.second.d);
-  for (auto& s : c->refit_staged) (void)hipFree(s.second.d);
-  for (int i = 0; i < 2; ++i) if (c->refit_ev[i]) (void)hipEventDestroy(c->refit_ev[i]);
-  for (void* p : c->chunks) (void)hipFree(p);
-  for (auto& b : c->pool.blocks) (void)hipFree(b.p);
-  for (void* p : c->persistent) (void)hipFree(p);
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->zero) (void)hipFree(c->zero);
-  if (c->tune_thrash) (void)hipFree(c->tune_thrash);
-  for (int i = 0; i < 4; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  delete c;
-}
-
-int dtp_load_tensor(dtp_ctx* ctx, const char* name, const float* data, int is_device, const int64_t* shape, int ndim) {
-  Ctx* c = (Ctx*)ctx;
-  if (!c || !name || !data || ndim < 1 || ndim > 4) { dtp_set_error("dtp_load_tensor: bad argument"); return DTP_ERR_ARG; }
-  if (c->finalized) { dtp_set_error("dtp_load_tensor: weights already finalized"); return DTP_ERR_STATE; }
-  HIP_CHECK(hipSetDevice(c->device));
-  Staged s;
-  s.n = 1;
-  for (int i = 0; i < ndim; ++i) { s.shape.push_back(shape[i]); s.n *= (size_t)shape[i]; }
-  HIP_CHECK(hipMalloc(&s.d, std::max<size_t>(s.n * 4, 16)));
-  HIP_CHECK(hipMemcpy(s.d, data, s.n * 4, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-  auto it = c->staged.find(name);
-  if (it != c->staged.end()) { (void)hipFree(it->second.d); c->staged.erase(it); }
-  c->staged.emplace(name, std::move(s));
-  return DTP_OK;
-}
-
-}  // extern "C"

@@ -245,8 +245,7 @@ __global__ void vae_sample_kernel(const float* __restrict__ mom, const float* __
   }
 }
 
-int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s, const float* eps3 = nullptr,
-                      int n_eps = -1) {
+int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s, const float* eps3, int n_eps) {
   const int HW = c->h * c->h;
   const int blocks = std::min((B * HW + 255) / 256, 2048);
   if (n_eps < 0) n_eps = B;

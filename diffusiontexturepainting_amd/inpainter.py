@@ -251,14 +251,18 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         strength = check_strength_args(strength, init_eps, B, h)
         seeded = check_seed_args(seeds, B, latents, vae_eps, init_eps, strength)
         s = {**DEFAULT_SETTINGS, **{k: v for k, v in settings.items() if k in DEFAULT_SETTINGS}}
-        st = Settings(int(s["steps"]), int(s["context_pad"]), int(s["tg_steps"]), float(s["cfg_weight"]), float(s["tg_weight"]),
-                      int(composite), int(output_u8))  # numpy scalars are cast here (server_io.py:104-119)
+
+        def setting(e):  # numpy scalars are cast here (server_io.py:104-119)
+            return Settings(int(e["steps"]), int(e["context_pad"]), int(e["tg_steps"]), float(e["cfg_weight"]), float(e["tg_weight"]),
+                            int(composite), int(output_u8))
+
+        st = setting(s)  # what dtp_stamp / dtp_stamp_slots take; the other entry points take `each`, one per stamp
         if per_stamp is not None:
             if len(per_stamp) != B:
                 raise ValueError(f"{len(per_stamp)} per_stamp entries for {B} stamps")
-            each = [{**s, **{k: v for k, v in d.items() if k in DEFAULT_SETTINGS}} for d in per_stamp]
-            st = (Settings * B)(*[Settings(int(e["steps"]), int(e["context_pad"]), int(e["tg_steps"]), float(e["cfg_weight"]),
-                                           float(e["tg_weight"]), int(composite), int(output_u8)) for e in each])
+            each = (Settings * B)(*[setting({**s, **{k: v for k, v in d.items() if k in DEFAULT_SETTINGS}}) for d in per_stamp])
+        else:
+            each = (Settings * B)(*([st] * B))
         if seeded is not None:  # the library draws: self.generator is not touched
             latents, vae_eps, init_eps = None, False, False
         if latents is None and seeded is None:
@@ -275,24 +279,19 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
         if slots is not None and len(slots) != B:
             raise ValueError(f"{len(slots)} slots for {B} stamps")
-        if seeded is not None:  # one settings array, like strength: dtp_stamp_seeded is dtp_stamp_strength with the library's own draws
-            each = st if per_stamp is not None else (Settings * B)(*([st] * B))
-            arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
+        arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
+        if seeded is not None:  # dtp_stamp_seeded is dtp_stamp_strength with the library's own draws
             check(self._lib.dtp_stamp_seeded(self._h, ptr(canvas), each, (C.c_uint64 * B)(*seeded[0]), int(seeded[1]), C.c_double(strength),
                                              ptr(out), B, arr, self._s()), "dtp_stamp_seeded")
-        elif strength < 1.0:  # strength is per call: one settings array (per_stamp's, or `settings` for every stamp)
-            each = st if per_stamp is not None else (Settings * B)(*([st] * B))
-            arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
+        elif strength < 1.0:  # strength is per call
             check(self._lib.dtp_stamp_strength(self._h, ptr(canvas), each, ptr(latents), ptr(vae_eps), ptr(init_eps), C.c_double(strength),
                                                ptr(out), B, arr, self._s()), "dtp_stamp_strength")
         elif per_stamp is not None:
-            arr = (C.c_int * B)(*[int(v) for v in slots]) if slots is not None else None
-            check(self._lib.dtp_stamp_mixed(self._h, ptr(canvas), st, ptr(latents), ptr(vae_eps), ptr(out), B, arr, self._s()),
+            check(self._lib.dtp_stamp_mixed(self._h, ptr(canvas), each, ptr(latents), ptr(vae_eps), ptr(out), B, arr, self._s()),
                   "dtp_stamp_mixed")
         elif slots is None:
             check(self._lib.dtp_stamp(self._h, ptr(canvas), C.byref(st), ptr(latents), ptr(vae_eps), ptr(out), B, self._s()), "dtp_stamp")
         else:
-            arr = (C.c_int * B)(*[int(v) for v in slots])
             check(self._lib.dtp_stamp_slots(self._h, ptr(canvas), C.byref(st), ptr(latents), ptr(vae_eps), ptr(out), B, arr, self._s()),
                   "dtp_stamp_slots")
         torch.cuda.current_stream(self._device).wait_stream(self.stream)

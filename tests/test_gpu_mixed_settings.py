@@ -139,6 +139,50 @@ def test_more_profiles_than_the_graph_cache_holds(env, four_slots):
     assert torch.equal(got, first)  # the first profile, evicted and captured again
 
 
+def _every_stamp_path(m, canvas, lat, eps, init_eps):
+    """One stamp through each kind of call (B = 2, 4 steps): [(output, graph nodes)].  Ends on the DDIM sampler it starts with."""
+    kw = dict(latents=lat, vae_eps=eps, slots=[0, 1], steps=4)
+    seeded = dict(slots=[0, 1], steps=4, seeds=7)
+    calls = [lambda: m.generate_raw(canvas, **kw),
+             lambda: m.generate_raw(canvas, per_stamp=[dict(tg_steps=1), dict(tg_steps=3)], **kw),
+             lambda: m.generate_raw(canvas, strength=0.5, init_eps=init_eps, **kw),
+             lambda: m.generate_raw(canvas, strength=0.5, init_eps=False, **dict(kw, vae_eps=False)),
+             lambda: m.generate_raw(canvas, **seeded),
+             lambda: m.generate_raw(canvas, strength=0.5, **seeded)]
+    got = []
+    try:
+        for i in range(8):
+            if i >= 6:
+                m.set_scheduler("DPM" if i == 6 else "DDIM")
+            out = calls[i if i < 6 else 0]().cpu()
+            got.append((out, m.stamp_info()["graph_nodes"]))
+    finally:
+        m.set_scheduler("DDIM")
+    return got
+
+
+def test_call_kinds_on_one_handle_do_not_share_captured_stages(env, four_slots):
+    """Plain, per_stamp, strength < 1 with and without its draws, seeded, seeded below strength 1 and a sampler switch, twice through on
+    one handle: a captured encode or loop stage replayed for a call of another kind would give other numbers than the first pass and
+    than the same calls without graphs."""
+    m = env["model"]
+    _, canvas, lat, eps = four_slots
+    canvas, lat, eps = canvas[:2], lat[:2], eps[:, :2]
+    init_eps = torch.randn(2, 4, R // 8, R // 8, generator=torch.Generator().manual_seed(11))
+    first = _every_stamp_path(m, canvas, lat, eps, init_eps)
+    second = _every_stamp_path(m, canvas, lat, eps, init_eps)
+    try:
+        m.set_option("use_graph", 0)
+        eager = _every_stamp_path(m, canvas, lat, eps, init_eps)
+    finally:
+        m.set_option("use_graph", 1)
+    for i, ((a, na), (b, nb), (e, _)) in enumerate(zip(first, second, eager)):
+        assert torch.isfinite(a).all(), i
+        assert torch.equal(b, a), f"call {i}: the second pass differs from the first"
+        assert torch.equal(e, a), f"call {i}: graph replay differs from eager"
+        assert nb == na and na > 0, (i, na, nb)
+
+
 def test_dilation_with_one_pad_per_image(env):
     from diffusiontexturepainting_amd import ops
     from oracle import pipeline
