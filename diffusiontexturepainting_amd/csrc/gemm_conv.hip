@@ -490,6 +490,10 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
   }
 
   __syncthreads();  // all waves finished reading the last stage (KH = 2: the exchange tile) before it is reused as staging
+  // The staging tile is fp16 ON PURPOSE (half the LDS of an fp32 tile: it fits in the pipeline buffers of every shape): an unsplit launch
+  // rounds its accumulators to fp16 HERE, before bias / residual / activation are added in fp32 -- also with GF_OUT_F32, whose output
+  // therefore carries fp16 precision unless the launch is split (the slabs above are fp32).  DESIGN.md section 4; tests/test_gpu_exact.py
+  // bounds its unsplit cases to |accumulator| <= 2048 for this reason.
   f16* stg = (f16*)smem;
   if (kh == 0)
 #pragma unroll
