@@ -30,6 +30,18 @@ class Settings(C.Structure):
                 ("tg_weight", C.c_float), ("composite", C.c_int), ("output_u8", C.c_int)]
 
 
+STROKE_MODES = {"inpaint": 0, "erase": 1, "overpaint": 2}  # DTP_STROKE_*: the Kit app's brush modes (manager.py:70)
+
+
+class StrokeStamp(C.Structure):  # dtp_stroke_stamp
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("mode", C.c_int), ("slot", C.c_int), ("seed", C.c_uint64)]
+
+
+class StrokeOpts(C.Structure):  # dtp_stroke_opts
+    _fields_ = [("wrap", C.c_int), ("margin", C.c_int), ("over_y", C.c_int), ("over_x", C.c_int), ("max_group", C.c_int),
+                ("sample_vae", C.c_int), ("strength", C.c_double)]
+
+
 class ProfRow(C.Structure):
     _fields_ = [("kind", C.c_int), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -141,6 +153,11 @@ SYMBOLS = {
     "dtp_refit_lora": (_i, [_vp, _f]),
     "dtp_last_refit_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f)]),
     "dtp_op_lora_refit": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "dtp_stroke": (_i, [_vp, _vp, _i, _i, C.POINTER(StrokeStamp), _i, C.POINTER(Settings), C.POINTER(StrokeOpts), _vp, _vp]),
+    "dtp_stroke_plan": (_i, [_i, _i, _i, _i, C.POINTER(StrokeStamp), _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "dtp_last_stroke_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "dtp_op_stroke_gather": (_i, [_vp, _i, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _vp]),
+    "dtp_op_stroke_paste": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _vp]),
 }
 
 

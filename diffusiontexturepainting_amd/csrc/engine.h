@@ -359,6 +359,8 @@ struct Ctx {
   unsigned long long graph_clock = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   int last_evals = 0, last_nodes = 0, last_unet_rows = 0;
+  std::map<int, unsigned char*> stroke_masks;  // dtp_stroke: the default paste mask make_stamp_mask(R, margin) by margin, u8 [R][R]
+  int last_stroke_stamps = -1, last_stroke_groups = 0, last_stroke_evals = 0;  // of the last dtp_stroke (-1: none yet)
   bool use_graph = true;
   bool exec_imgenc_ready = false;
   bool profile = false;

@@ -7,7 +7,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "engine.h"
+#include "stamp.h"
 #include <dlfcn.h>
 
 // roctx ranges around the stages of a stamp (host side, like the reference's NVTX ranges: stable_diffusion_pipeline.py:358-366), so that
@@ -41,8 +41,7 @@ struct RoctxRange {
 namespace {
 
 // separable flat dilation (kornia.morphology.dilation with ones(pad,pad), geodesic border), each stamp with its own pad:
-// out[i] = max over [i - lo[b], i + hi[b]] clipped to the image, lo = pad/2, hi = pad - pad/2 - 1.
-struct PadArgs { int lo[DTP_STAMP_MAXB], hi[DTP_STAMP_MAXB]; };
+// out[i] = max over [i - lo[b], i + hi[b]] clipped to the image, lo = pad/2, hi = pad - pad/2 - 1 (PadArgs, stamp.h).
 __global__ void dilate_row_kernel(const float* __restrict__ canvas, float* __restrict__ tmp, int B, int R, PadArgs pa) {
   const long long total = (long long)B * R * R;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -228,7 +227,7 @@ __global__ void step_kernel(const float* __restrict__ eps_out, float* __restrict
 }
 
 // inpaint_pipeline.py:148 clamp, optional alpha composite (model_base.py:56-58) and the truncating
-// u8 conversion (handler.py:55-56).
+// u8 conversion (handler.py:55-56); finish_value / finish_u8: stamp.h, shared with the stroke's paste.
 __global__ void finish_kernel(const float* __restrict__ dec, const float* __restrict__ canvas, void* __restrict__ out, int B,
                               int HW, int composite, int u8) {
   const long long total = (long long)B * HW;
@@ -237,9 +236,9 @@ __global__ void finish_kernel(const float* __restrict__ dec, const float* __rest
     const float a = composite ? canvas[((size_t)b * 4 + 3) * HW + pix] : 0.f;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-      float v = fminf(fmaxf(dec[i * 4 + ch] / 2.0f + 0.5f, 0.f), 1.f);
+      float v = finish_value(dec[i * 4 + ch]);
       if (composite) v = canvas[((size_t)b * 4 + ch) * HW + pix] * a + v * (1.0f - a);
-      if (u8) ((unsigned char*)out)[i * 3 + ch] = (unsigned char)(v * 255.0f);
+      if (u8) ((unsigned char*)out)[i * 3 + ch] = finish_u8(v);
       else ((float*)out)[((size_t)b * 3 + ch) * HW + pix] = v;
     }
   }
@@ -258,8 +257,7 @@ __global__ void build_ctx_kernel(const float* __restrict__ cond_slots, const int
   }
 }
 
-struct SlotArgs { int s[64]; };
-// the per-stamp slot ids travel as a kernel argument (no host staging buffer to keep alive, no sync)
+// the per-stamp slot ids travel as a kernel argument (SlotArgs, stamp.h)
 __global__ void set_slots_kernel(int* __restrict__ dst, SlotArgs a, int B) {
   if ((int)threadIdx.x < B) dst[threadIdx.x] = a.s[threadIdx.x];
 }
@@ -396,37 +394,8 @@ int dtp_op_dilate(const float* canvas, float* tmp, float* out, int B, int R, int
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- one plan per stamp call
-// The entry points fill the first part; stamp_plan, which owns every argument check, resolves the rest; the stages only read it.
-struct StampPlan {
-  // the call (st, slot_ids: [B]; slot_ids null: slot 0 for every stamp)
-  const float* canvas = nullptr;
-  const dtp_settings* st = nullptr;
-  void* out = nullptr;
-  int B = 0;
-  const int* slot_ids = nullptr;
-  double strength = 1.0;
-  // ... and its noise source: the caller's tensors (vae_eps / init_eps null: the distribution means), or with `seeded` one host seed per
-  // stamp, from which the call's draws are generated into the staging buffers (noise.hip), and one switch for all the VAE draws
-  const float *latents = nullptr, *vae_eps = nullptr, *init_eps = nullptr;
-  const uint64_t* seeds = nullptr;
-  bool seeded = false, sample_vae = false;
-  // resolved by stamp_plan
-  bool use_eps = false, use_init = false;  // the encode stage samples the two VAE encodes / the init image's
-  SlotArgs slots = {};
-  PadArgs pads = {};
-  int steps = 0, sched = 0, composite = 0, output_u8 = 0;
-  // the start point: with `init` (strength < 1) x = a z0 + b latents from the init image, and the loop runs rows [row0, row0 + E) of
-  // the (scheduler, steps) tables (the reference index t_start + i, minus steps_offset); E_full: the rows of the whole table
-  bool init = false;
-  float a = 0.f, b = 0.f;
-  int row0 = 0, E = 0, E_full = 0;
-  int tg_evals[DTP_STAMP_MAXB];
-  StampCoefs coef = {};
-  std::vector<int> ks;  // k_i: tg rows of evaluation i
-};
-
-static int stamp_plan(Ctx* c, StampPlan& p) {
+// ---------------------------------------------------------------- one plan per stamp call (StampPlan: stamp.h)
+int stamp_plan(Ctx* c, StampPlan& p) {
   const dtp_settings* st = p.st;
   const int B = p.B;
   if (p.seeded && !p.seeds) { dtp_set_error("dtp_stamp_seeded: seeds is NULL (one uint64 per stamp, host memory)"); return DTP_ERR_ARG; }
@@ -447,7 +416,7 @@ static int stamp_plan(Ctx* c, StampPlan& p) {
     p.row0 = t_start - (c->scheduler == DTP_SCHED_DDIM ? 1 : 0);
     p.a = ab[0]; p.b = ab[1];
   }
-  if (!p.canvas || !st || (!p.latents && !p.seeded) || !p.out || B < 1 || B > c->maxB) { dtp_set_error("dtp_stamp: bad argument (B=%d, max %d)", B, c->maxB); return DTP_ERR_ARG; }
+  if ((!p.canvas && !p.canvas_staged) || !st || (!p.latents && !p.seeded) || (!p.out && !p.paste) || B < 1 || B > c->maxB) { dtp_set_error("dtp_stamp: bad argument (B=%d, max %d)", B, c->maxB); return DTP_ERR_ARG; }
   for (int b = 0; b < B; ++b) {
     const int sl = p.slot_ids ? p.slot_ids[b] : 0;
     if (sl < 0 || sl >= DTP_MAX_SLOTS) { dtp_set_error("dtp_stamp: slot %d of stamp %d outside 0..%d", sl, b, DTP_MAX_SLOTS - 1); return DTP_ERR_ARG; }
@@ -467,6 +436,10 @@ static int stamp_plan(Ctx* c, StampPlan& p) {
   }
   p.pads = pad_args(pads, B);
   p.steps = st[0].steps; p.composite = st[0].composite; p.output_u8 = st[0].output_u8;
+  if (p.paste && (p.composite || p.output_u8)) {
+    dtp_set_error("dtp_stroke: composite=%d output_u8=%d: both must be 0 (the stamps are pasted into the texture)", p.composite, p.output_u8);
+    return DTP_ERR_ARG;
+  }
   p.sched = c->scheduler;
   p.E_full = sched_evals(p.sched, p.steps);
   if (!p.init) p.E = p.E_full;
@@ -591,7 +564,7 @@ static int stamp_encode(Ctx* c, const StampPlan& p, const StampRes& r, hipStream
     if (p.use_eps) HIP_CHECK(hipMemcpyAsync(sb->eps, p.vae_eps, (size_t)2 * B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
     if (p.use_init) HIP_CHECK(hipMemcpyAsync(eps3, p.init_eps, (size_t)B * 4 * HWl * 4, hipMemcpyDeviceToDevice, s));
   }
-  HIP_CHECK(hipMemcpyAsync(c->canvas32, p.canvas, (size_t)B * 4 * HW * 4, hipMemcpyDeviceToDevice, s));
+  if (!p.canvas_staged) HIP_CHECK(hipMemcpyAsync(c->canvas32, p.canvas, (size_t)B * 4 * HW * 4, hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(dilate_row_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, c->canvas32, c->alpha_tmp, B, R, p.pads);
   hipLaunchKernelGGL(dilate_col_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, c->alpha_tmp,
                      c->alpha_tmp + (size_t)c->maxB * HW, B, R, p.pads);
@@ -666,8 +639,11 @@ static int stamp_decode(Ctx* c, const StampPlan& p, const StampRes& r, hipStream
       RC(launch_post_quant(c, c->x32, 1, 1.0f / VAE_SCALE, dec->in8, B, q));
       return dec->main.run(q, 0);
     }));
-    hipLaunchKernelGGL(finish_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, dec->out32, c->canvas32, p.out, B, HW, p.composite,
-                       p.output_u8);
+    if (p.paste)  // a stroke group: straight into the texture, no [B,3,R,R] image in between
+      RC(dtp_launch_stroke_paste(dec->out32, *p.paste, c->R, B, s));
+    else
+      hipLaunchKernelGGL(finish_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, dec->out32, c->canvas32, p.out, B, HW, p.composite,
+                         p.output_u8);
   }
   c->finite_pending = c->check_finite;
   if (c->check_finite) {
@@ -678,10 +654,7 @@ static int stamp_decode(Ctx* c, const StampPlan& p, const StampRes& r, hipStream
   return DTP_OK;
 }
 
-static int stamp_run(dtp_ctx* ctx, StampPlan& p, dtp_stream s_) {
-  Ctx* c = (Ctx*)ctx;
-  hipStream_t s = (hipStream_t)s_;
-  RC(stamp_plan(c, p));
+int stamp_enqueue(Ctx* c, const StampPlan& p, hipStream_t s) {
   HIP_CHECK(hipSetDevice(c->device));
   StampRes r;
   RC(stamp_acquire(c, p, r));
@@ -700,6 +673,11 @@ static int stamp_run(dtp_ctx* ctx, StampPlan& p, dtp_stream s_) {
   RC(stamp_decode(c, p, r, s));
   HIP_CHECK(hipEventRecord(c->ev[3], s));
   return LAUNCH_OK();
+}
+
+static int stamp_run(dtp_ctx* ctx, StampPlan& p, dtp_stream s) {
+  RC(stamp_plan((Ctx*)ctx, p));
+  return stamp_enqueue((Ctx*)ctx, p, (hipStream_t)s);
 }
 
 // ---------------------------------------------------------------- C ABI: the stamp entry points

@@ -70,6 +70,44 @@ def check_seed_args(seeds, B, latents=None, vae_eps=None, init_eps=None, strengt
     return out, vae_eps is not False
 
 
+def _stroke_stamps(positions, seeds=None, modes=None, slots=None):
+    """The dtp_stroke_stamp array of a stroke.  positions: (x, y) per stamp; seeds: as check_seed_args (None: all 0, for planning);
+    modes: None (Inpaint), one mode for all or one per stamp, each a name of _lib.STROKE_MODES or its int (an unknown int is passed
+    on: the library refuses it, naming the stamp); slots: None (slot 0) or one per stamp."""
+    n = len(positions)
+    if n < 1:
+        raise ValueError("a stroke needs at least one position")
+    if modes is None or isinstance(modes, (str, int)):
+        modes = [0 if modes is None else modes] * n
+    if len(modes) != n:
+        raise ValueError(f"{len(modes)} modes for {n} stamps")
+    ids = []
+    for m in modes:
+        if isinstance(m, str):
+            if m.lower() not in _lib.STROKE_MODES:
+                raise ValueError(f"brush mode {m!r} is not one of {', '.join(_lib.STROKE_MODES)}")
+            m = _lib.STROKE_MODES[m.lower()]
+        ids.append(int(m))
+    if slots is not None and len(slots) != n:
+        raise ValueError(f"{len(slots)} slots for {n} stamps")
+    seeds = [0] * n if seeds is None else check_seed_args(seeds, n)[0]
+    arr = (_lib.StrokeStamp * n)()
+    for i, (x, y) in enumerate(positions):
+        arr[i] = _lib.StrokeStamp(int(x), int(y), ids[i], int(slots[i]) if slots is not None else 0, seeds[i])
+    return arr
+
+
+def plan_stroke(positions, H, W, R, modes=None, wrap=False, max_group=1):
+    """The groups dtp_stroke makes of a stroke on an H x W texture with R x R windows (dtp_stroke_plan, host only: needs no GPU): the
+    list group_of, one non-decreasing group id per stamp.  Stamp i joins the current group iff the group has fewer than max_group
+    members, no Erase stamp is involved and its window is disjoint from every window of the group; the order never changes."""
+    arr = _stroke_stamps(positions, modes=modes)
+    n = len(arr)
+    group_of, ng = (C.c_int * n)(), C.c_int()
+    check(_lib.load().dtp_stroke_plan(int(H), int(W), int(R), int(bool(wrap)), arr, n, int(max_group), group_of, C.byref(ng)), "dtp_stroke_plan")
+    return list(group_of)
+
+
 class MI355ConditionalInpainter(ConditionalInpainterBase):
     def __init__(self, resolution, device=0, weights="synthetic", max_batch=1, seed=42, use_graph=True, fp8_attention=None, fp8_linear=None,
                  fp8_operands=None, scheduler="DDIM"):
@@ -135,6 +173,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.last_times_ms = None
         self._check_finite = False
         self.lora_scale = 1.0  # of the LoRA the handle holds (set_lora)
+        self._stroke_seed = (int(seed) & 0xFFFFFFFF) << 32  # paint_stroke(seeds=None) counts up from here
 
     # ------------------------------------------------------------------ weights
     def _load(self, nets):
@@ -331,6 +370,60 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         """Same as generate() but returns the handler's wire image: uint8 HWC, truncated (handler.py:55-56)."""
         return self._stamp(canvas, settings, composite=composite, output_u8=True, slots=slots, per_stamp=per_stamp, strength=strength,
                            init_eps=init_eps, seeds=seeds)
+
+    def plan_stroke(self, positions, H, W, modes=None, wrap=False, max_group=1):
+        """The groups paint_stroke makes of these stamps on an H x W texture: plan_stroke at this model's resolution, with max_group
+        bounded by max_batch as dtp_stroke bounds it."""
+        return plan_stroke(positions, H, W, self._resolution, modes=modes, wrap=wrap, max_group=min(int(max_group), self.max_batch))
+
+    def paint_stroke(self, texture, positions, seeds=None, modes=None, slots=None, wrap=False, margin=0, overpaint_margins=(10, 25),
+                     mask=None, max_group=1, sample_vae=True, strength=1.0, **settings):
+        """Paint a stroke into `texture` (uint8 [H,W,4] RGBA on the model's device, contiguous; painted in place and returned) without a
+        host round trip per stamp: the Kit app's loop (manager.py:229-271) as one dtp_stroke call.  positions: (x, y) per stamp, the
+        top-left texel (column x, row y) of its R x R window; any ints.  seeds: an int s (stamp i gets s + i), one per stamp, or None
+        (an internal counter).  modes: "inpaint" | "erase" | "overpaint" (or 0 | 1 | 2), one for all or one per stamp (manager.py:70).
+        slots: one conditioning slot per stamp.  wrap: window coordinates modulo H and W (a tileable texture stays tileable); otherwise
+        texels outside the texture are unknown to the stamp and never written.  margin: the default paste mask is 1 on
+        [margin, R - margin)^2 (make_stamp_mask); mask: an [R,R] tensor instead, applied where > 0.  overpaint_margins: (rows, columns)
+        of overpaint_canvas.  max_group: up to this many (and max_batch) consecutive stamps with disjoint windows share one batched
+        stamp (plan_stroke); 1 = strictly serial, bit for bit the host loop over generate_u8(composite=False, seeds=[seed]).
+        sample_vae, strength, settings: as generate_raw(seeds=...), for every stamp.  The call only enqueues (dtp_stroke)."""
+        if not self._slots:
+            raise _lib.DtpError("no brush set: call set_brush() first")
+        R = self._resolution
+        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
+                and texture.device == self._device and texture.is_contiguous()):
+            raise ValueError(f"texture must be a contiguous uint8 [H, W, 4] tensor on {self._device} (it is painted in place)")
+        n = len(positions)
+        if seeds is None:
+            seeds = self._stroke_seed
+            self._stroke_seed = (self._stroke_seed + n) & ((1 << 64) - 1)
+        stamps = _stroke_stamps(positions, seeds, modes, slots)
+        strength = check_strength_args(strength, False, n, R // 8)
+        s = {**DEFAULT_SETTINGS, **{k: v for k, v in settings.items() if k in DEFAULT_SETTINGS}}
+        st = Settings(int(s["steps"]), int(s["context_pad"]), int(s["tg_steps"]), float(s["cfg_weight"]), float(s["tg_weight"]), 0, 0)
+        opts = _lib.StrokeOpts(int(bool(wrap)), int(margin), int(overpaint_margins[0]), int(overpaint_margins[1]), int(max_group),
+                               int(bool(sample_vae)), strength)
+        if mask is not None:
+            if tuple(mask.shape) != (R, R):
+                raise ValueError(f"mask must be {R} x {R}, got {tuple(mask.shape)}")
+            mask = (mask.detach().to(self._device) > 0).to(torch.uint8).contiguous()
+        self.stream.wait_stream(torch.cuda.current_stream(self._device))
+        check(self._lib.dtp_stroke(self._h, ptr(texture), texture.shape[0], texture.shape[1], stamps, n, C.byref(st), C.byref(opts),
+                                   ptr(mask), self._s()), "dtp_stroke")
+        torch.cuda.current_stream(self._device).wait_stream(self.stream)
+        for t in (texture, mask):  # keep them alive until the stream has consumed them
+            if t is not None:
+                t.record_stream(self.stream)
+        if self._check_finite and not self.last_stamp_finite():
+            raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
+        return texture
+
+    def stroke_info(self):
+        """Of the last paint_stroke: its stamps, its groups and the UNet evaluations of all groups (dtp_last_stroke_info)."""
+        a, b, e = C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.dtp_last_stroke_info(self._h, C.byref(a), C.byref(b), C.byref(e)), "dtp_last_stroke_info")
+        return dict(stamps=a.value, groups=b.value, unet_evals=e.value)
 
     def stage_times_ms(self):
         """[vae_encoder x2 + pre, denoise loop, vae + post] GPU ms of the last stamp (print_summary, sdp:486-503)."""

@@ -524,3 +524,31 @@ def stamp_noise(seed, draw, n, device=None):
     out = torch.empty(max(int(n), 0), dtype=torch.float32, device=device if device is not None else torch.cuda.current_device())
     check(lib.dtp_op_stamp_noise(C.c_uint64(int(seed)), int(draw), ptr(out), C.c_longlong(int(n)), _stream()), "stamp_noise")
     return out
+
+
+def _windows(xs, ys, modes):
+    B = len(xs)
+    arr = C.c_int * B
+    return B, arr(*[int(v) for v in xs]), arr(*[int(v) for v in ys]), (arr(*[int(v) for v in modes]) if modes is not None else None)
+
+
+def stroke_gather(texture, xs, ys, R, modes=None, wrap=False, over_y=0, over_x=0):
+    """dtp_op_stroke_gather, the gather kernel of dtp_stroke on its own: texture u8 [H,W,4] (device) and B windows with top-left texel
+    (row ys[b], column xs[b]) and DTP_STROKE_* modes[b] -> canvas f32 [B,4,R,R] = texel / 255; 0 outside a non-wrapping texture and in
+    the inner rectangle of an Overpaint window."""
+    lib = _lib.load()
+    B, ax, ay, am = _windows(xs, ys, modes)
+    canvas = torch.empty(B, 4, R, R, dtype=torch.float32, device=texture.device)
+    check(lib.dtp_op_stroke_gather(ptr(texture), texture.shape[0], texture.shape[1], ptr(canvas), int(R), B, ax, ay, am, int(bool(wrap)),
+                                   int(over_y), int(over_x), _stream()), "stroke_gather")
+    return canvas
+
+
+def stroke_paste(dec, mask, texture, xs, ys, modes=None, wrap=False):
+    """dtp_op_stroke_paste, the paste kernel of dtp_stroke on its own: dec f32 [B,R,R,4] (the VAE decoder's working layout; None when
+    every window is an Erase window), mask u8 [R,R], texture u8 [H,W,4] written in place where the mask is > 0.  Returns texture."""
+    lib = _lib.load()
+    B, ax, ay, am = _windows(xs, ys, modes)
+    check(lib.dtp_op_stroke_paste(ptr(dec), ptr(mask), ptr(texture), texture.shape[0], texture.shape[1], mask.shape[0], B, ax, ay, am,
+                                  int(bool(wrap)), _stream()), "stroke_paste")
+    return texture

@@ -20,9 +20,10 @@
 extern "C" {
 #endif
 
-/* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32) and the LoRA refit (dtp_refit_stage,
- * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) are additions; nothing that existed at version 3 changed its signature or
- * behaviour, so a caller built against the earlier header keeps working. */
+/* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32), the LoRA refit (dtp_refit_stage,
+ * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) and the strokes (dtp_stroke, dtp_stroke_plan, dtp_last_stroke_info,
+ * dtp_op_stroke_gather, dtp_op_stroke_paste) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
+ * caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
 /* error codes (every entry point returns one; dtp_last_error() has the text) */
@@ -192,6 +193,53 @@ int dtp_stamp_seeded(dtp_ctx* ctx, const float* canvas, const dtp_settings* st, 
 int dtp_op_stamp_noise(uint64_t seed, int draw, float* out, long long n, dtp_stream s);
 /* Host-only: Philox4x32-10 of one (counter, key), compiled from the function the kernel runs (Random123's known answers hold). */
 int dtp_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+
+/* ---------------------------------------------------------------- strokes on a device-resident texture
+ * replaces: the loop the reference's Kit app runs on the host around every stamp (kit_app/.../python/manager.py:229-271, in 2D: the
+ * window of a stamp is an axis-aligned R x R rectangle of the texture, not a render of a mesh): renderable_texture() = u8 / 255,
+ * generate_raw, (painted.clip(max=1) * 255).to(uint8) written where the stamp mask is > 0, and its three brush modes (:37-45,70).
+ *   texture     u8 [H][W][4] RGBA on the device, 4-byte aligned, H >= R and W >= R; painted in place
+ *   stamps      host dtp_stroke_stamp[n], read before the call returns.  The window of a stamp is the R x R rectangle whose top-left texel
+ *               is (row y, column x); x and y may be any int.  mode: DTP_STROKE_*; slot: the conditioning slot; seed: as dtp_stamp_seeded.
+ *   st          ONE dtp_settings for every stamp of the stroke; composite and output_u8 must be 0
+ *   o           wrap: 1 = coordinates are taken modulo H and W (painting across the border of a tileable texture keeps it tileable);
+ *               0 = texels outside the texture read as 0 in all four channels (alpha 0: unknown, to be inpainted) and are never written.
+ *               margin: the default paste mask is make_stamp_mask(R, margin) (manager.py:42-45), 1 on [margin, R - margin)^2, built once
+ *               per handle and margin.  over_y, over_x: overpaint_canvas's margins (manager.py:37-39; the Kit app's are 10, 25).
+ *               max_group: the largest number of stamps that may share one batched stamp (see dtp_stroke_plan; the handle's max_batch
+ *               bounds it).  sample_vae, strength: as dtp_stamp_seeded, for every stamp.
+ *   paste_mask  device u8 [R][R], applied where > 0; NULL = the default mask of o->margin
+ * Per stamp: the canvas f32 [4][R][R] = window texel / 255 (a real fp32 division) goes straight into the stamp's staging buffer; in mode
+ * OVERPAINT rows [over_y, R - over_y) x columns [over_x, R - over_x) of all four channels are then 0; the stamp runs as dtp_stamp_seeded
+ * runs it; under the mask RGB = the u8 dtp_stamp writes with composite 0 and output_u8 1, (unsigned char)(clamp(v, 0, 1) * 255), and
+ * A = 255.  Texels outside the mask are neither read nor written.  An ERASE stamp runs no stamp: the four channels under the mask become 0
+ * (manager.py:270).
+ * Grouping and order: the stamps are grouped by dtp_stroke_plan with min(o->max_group, max_batch); the call enqueues, group after group in
+ * the caller's order, gather -> ONE stamp call of B = group size -> paste (an ERASE stamp: the paste only).  The stream keeps the groups
+ * ordered, so stamp i + 1 sees what stamp i pasted; the windows of a group are disjoint, so its members neither see each other's result
+ * nor race.  With max_group 1 the result is the host loop over single stamps, bit for bit; a group of k is the B = k stamp call.
+ * Asynchronous like dtp_stamp: the whole stroke is enqueued and the call returns; a change of `steps` still waits once (and the first use
+ * of a margin allocates its mask).  dtp_last_stamp_* and the check_finite verdict describe the last group that ran a stamp.
+ * Validation: everything is checked before anything is enqueued, and a refused call does not touch the texture.  DTP_ERR_ARG, naming the
+ * stamp where there is one: a NULL pointer, H < R or W < R, n < 1, an unknown mode, over_y / over_x outside [1, R/2) with an OVERPAINT
+ * stamp present, margin outside [0, R/2), composite or output_u8 set, a slot outside 0..15, a window entirely outside a non-wrapping
+ * texture.  What dtp_stamp_seeded refuses is refused with its code (an unset slot: DTP_ERR_STATE, naming the stamp; a bad strength;
+ * strength < 1 under an fp8 option). */
+enum { DTP_STROKE_INPAINT = 0, DTP_STROKE_ERASE = 1, DTP_STROKE_OVERPAINT = 2 };
+typedef struct { int x, y, mode, slot; uint64_t seed; } dtp_stroke_stamp;
+typedef struct { int wrap, margin, over_y, over_x, max_group, sample_vae; double strength; } dtp_stroke_opts;
+int dtp_stroke(dtp_ctx* ctx, uint8_t* texture, int H, int W, const dtp_stroke_stamp* stamps, int n, const dtp_settings* st,
+               const dtp_stroke_opts* o, const uint8_t* paste_mask, dtp_stream s);
+/* Host-only: the groups of a stroke, and the contract its batching is held to.  Walking the stamps in order, stamp i joins the current
+ * group in exactly one case: the group has fewer than max_group members, neither i nor the group is an ERASE stamp, and i's window is
+ * disjoint from every window already in the group; otherwise i opens a new group.  The order is never changed.  Two windows are disjoint
+ * iff they are disjoint on x or on y; on an axis, without wrap: |a_i - a_j| >= R; with wrap, on an axis of length L and with
+ * d = (a_i - a_j) mod L: R <= d <= L - R.  group_of: int[n] (non-decreasing group ids from 0); n_groups may be NULL.  max_group <= 1 puts
+ * every stamp in its own group.  DTP_ERR_ARG for a NULL stamps / group_of, n < 1, R < 1, H < R or W < R, an unknown mode (naming the stamp). */
+int dtp_stroke_plan(int H, int W, int R, int wrap, const dtp_stroke_stamp* stamps, int n, int max_group, int* group_of, int* n_groups);
+/* of the last dtp_stroke that was enqueued: its stamps, its groups, and the UNet evaluations summed over the groups that ran a stamp.
+ * DTP_ERR_STATE when no stroke has run on the handle.  Any pointer may be NULL. */
+int dtp_last_stroke_info(dtp_ctx* ctx, int* stamps, int* groups, int* unet_evals);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
@@ -483,6 +531,16 @@ int dtp_op_dilate_pads(const float* canvas, float* tmp, float* out, int B, int R
 int dtp_op_sched_step(int scheduler, const float* eps_out, float* x, float* hist, void* in16, const float* row, const float* next_scale,
                       const float* cfg, const float* tg, const int* rank, int step_index, int B, int hw, int k, dtp_stream s);
 
+/* The two kernels of dtp_stroke on their own, B <= 64 windows per launch: xs, ys, modes host int[B] (modes NULL = all INPAINT), the
+ * top-left texel and DTP_STROKE_* mode of window b; texture u8 [H][W][4] (device, 4-byte aligned), H >= R, W >= R; wrap, over_y, over_x as in
+ * dtp_stroke_opts.  gather: canvas f32 [B][4][R][R] = window texel / 255, 0 outside a non-wrapping texture and in an OVERPAINT window's
+ * inner rectangle.  paste: dec f32 [B][R][R][4] is the VAE decoder's output in its working layout (NHWC, values around -1..1, channel 3
+ * unused; NULL when every window is an ERASE window); under mask u8 [R][R] > 0 the texel becomes (u8(clamp(dec / 2 + 0.5, 0, 1) * 255) x 3,
+ * 255), or 0 x 4 for an ERASE window.  Overlapping windows in ONE paste launch race; dtp_stroke never issues them. */
+int dtp_op_stroke_gather(const uint8_t* texture, int H, int W, float* canvas, int R, int B, const int* xs, const int* ys, const int* modes,
+                         int wrap, int over_y, int over_x, dtp_stream s);
+int dtp_op_stroke_paste(const float* dec, const uint8_t* mask, uint8_t* texture, int H, int W, int R, int B, const int* xs, const int* ys,
+                        const int* modes, int wrap, dtp_stream s);
 #ifdef __cplusplus
 }
 #endif
