@@ -42,6 +42,16 @@ class StrokeOpts(C.Structure):  # dtp_stroke_opts
                 ("sample_vae", C.c_int), ("strength", C.c_double)]
 
 
+class MeshStamp(C.Structure):  # dtp_mesh_stamp
+    _fields_ = [("pos", C.c_float * 3), ("normal", C.c_float * 3), ("prev", C.c_float * 3), ("fov", C.c_float), ("mode", C.c_int),
+                ("slot", C.c_int), ("seed", C.c_uint64)]
+
+
+class MeshStrokeOpts(C.Structure):  # dtp_mesh_stroke_opts
+    _fields_ = [("flip_normals", C.c_int), ("margin", C.c_int), ("over_y", C.c_int), ("over_x", C.c_int), ("sample_vae", C.c_int),
+                ("strength", C.c_double)]
+
+
 class ProfRow(C.Structure):
     _fields_ = [("kind", C.c_int), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -158,6 +168,12 @@ SYMBOLS = {
     "dtp_last_stroke_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "dtp_op_stroke_gather": (_i, [_vp, _i, _i, _vp, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _vp]),
     "dtp_op_stroke_paste": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _vp]),
+    "dtp_mesh_create": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(_vp)]),
+    "dtp_mesh_destroy": (_i, [_vp]),
+    "dtp_mesh_camera": (_i, [C.POINTER(_f * 3), C.POINTER(_f * 3), C.POINTER(_f * 3), _f, C.POINTER(_f * 12)]),
+    "dtp_mesh_stroke": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(MeshStamp), _i, C.POINTER(Settings), C.POINTER(MeshStrokeOpts), _vp, _vp]),
+    "dtp_op_mesh_render": (_i, [_vp, C.POINTER(_f * 12), _f, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dtp_op_mesh_backproject": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
 }
 
 

@@ -18,6 +18,7 @@ int stamp_init(Ctx* c) {
   RC(ctx_persistent(c, (size_t)DTP_MAX_SLOTS * 3 * RR * 4, &p, true)); c->brush32 = (float*)p;
   RC(ctx_persistent(c, 64 * sizeof(int), &p, true)); c->slot_map = (int*)p;
   RC(ctx_persistent(c, 256, &p, true)); c->finite_flag = (int*)p;
+  RC(ctx_persistent(c, RR * 4, &p, true)); c->mesh_face_idx = (int*)p;
   return DTP_OK;
 }
 
@@ -62,6 +63,7 @@ void dtp_destroy(dtp_ctx* ctx) {
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   graphs_drop_all(c);
+  mesh_drop_ctx(c);
   for (auto& s : c->staged) (void)hipFree(s.second.d);
   for (auto& s : c->refit_staged) (void)hipFree(s.second.d);
   for (int i = 0; i < 2; ++i) if (c->refit_ev[i]) (void)hipEventDestroy(c->refit_ev[i]);

@@ -360,7 +360,9 @@ struct Ctx {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   int last_evals = 0, last_nodes = 0, last_unet_rows = 0;
   std::map<int, unsigned char*> stroke_masks;  // dtp_stroke: the default paste mask make_stamp_mask(R, margin) by margin, u8 [R][R]
-  int last_stroke_stamps = -1, last_stroke_groups = 0, last_stroke_evals = 0;  // of the last dtp_stroke (-1: none yet)
+  int last_stroke_stamps = -1, last_stroke_groups = 0, last_stroke_evals = 0;  // of the last dtp_stroke / dtp_mesh_stroke (-1: none yet)
+  int* mesh_face_idx = nullptr;            // dtp_mesh_stroke: i32 [R][R], the face that won each pixel of the current stamp's render (-1: none)
+  unsigned char* mesh_disc = nullptr;      // dtp_mesh_stroke: the Erase stamp's default mask, u8 [R][R] (built at its first use)
   bool use_graph = true;
   bool exec_imgenc_ready = false;
   bool profile = false;
@@ -392,6 +394,7 @@ int ctx_arena_alloc(Ctx* c, size_t bytes, void** out);
 int ctx_pool_get(Ctx* c, size_t bytes, void** out);
 void ctx_pool_put(Ctx* c, void* p);
 int ctx_persistent(Ctx* c, size_t bytes, void** out, bool zero);
+void mesh_drop_ctx(Ctx* c);  // mesh.hip: frees the meshes created on this handle (dtp_destroy)
 const Staged* ctx_find(Ctx* c, const std::string& name);
 int ctx_fetch_host(Ctx* c, const std::string& name, std::vector<float>& out);
 int ctx_upload_f32(Ctx* c, const std::vector<float>& v, float** out);

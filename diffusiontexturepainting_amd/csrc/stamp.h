@@ -1,6 +1,7 @@
 // What the stamp path (stamp.hip) shares with the stroke layer on top of it (stroke.hip): the plan of one stamp call, the kernel-argument
 // records, and the device functions of the output conversion.
 #pragma once
+#include <functional>
 #include <vector>
 
 #include "engine.h"
@@ -38,10 +39,11 @@ struct StampPlan {
   const float *latents = nullptr, *vae_eps = nullptr, *init_eps = nullptr;
   const uint64_t* seeds = nullptr;
   bool seeded = false, sample_vae = false;
-  // the two hooks of a stroke group (dtp_stroke): the canvas is already in Ctx::canvas32 (stroke_gather_kernel wrote it: `canvas` is
-  // unused), and the decoded stamps are pasted into a texture instead of converted into `out` (unused; composite and output_u8 must be 0)
+  // the two hooks of a stroke (dtp_stroke, dtp_mesh_stroke): the canvas is already in Ctx::canvas32 (the stroke's gather or render kernel
+  // wrote it: `canvas` is unused), and the decoded stamps are pasted into a texture instead of converted into `out` (unused; composite and
+  // output_u8 must be 0).  paste: a paste launcher, called with the decoder's output f32 [B][R][R][4], R, B and the stream
   bool canvas_staged = false;
-  const StrokePaste* paste = nullptr;
+  std::function<int(const float* dec, int R, int B, hipStream_t s)> paste;
   // resolved by stamp_plan
   bool use_eps = false, use_init = false;  // the encode stage samples the two VAE encodes / the init image's
   SlotArgs slots = {};
@@ -66,3 +68,5 @@ int dtp_launch_stroke_gather(const unsigned char* texture, int H, int W, float* 
                              int over_y, int over_x, hipStream_t s);
 // dec f32 [B][R][R][4] (the VAE decoder's output, 3 channels used); null: every window is erased
 int dtp_launch_stroke_paste(const float* dec, const StrokePaste& p, int R, int B, hipStream_t s);
+// make_stamp_mask(R, margin) of the handle, u8 [R][R] on the device; the first use of a margin allocates and fills it
+int stroke_default_mask(Ctx* c, int margin, hipStream_t s, const unsigned char** out);

@@ -640,7 +640,7 @@ static int stamp_decode(Ctx* c, const StampPlan& p, const StampRes& r, hipStream
       return dec->main.run(q, 0);
     }));
     if (p.paste)  // a stroke group: straight into the texture, no [B,3,R,R] image in between
-      RC(dtp_launch_stroke_paste(dec->out32, *p.paste, c->R, B, s));
+      RC(p.paste(dec->out32, c->R, B, s));
     else
       hipLaunchKernelGGL(finish_kernel, dim3(nblk((long long)B * HW)), dim3(256), 0, s, dec->out32, c->canvas32, p.out, B, HW, p.composite,
                          p.output_u8);

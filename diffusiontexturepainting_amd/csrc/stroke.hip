@@ -160,7 +160,9 @@ struct StrokeGroup {
   StampPlan plan;
 };
 
-int default_mask(Ctx* c, int margin, hipStream_t s, const unsigned char** out) {
+}  // namespace
+
+int stroke_default_mask(Ctx* c, int margin, hipStream_t s, const unsigned char** out) {
   auto it = c->stroke_masks.find(margin);
   if (it == c->stroke_masks.end()) {
     void* p;
@@ -172,8 +174,6 @@ int default_mask(Ctx* c, int margin, hipStream_t s, const unsigned char** out) {
   *out = it->second;
   return DTP_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -236,7 +236,8 @@ int dtp_stroke(dtp_ctx* ctx, uint8_t* texture, int H, int W, const dtp_stroke_st
     StampPlan& p = g.plan;
     p.st = g.st.data(); p.B = g.k; p.slot_ids = g.slots.data(); p.strength = o->strength;
     p.seeded = true; p.seeds = g.seeds.data(); p.sample_vae = o->sample_vae != 0;
-    p.canvas_staged = true; p.paste = &g.paste;
+    p.canvas_staged = true;
+    p.paste = [&g](const float* dec, int R, int B, hipStream_t q) { return dtp_launch_stroke_paste(dec, g.paste, R, B, q); };
     const int rc = stamp_plan(c, p);
     if (rc) {  // dtp_stamp_seeded's refusal and code, with the stamps it is about
       const std::string why = dtp_last_error();
@@ -248,7 +249,7 @@ int dtp_stroke(dtp_ctx* ctx, uint8_t* texture, int H, int W, const dtp_stroke_st
   // ---- enqueue: per group gather -> one stamp of B = k -> paste; an Erase stamp only pastes.  The stream orders the groups.
   HIP_CHECK(hipSetDevice(c->device));
   const unsigned char* mask = paste_mask;
-  if (!mask) RC(default_mask(c, o->margin, s, &mask));
+  if (!mask) RC(stroke_default_mask(c, o->margin, s, &mask));
   for (StrokeGroup& g : groups) {
     g.paste.mask = mask;
     if (g.erase) { RC(dtp_launch_stroke_paste(nullptr, g.paste, R, g.k, s)); continue; }

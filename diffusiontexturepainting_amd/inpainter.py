@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from . import _lib, weights as W
+from . import _lib, mesh as _mesh, weights as W
 from ._lib import Settings, check, ptr
 from .model_base import ConditionalInpainterBase
 
@@ -70,11 +70,8 @@ def check_seed_args(seeds, B, latents=None, vae_eps=None, init_eps=None, strengt
     return out, vae_eps is not False
 
 
-def _stroke_stamps(positions, seeds=None, modes=None, slots=None):
-    """The dtp_stroke_stamp array of a stroke.  positions: (x, y) per stamp; seeds: as check_seed_args (None: all 0, for planning);
-    modes: None (Inpaint), one mode for all or one per stamp, each a name of _lib.STROKE_MODES or its int (an unknown int is passed
-    on: the library refuses it, naming the stamp); slots: None (slot 0) or one per stamp."""
-    n = len(positions)
+def _stroke_modes(modes, n, slots=None):
+    """The DTP_STROKE_* ids of the n stamps of a stroke (modes: see _stroke_stamps), after the checks every stroke shares."""
     if n < 1:
         raise ValueError("a stroke needs at least one position")
     if modes is None or isinstance(modes, (str, int)):
@@ -90,6 +87,15 @@ def _stroke_stamps(positions, seeds=None, modes=None, slots=None):
         ids.append(int(m))
     if slots is not None and len(slots) != n:
         raise ValueError(f"{len(slots)} slots for {n} stamps")
+    return ids
+
+
+def _stroke_stamps(positions, seeds=None, modes=None, slots=None):
+    """The dtp_stroke_stamp array of a stroke.  positions: (x, y) per stamp; seeds: as check_seed_args (None: all 0, for planning);
+    modes: None (Inpaint), one mode for all or one per stamp, each a name of _lib.STROKE_MODES or its int (an unknown int is passed
+    on: the library refuses it, naming the stamp); slots: None (slot 0) or one per stamp."""
+    n = len(positions)
+    ids = _stroke_modes(modes, n, slots)
     seeds = [0] * n if seeds is None else check_seed_args(seeds, n)[0]
     arr = (_lib.StrokeStamp * n)()
     for i, (x, y) in enumerate(positions):
@@ -411,6 +417,55 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
         check(self._lib.dtp_stroke(self._h, ptr(texture), texture.shape[0], texture.shape[1], stamps, n, C.byref(st), C.byref(opts),
                                    ptr(mask), self._s()), "dtp_stroke")
+        torch.cuda.current_stream(self._device).wait_stream(self.stream)
+        for t in (texture, mask):  # keep them alive until the stream has consumed them
+            if t is not None:
+                t.record_stream(self.stream)
+        if self._check_finite and not self.last_stamp_finite():
+            raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
+        return texture
+
+    def load_mesh(self, vertices, faces, face_uvs):
+        """A mesh on this model's device for paint_mesh_stroke (dtp_mesh_create): vertices [V, 3], faces [F, 3], face_uvs [F, 3, 2]
+        (per face and corner, in 0..1, v up), copied from the host once.  Returns a mesh.Mesh; it lives as long as this model."""
+        return _mesh.Mesh(self._h, vertices, faces, face_uvs, keep=self)
+
+    def paint_mesh_stroke(self, mesh, texture, positions, normals, prev_positions, fov, seeds=None, modes=None, slots=None,
+                          flip_normals=False, margin=1, overpaint_margins=(10, 25), mask=None, sample_vae=True, strength=1.0, **settings):
+        """Paint a stroke on a textured mesh without a host round trip per stamp: TexturePainterManager.stamp (manager.py:199-271) as one
+        dtp_mesh_stroke call.  Per stamp, in order: an orthographic look-at camera from positions[i] + normals[i] at positions[i] with
+        up = prev_positions[i] - positions[i] (mesh_camera), the render of `mesh` with `texture` (uint8 [H,W,4] on the model's device,
+        contiguous; painted in place and returned) into the R x R window, the stamp, and the backprojection of the painted stamp into the
+        texture through the faces the window shows.  fov: half the window's width in world units, one float or one per stamp (the Kit
+        app's fov_distance * fov_scale).  seeds, modes, slots, mask, overpaint_margins, sample_vae, strength, settings: as paint_stroke;
+        margin=1 is the Kit app's stamp mask; an "erase" stamp without `mask` uses the analytic disc.  flip_normals: a left-handed mesh.
+        Strictly serial: stamp i + 1 renders what stamp i painted.  The call only enqueues."""
+        if not self._slots:
+            raise _lib.DtpError("no brush set: call set_brush() first")
+        R = self._resolution
+        if not isinstance(mesh, _mesh.Mesh):
+            raise ValueError("mesh must come from load_mesh()")
+        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
+                and texture.device == self._device and texture.is_contiguous()):
+            raise ValueError(f"texture must be a contiguous uint8 [H, W, 4] tensor on {self._device} (it is painted in place)")
+        n = len(positions)
+        ids = _stroke_modes(modes, n, slots)
+        if seeds is None:
+            seeds = self._stroke_seed
+            self._stroke_seed = (self._stroke_seed + n) & ((1 << 64) - 1)
+        stamps = _mesh.mesh_stamps(positions, normals, prev_positions, fov, check_seed_args(seeds, n)[0], ids, slots)
+        strength = check_strength_args(strength, False, n, R // 8)
+        s = {**DEFAULT_SETTINGS, **{k: v for k, v in settings.items() if k in DEFAULT_SETTINGS}}
+        st = Settings(int(s["steps"]), int(s["context_pad"]), int(s["tg_steps"]), float(s["cfg_weight"]), float(s["tg_weight"]), 0, 0)
+        opts = _lib.MeshStrokeOpts(int(bool(flip_normals)), int(margin), int(overpaint_margins[0]), int(overpaint_margins[1]),
+                                   int(bool(sample_vae)), strength)
+        if mask is not None:
+            if tuple(mask.shape) != (R, R):
+                raise ValueError(f"mask must be {R} x {R}, got {tuple(mask.shape)}")
+            mask = (mask.detach().to(self._device) > 0).to(torch.uint8).contiguous()
+        self.stream.wait_stream(torch.cuda.current_stream(self._device))
+        check(self._lib.dtp_mesh_stroke(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n, C.byref(st),
+                                        C.byref(opts), ptr(mask), self._s()), "dtp_mesh_stroke")
         torch.cuda.current_stream(self._device).wait_stream(self.stream)
         for t in (texture, mask):  # keep them alive until the stream has consumed them
             if t is not None:

@@ -552,3 +552,35 @@ def stroke_paste(dec, mask, texture, xs, ys, modes=None, wrap=False):
     check(lib.dtp_op_stroke_paste(ptr(dec), ptr(mask), ptr(texture), texture.shape[0], texture.shape[1], mask.shape[0], B, ax, ay, am,
                                   int(bool(wrap)), _stream()), "stroke_paste")
     return texture
+
+
+def mesh_render(mesh, camera, fov, texture, R, flip_normals=False, mode=0, over_y=0, over_x=0):
+    """dtp_op_mesh_render, the render half of a dtp_mesh_stroke stamp on its own: mesh a mesh.Mesh, camera the [3, 4] matrix of
+    mesh_camera, texture u8 [H,W,4] (device) -> (canvas f32 [1,4,R,R], face_idx i32 [R,R]).  The mesh keeps the projection for
+    mesh_backproject."""
+    lib = _lib.load()
+    cam = (C.c_float * 12)(*[float(v) for v in torch.as_tensor(camera).reshape(-1).tolist()])
+    canvas = torch.empty(1, 4, R, R, dtype=torch.float32, device=texture.device)
+    face_idx = torch.empty(R, R, dtype=torch.int32, device=texture.device)
+    check(lib.dtp_op_mesh_render(mesh.handle, C.byref(cam), C.c_float(float(fov)), int(bool(flip_normals)), ptr(texture), texture.shape[0],
+                                 texture.shape[1], int(R), int(mode), int(over_y), int(over_x), ptr(canvas), ptr(face_idx), _stream()),
+          "mesh_render")
+    return canvas, face_idx
+
+
+def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None):
+    """dtp_op_mesh_backproject, the other half: through the faces the LAST mesh_render of `mesh` showed (face_idx: that render's), the
+    stamp image is carried into texture u8 [H,W,4] in place where the sampled mask u8 [R,R] * (face_idx != -1) is > 0.  The stamp image
+    is dec f32 [R,R,4] (the VAE decoder's working layout, values around -1..1), or `painted` f32 [3,R,R] / [1,3,R,R] in 0..1 (what
+    generate_raw returns, used as it is); neither: erase.  Returns texture."""
+    lib = _lib.load()
+    finished = painted is not None
+    if finished:
+        if dec is not None:
+            raise ValueError("dec and painted are exclusive")
+        R = face_idx.shape[0]
+        dec = torch.zeros(R, R, 4, dtype=torch.float32, device=texture.device)
+        dec[..., :3] = painted.reshape(3, R, R).permute(1, 2, 0)
+    check(lib.dtp_op_mesh_backproject(mesh.handle, ptr(dec), int(finished), ptr(mask), ptr(face_idx), face_idx.shape[0], ptr(texture),
+                                      texture.shape[0], texture.shape[1], _stream()), "mesh_backproject")
+    return texture

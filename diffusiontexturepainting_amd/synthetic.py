@@ -73,3 +73,37 @@ def make_conditioning(seed):
     """Synthetic [1,14,768] cond / uncond embeddings (used when the brush encoder is bypassed)."""
     g = torch.Generator().manual_seed(seed)
     return torch.randn(1, 14, 768, generator=g), torch.randn(1, 14, 768, generator=g)
+
+
+# ---------------------------------------------------------------- meshes for the mesh strokes (tests/test_gpu_mesh.py, tools/mesh_stroke_timing.py)
+def make_quad():
+    """The square [-1, 1]^2 in the plane z = 0 as two faces whose normal is +z, UVs the unit square (u = (x + 1) / 2, v = (y + 1) / 2):
+    seen from +z with fov 1 it fills the stamp window exactly.  -> vertices f32 [4, 3], faces i32 [2, 3], face_uvs f32 [2, 3, 2]."""
+    v = torch.tensor([[-1.0, -1.0, 0.0], [1.0, -1.0, 0.0], [1.0, 1.0, 0.0], [-1.0, 1.0, 0.0]])
+    f = torch.tensor([[0, 1, 2], [0, 2, 3]], dtype=torch.int32)
+    return v, f, ((v[:, :2] + 1) / 2)[f.long()].contiguous()
+
+
+def make_height_field(nx=17, ny=13, seed=0, bump=0.35):
+    """A bumpy height field over [-1, 1] x [-0.75, 0.75]: nx x ny vertices, 2 (nx - 1)(ny - 1) faces with normals towards +z, and a
+    two-chart UV atlas: the faces left of the middle column fill u in [0.03, 0.47], the others u in [0.53, 0.97] MIRRORED (u falls as x
+    grows); v in [0.05, 0.95] for both.  Seeded, so every caller gets the same mesh.  -> vertices, faces, face_uvs as make_quad."""
+    g = torch.Generator().manual_seed(seed)
+    xs, ys = torch.linspace(-1.0, 1.0, nx, dtype=torch.float64), torch.linspace(-0.75, 0.75, ny, dtype=torch.float64)
+    yy, xx = torch.meshgrid(ys, xs, indexing="ij")
+    zz = bump * (torch.sin(3.1 * xx + 0.4) * torch.cos(2.3 * yy - 0.2) + 0.25 * torch.sin(9.0 * xx * yy))
+    zz = zz + 0.02 * torch.rand(ny, nx, generator=g, dtype=torch.float64)
+    verts = torch.stack([xx, yy, zz], dim=-1).reshape(-1, 3).to(torch.float32)
+    mid = (nx - 1) // 2
+    faces, uvs = [], []
+    for j in range(ny - 1):
+        for i in range(nx - 1):
+            a, b, c, d = j * nx + i, j * nx + i + 1, (j + 1) * nx + i + 1, (j + 1) * nx + i
+
+            def uv(col, row, left=i < mid):
+                s = col / mid if left else (col - mid) / (nx - 1 - mid)
+                return (0.03 + 0.44 * s) if left else (0.97 - 0.44 * s), 0.05 + 0.9 * row / (ny - 1)
+            ua, ub, uc, ud = uv(i, j), uv(i + 1, j), uv(i + 1, j + 1), uv(i, j + 1)
+            faces += [[a, b, c], [a, c, d]]
+            uvs += [[ua, ub, uc], [ua, uc, ud]]
+    return verts, torch.tensor(faces, dtype=torch.int32), torch.tensor(uvs, dtype=torch.float32)

@@ -22,7 +22,8 @@ extern "C" {
 
 /* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32), the LoRA refit (dtp_refit_stage,
  * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) and the strokes (dtp_stroke, dtp_stroke_plan, dtp_last_stroke_info,
- * dtp_op_stroke_gather, dtp_op_stroke_paste) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
+ * dtp_op_stroke_gather, dtp_op_stroke_paste) and the mesh strokes (dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_camera, dtp_mesh_stroke,
+ * dtp_op_mesh_render, dtp_op_mesh_backproject) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
  * caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -240,6 +241,75 @@ int dtp_stroke_plan(int H, int W, int R, int wrap, const dtp_stroke_stamp* stamp
 /* of the last dtp_stroke that was enqueued: its stamps, its groups, and the UNet evaluations summed over the groups that ran a stamp.
  * DTP_ERR_STATE when no stroke has run on the handle.  Any pointer may be NULL. */
 int dtp_last_stroke_info(dtp_ctx* ctx, int* stamps, int* groups, int* unet_evals);
+
+/* ---------------------------------------------------------------- strokes on a textured mesh
+ * replaces: what the reference's Kit app does around every stamp when it paints on a mesh (kit_app/.../python/manager.py:199-271,
+ * util/render.py:22-178): an orthographic look-at camera at the brush, a rasterisation of the mesh into the R x R stamp window with the
+ * texture sampled through the interpolated UVs, generate_raw, and a rasterisation of the visible faces in UV space that carries the
+ * painted stamp back into the texture.  Both rasterisations are kaolin's in the reference.  The contract below was written from kaolin
+ * 0.15's documented conventions (the camera looks down -z, a larger camera z is nearer, NDC y is up, image row 0 is the top,
+ * texture_mapping = bilinear grid_sample with align_corners=False, border padding, v flipped); it was not captured from a kaolin run.
+ *
+ * Camera (dtp_mesh_camera; host only, in double, rounded to fp32 once): eye = pos + normal, up = prev - pos, b = normalize(eye - pos),
+ * r = normalize(cross(up, b)), u = cross(b, r); out = the rows (r, u, b), each followed by t = -row . eye: out[4 k .. 4 k + 2] the row,
+ * out[4 k + 3] its t.  NDC x = cam.x / fov, y = cam.y / fov (OrthographicIntrinsics.from_frustum with width = height).  DTP_ERR_ARG for a
+ * zero normal, an up that is zero or parallel to the normal (sine below 1e-9), a non-finite input, fov <= 0 or not finite, or a camera
+ * that does not fit fp32.
+ * Projection (per face, fp32, every operation rounded once, no contraction): cam_k = ((m0 x + m1 y) + m2 z) + t per row; the normal
+ * cross(v1 - v0, v2 - v0) of the camera-space face, its z divided by its length (negated under flip_normals).  front: that z >= 0; steep:
+ * that z < 0.5.  A face whose camera coordinates or unit normal are not finite (zero area: 0 / 0) is neither front nor rasterised.
+ * Coverage (exact integers): every vertex is snapped to 1/256 pixel, X = rint((ndc_x + 1) * 128 R), Y = rint((1 - ndc_y) * 128 R), clamped
+ * to +-2^26; pixel (row i, column j) has its centre at (256 j + 128, 256 i + 128); the edge functions are int64, both windings are taken
+ * (multiplied by the sign of the area), and the top-left fill rule gives a centre on a shared edge to exactly one face.  kaolin's
+ * coverage is floating point: a deliberate difference of at most 1/256 pixel, which makes coverage reproducible bit for bit.
+ * Interpolation: w_k = (float)E_k / (float)A, an fp32 division; an attribute is (w0 a0 + w1 a1) + w2 a2.  Among the front faces that
+ * cover a centre the winner is the largest (interpolated camera z, -face index): nearer wins, a tie goes to the lower index, whatever
+ * the order of the faces.  face_idx i32 [R][R]: the winner, -1 for none.
+ * Render: where face_idx != -1 the canvas f32 [4][R][R] is the bilinear sample of the texture (texel = byte / 255.0f) at x = u W - 0.5,
+ * y = (1 - v) H - 0.5, clamped to [0, W - 1] x [0, H - 1]: ((t00 gx gy + t01 fx gy) + t10 gx fy) + t11 fx fy with fx = x - floor(x),
+ * gx = 1 - fx.  Where face_idx == -1 it is 0 in all four channels (unknown; the reference samples the texel at uv = (0, 0) there, a quirk
+ * that is not reproduced); an OVERPAINT window is 0 as well in rows [over_y, R - over_y) x columns [over_x, R - over_x).
+ * Backprojection: a face is valid when it is front, not steep and the winner of at least one pixel.  The valid faces are rasterised in
+ * texture space by the same integer rule: X = rint((u W) 256), Y = rint(((1 - v) H) 256), the same clamp, texel centres at
+ * (256 j + 128, 256 i + 128); the lowest valid face index wins.  Its interpolated feature (p, q) = stamp NDC / 2 + 0.5 addresses the stamp
+ * image at x = p R - 0.5, y = (1 - q) R - 0.5 (bilinear, border-clamped, the same expression), whose RGB is the decoder's value clamped
+ * to 0..1 (dtp_stamp's with composite 0) and whose A is (mask[i][j] > 0) * (face_idx[i][j] != -1).  Where the sampled A is > 0, all four
+ * bytes of the texel become (unsigned char)(min(v, 1) * 255.0f) -- alpha included, as manager.py:268 does, so texels at the silhouette get
+ * a partial alpha.  An ERASE stamp runs no stamp and writes 0 to the four channels there.  Texels no valid face covers are neither read
+ * nor written.
+ *
+ * dtp_mesh_create copies host arrays to the device of `ctx`: vertices f32 [V][3], faces i32 [F][3], face_uvs f32 [F][3][2] (UVs in 0..1,
+ * v up), F <= 2^20; with them it allocates the per-face records of a stamp, so a stroke allocates nothing.  DTP_ERR_ARG, before any
+ * device call, for a NULL pointer, V < 1, F outside 1..2^20, an index outside 0..V-1 or a non-finite UV (naming the face), a non-finite
+ * vertex.  A mesh belongs to its handle: dtp_destroy frees the meshes still alive; dtp_mesh_destroy(NULL) is a no-op, and a handle that is
+ * not a live mesh is DTP_ERR_ARG.
+ *
+ * dtp_mesh_stroke: per stamp, in the caller's order, on the one stream and without a host round trip: camera -> render (straight into the
+ * stamp's staging buffer) -> the stamp as dtp_stamp_seeded runs it, B = 1 -> backproject.  Stamp i + 1 renders what stamp i pasted.
+ *   texture     u8 [H][W][4] RGBA on the device, 4-byte aligned, 1 <= H, W <= 32768; painted in place
+ *   stamps      host dtp_mesh_stamp[n]: pos, the brush position on the mesh; normal, the surface normal there (the camera sits at
+ *               pos + normal); prev, the previous brush position (up = prev - pos); fov > 0, half the window's width in world units (the
+ *               Kit app's fov_distance * fov_scale); mode DTP_STROKE_*; slot, seed as in dtp_stroke_stamp
+ *   st          ONE dtp_settings for every stamp; composite and output_u8 must be 0
+ *   o           flip_normals (a left-handed mesh, manager.py:197); margin: the default paste mask make_stamp_mask(R, margin) (the Kit
+ *               app's is 1); over_y, over_x: overpaint_canvas's margins; sample_vae, strength: as dtp_stamp_seeded
+ *   paste_mask  device u8 [R][R], applied where > 0, for every stamp; NULL = make_stamp_mask(R, o->margin), and for an ERASE stamp the
+ *               analytic disc (2 i - (R - 1))^2 + (2 j - (R - 1))^2 <= (R - 4)^2 (the reference draws its circle_mask with PIL)
+ * The call checks everything, then enqueues and returns: no wait (a change of `steps` still waits once, and the first use of a mask
+ * allocates it), no allocation, no copy back.  DTP_ERR_ARG, naming the stamp where there is one: a NULL pointer, a mesh that is not alive
+ * or belongs to another handle, H or W outside 1..32768, n < 1, an unknown mode, margin outside [0, R/2), over_y / over_x outside
+ * [1, R/2) with an OVERPAINT stamp, a slot outside 0..15, a camera dtp_mesh_camera refuses.  What dtp_stamp_seeded refuses is refused with
+ * its code (an unset slot: DTP_ERR_STATE).  A refused call leaves the texture untouched.  A window that the bounding box of the mesh
+ * misses is skipped on the host; a window that meets the box and covers no face still runs its stamp, and pastes nothing.  Neither is an
+ * error.  dtp_last_stroke_info answers for the call: stamps = groups = n, and the UNet evaluations of the stamps that ran. */
+typedef struct dtp_mesh dtp_mesh;
+typedef struct { float pos[3], normal[3], prev[3], fov; int mode, slot; uint64_t seed; } dtp_mesh_stamp;
+typedef struct { int flip_normals, margin, over_y, over_x, sample_vae; double strength; } dtp_mesh_stroke_opts;
+int dtp_mesh_create(dtp_ctx* ctx, const float* vertices, int V, const int* faces, int F, const float* face_uvs, dtp_mesh** out);
+int dtp_mesh_destroy(dtp_mesh* mesh);
+int dtp_mesh_camera(const float pos[3], const float normal[3], const float prev[3], float fov, float out[12]);
+int dtp_mesh_stroke(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
+                    const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, dtp_stream s);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
@@ -541,6 +611,16 @@ int dtp_op_stroke_gather(const uint8_t* texture, int H, int W, float* canvas, in
                          int wrap, int over_y, int over_x, dtp_stream s);
 int dtp_op_stroke_paste(const float* dec, const uint8_t* mask, uint8_t* texture, int H, int W, int R, int B, const int* xs, const int* ys,
                         const int* modes, int wrap, dtp_stream s);
+
+/* The two halves of a dtp_mesh_stroke stamp on their own (the contract: see dtp_mesh_stroke).  render: cam the 12 floats of
+ * dtp_mesh_camera; projects the mesh, keeps the per-face records with it, and writes canvas f32 [4][R][R] and face_idx i32 [R][R]
+ * (device), 1 <= R <= 4096.  backproject: uses the records of the LAST render of this mesh and that render's face_idx; dec f32 [R][R][4] is
+ * the VAE decoder's output in its working layout (values around -1..1, channel 3 unused), NULL = erase; dec_finished 1: dec holds the
+ * clamped 0..1 values already (what dtp_stamp returns with composite 0, in the same [R][R][4] layout) and is used as it is; mask u8 [R][R]. */
+int dtp_op_mesh_render(dtp_mesh* mesh, const float cam[12], float fov, int flip_normals, const uint8_t* texture, int H, int W, int R, int mode,
+                       int over_y, int over_x, float* canvas, int* face_idx, dtp_stream s);
+int dtp_op_mesh_backproject(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R, uint8_t* texture, int H, int W,
+                            dtp_stream s);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,94 @@
+// Stand-alone host check of csrc/mesh.hip for a sanitizer build: the part of it that needs no device -- dtp_mesh_camera and the argument
+// checks of dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_stroke and the two ops, all of which return before their first HIP call --
+// driven from its own main().  The rest of the library is replaced by the stubs below; none of them may be reached.  Build and run:
+//   hipcc --offload-arch=gfx950 -std=c++17 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//         -I include -I diffusiontexturepainting_amd/csrc diffusiontexturepainting_amd/csrc/mesh.hip tools/mesh_host_check.cpp -o mesh_host_check
+//   ./mesh_host_check
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+
+#include "stamp.h"
+
+static char g_err[1024];
+void dtp_set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+}
+extern "C" const char* dtp_last_error(void) { return g_err; }
+static int unreachable(const char* what) { fprintf(stderr, "reached %s: a check let a bad call through\n", what); abort(); }
+int stamp_plan(Ctx*, StampPlan&) { return unreachable("stamp_plan"); }
+int stamp_enqueue(Ctx*, const StampPlan&, hipStream_t) { return unreachable("stamp_enqueue"); }
+int ctx_persistent(Ctx*, size_t, void**, bool) { return unreachable("ctx_persistent"); }
+int stroke_default_mask(Ctx*, int, hipStream_t, const unsigned char**) { return unreachable("stroke_default_mask"); }
+
+static int g_checks = 0;
+#define EXPECT(cond)                                                                      \
+  do {                                                                                    \
+    ++g_checks;                                                                           \
+    if (!(cond)) { fprintf(stderr, "%s:%d: %s failed (%s)\n", __FILE__, __LINE__, #cond, g_err); return 1; } \
+  } while (0)
+
+int main() {
+  float out[12];
+  const float pos[3] = {0.3f, -1.7f, 2.9f}, normal[3] = {0.2f, 0.5f, 0.84f}, prev[3] = {0.1f, -1.2f, 2.6f}, zero[3] = {0, 0, 0};
+  EXPECT(dtp_mesh_camera(pos, normal, prev, 0.37f, out) == DTP_OK);
+  for (int k = 0; k < 3; ++k) {  // orthonormal rows
+    double n = 0;
+    for (int i = 0; i < 3; ++i) n += (double)out[4 * k + i] * out[4 * k + i];
+    EXPECT(fabs(n - 1.0) < 1e-6);
+  }
+  const float nanv[3] = {NAN, 0, 0}, p2[3] = {1.f, 2.f, 3.f}, n2[3] = {0.25f, 0.5f, 0.75f}, par[3] = {1.5f, 3.f, 4.5f}, huge[3] = {3e38f, 3e38f, 3e38f};
+  EXPECT(dtp_mesh_camera(pos, zero, prev, 1.f, out) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_camera(pos, normal, pos, 1.f, out) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_camera(p2, n2, par, 1.f, out) == DTP_ERR_ARG);  // prev = pos + 2 normal, exactly
+  EXPECT(dtp_mesh_camera(nanv, normal, prev, 1.f, out) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_camera(pos, normal, prev, 0.f, out) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_camera(pos, normal, prev, INFINITY, out) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_camera(huge, normal, prev, 1.f, out) == DTP_ERR_ARG || isfinite(out[3]));
+  EXPECT(dtp_mesh_camera(nullptr, normal, prev, 1.f, out) == DTP_ERR_ARG);
+
+  // dtp_mesh_create: every byte of the arrays is read before the refusal at the end (ctx NULL), at the exact sizes
+  const int V = 1000, F = 1998;
+  std::vector<float> verts(3 * V), uvs(6 * F);
+  std::vector<int> faces(3 * F);
+  for (int i = 0; i < 3 * V; ++i) verts[i] = (float)(i % 17) * 0.25f;
+  for (int i = 0; i < 6 * F; ++i) uvs[i] = (float)(i % 11) / 11.f;
+  for (int i = 0; i < 3 * F; ++i) faces[i] = i % V;
+  dtp_mesh* mesh = nullptr;
+  EXPECT(dtp_mesh_create(nullptr, verts.data(), V, faces.data(), F, uvs.data(), &mesh) == DTP_ERR_ARG && strstr(g_err, "ctx is NULL"));
+  faces[3 * F - 1] = V;
+  EXPECT(dtp_mesh_create(nullptr, verts.data(), V, faces.data(), F, uvs.data(), &mesh) == DTP_ERR_ARG && strstr(g_err, "face 1997"));
+  faces[3 * F - 1] = 0;
+  uvs[6 * F - 1] = NAN;
+  EXPECT(dtp_mesh_create(nullptr, verts.data(), V, faces.data(), F, uvs.data(), &mesh) == DTP_ERR_ARG && strstr(g_err, "face 1997"));
+  uvs[6 * F - 1] = 0.f;
+  verts[3 * V - 1] = INFINITY;
+  EXPECT(dtp_mesh_create(nullptr, verts.data(), V, faces.data(), F, uvs.data(), &mesh) == DTP_ERR_ARG && strstr(g_err, "vertex 999"));
+  EXPECT(dtp_mesh_create(nullptr, verts.data(), 0, faces.data(), F, uvs.data(), &mesh) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_create(nullptr, verts.data(), V, faces.data(), (1 << 20) + 1, uvs.data(), &mesh) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_create(nullptr, nullptr, V, faces.data(), F, uvs.data(), &mesh) == DTP_ERR_ARG);
+  EXPECT(mesh == nullptr);
+
+  // handles that are not live meshes are refused without being followed
+  int not_a_mesh[64] = {0};
+  EXPECT(dtp_mesh_destroy(nullptr) == DTP_OK);
+  EXPECT(dtp_mesh_destroy((dtp_mesh*)not_a_mesh) == DTP_ERR_ARG);
+  float canvas[4];
+  int face_idx[1];
+  unsigned char tex[4], mask[1];
+  EXPECT(dtp_op_mesh_render((dtp_mesh*)not_a_mesh, out, 1.f, 0, tex, 1, 1, 1, 0, 0, 0, canvas, face_idx, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_op_mesh_render(nullptr, out, 1.f, 0, tex, 1, 1, 1, 0, 0, 0, canvas, face_idx, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_op_mesh_backproject((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr) == DTP_ERR_ARG);
+  dtp_settings st = {};
+  dtp_mesh_stroke_opts o = {};
+  dtp_mesh_stamp stamp = {};
+  EXPECT(dtp_mesh_stroke(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, nullptr) == DTP_ERR_ARG);
+  printf("mesh_host_check: %d checks passed\n", g_checks);
+  return 0;
+}

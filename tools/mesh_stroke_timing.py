@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""What the render and the backprojection of a mesh stroke cost per stamp: one 16-stamp stroke at 512^2 / 20 steps on a
+2048^2 texture over the height field refined to about 100 k faces (`paint_mesh_stroke`), against `paint_stroke(max_group=1)` with the
+same number of stamps and the same seeds, in one process, alternating, warmed up, three repeats each.  Wall time from the call to the
+end of the device work, the host time of the call itself, and the two mesh kernels' groups on their own between events (render =
+reset + project + render; backproject = valid + backproject).  Prints one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--texture", type=int, default=2048)
+    ap.add_argument("--ddim-steps", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--grid", type=int, default=225, help="vertices per side of the height field (225: 100 352 faces)")
+    a = ap.parse_args()
+    from diffusiontexturepainting_amd import ops, synthetic, weights as W
+    from diffusiontexturepainting_amd.inpainter import MI355ConditionalInpainter
+    from diffusiontexturepainting_amd.mesh import mesh_camera
+    dev = torch.device("cuda", 0)
+    R, T = a.res, a.texture
+    sd = dict(unet=W.synthetic_unet(), lora=W.synthetic_lora(), vae=W.synthetic_vae())
+    st = dict(steps=a.ddim_steps, context_pad=150, tg_steps=a.ddim_steps, cfg_weight=2.0, tg_weight=1.0)
+    _, brush, _, _ = synthetic.make_stamp_batch(1, R, seed=1000)
+    cond, uncond = synthetic.make_conditioning(7)
+    m = MI355ConditionalInpainter(R, device=0, weights=sd, max_batch=1)
+    m.set_conditioning(cond, uncond, brush)
+    verts, faces, uvs = synthetic.make_height_field(a.grid, a.grid, seed=3)
+    mesh = m.load_mesh(verts, faces, uvs)
+    # a 4 x 4 grid of brush positions over the field, slightly tilted cameras, windows 0.5 wide (each sees about 1/12 of the faces)
+    positions = [(-0.6 + 0.4 * (i % 4), -0.45 + 0.3 * (i // 4), 0.1) for i in range(16)]
+    normals = [(0.1 * ((i % 3) - 1), 0.1 * ((i % 2) - 0.5), 1.0) for i in range(16)]
+    prevs = [(x, y + 0.1, z) for x, y, z in positions]
+    fov = 0.25
+    per_row = T // R
+    windows = [((i % per_row) * R, (i // per_row) * R) for i in range(16)]
+    seeds = list(range(500, 516))
+    tex0 = torch.randint(0, 256, (T, T, 4), dtype=torch.uint8, generator=torch.Generator().manual_seed(1)).to(dev)
+
+    arms = {
+        "paint_mesh_stroke": lambda tex: m.paint_mesh_stroke(mesh, tex, positions, normals, prevs, fov, seeds=seeds, **st),
+        "paint_stroke_serial": lambda tex: m.paint_stroke(tex, windows, seeds=seeds, max_group=1, margin=1, **st),
+    }
+    for fn in arms.values():  # build, capture, warm
+        fn(tex0.clone())
+    torch.cuda.synchronize()
+    wall, host = {k: [] for k in arms}, {k: [] for k in arms}
+    for _ in range(a.repeats):
+        for name, fn in arms.items():
+            tex = tex0.clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(tex)
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            host[name].append((t1 - t0) * 1e3)
+            wall[name].append((t2 - t0) * 1e3)
+    # the two kernel groups on their own, per stamp
+    tex = tex0.clone()
+    dec = torch.randn(R, R, 4, device=dev)
+    mask = torch.ones(R, R, dtype=torch.uint8, device=dev)
+    mask[0], mask[-1], mask[:, 0], mask[:, -1] = 0, 0, 0, 0
+    cams = [mesh_camera(p, n, q, fov) for p, n, q in zip(positions, normals, prevs)]
+    render_ms, back_ms, shown, written = [], [], [], []
+    for rep in range(2):  # (the first round warms up)
+        render_ms, back_ms = [], []
+        for cam in cams:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            before = tex.clone()
+            ev[0].record()
+            _, face_idx = ops.mesh_render(mesh, cam, fov, tex, R)
+            ev[1].record()
+            ops.mesh_backproject(mesh, dec, mask, face_idx, tex)
+            ev[2].record()
+            torch.cuda.synchronize()
+            render_ms.append(ev[0].elapsed_time(ev[1]))
+            back_ms.append(ev[1].elapsed_time(ev[2]))
+            if rep == 1:
+                shown.append(int(face_idx.unique().numel()) - int((face_idx < 0).any()))
+                written.append(int((tex != before).any(dim=-1).sum()))
+    out = dict(res=R, texture=T, faces=int(faces.shape[0]), stamps=16, ddim_steps=a.ddim_steps, repeats=a.repeats)
+    for name in arms:
+        med = statistics.median(wall[name])
+        out[name] = dict(wall_ms=[round(v, 1) for v in wall[name]], median_wall_ms=round(med, 1), per_stamp_ms=round(med / 16, 2),
+                         host_ms_until_the_call_returned=round(statistics.median(host[name]), 1))
+    diff = (out["paint_mesh_stroke"]["median_wall_ms"] - out["paint_stroke_serial"]["median_wall_ms"]) / 16
+    out["per_stamp_difference_ms"] = round(diff, 3)
+    out["per_stamp_difference_percent_of_a_stamp"] = round(100 * diff / out["paint_stroke_serial"]["per_stamp_ms"], 2)
+    out["kernels_alone"] = dict(render_ms_median=round(statistics.median(render_ms), 3), render_ms_max=round(max(render_ms), 3),
+                                backproject_ms_median=round(statistics.median(back_ms), 3), backproject_ms_max=round(max(back_ms), 3),
+                                faces_shown_median=int(statistics.median(shown)), texels_written_median=int(statistics.median(written)))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
