@@ -302,7 +302,7 @@ struct GemmParams {
   const unsigned char* W8;
   int ldw8;
   float a_scale, w_scale;  // A8 = e4m3(A / a_scale), W8 = e4m3(W / w_scale); powers of two
-  // host-side only (engine.hip make_gemm_op): the calibrated activation scale of this fp8 problem lives at *a_scale_host (read at
+  // host-side only (builder.hip make_gemm_op): the calibrated activation scale of this fp8 problem lives at *a_scale_host (read at
   // enqueue time, i.e. before graph capture); amax_slot1 - 1 = its slot in the context's amax table (0: none)
   const float* a_scale_host;
   int amax_slot1;

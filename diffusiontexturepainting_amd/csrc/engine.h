@@ -389,7 +389,7 @@ struct Ctx {
   float refit_ms = 0.f;
 };
 
-// ---- engine.hip
+// ---- engine.hip: memory, staging, weight loaders
 int ctx_arena_alloc(Ctx* c, size_t bytes, void** out);
 int ctx_pool_get(Ctx* c, size_t bytes, void** out);
 void ctx_pool_put(Ctx* c, void* p);
@@ -427,9 +427,36 @@ struct RowStats {
   int rows_total = 0, row_off = 0;
 };
 
-// ---- builder helpers (engine.hip): every function appends ops to `prog` and returns planned buffers
+// ---- builder.hip: every function appends ops to `prog` and returns planned buffers
 void prog_push(Ctx* c, Prog* prog, int kind, double flops, double bytes, Op fn, const std::string& label);
-int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg, RowStats* emit = nullptr);
+int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg, RowStats* emit = nullptr);  // emit (with a buffer): the launch writes its row statistics there (GF_ROWSTATS) and fills in parts / M
+bool dtp_conv_output_can_carry_gn_stats(const GemmParams& p);  // the UNSPLIT conv problem p: may its epilogue emit its consumer GroupNorm's statistics?
+
+struct MemRange { const void* p; size_t bytes; };
+
+// A split-K producer whose reduce the GroupNorm-side launch that consumes its output has taken over (Builder::claim_reduce)
+struct ReduceClaim {
+  bool claimed = false;
+  GemmParams p = {};       // the producer as it was re-pushed (GF_NOREDUCE)
+  int bias_step_off = -1;  // >= 0: its bias is this slice of the step-bias table
+  explicit operator bool() const { return claimed; }
+  size_t slab_bytes() const;           // the producer's fp32 slabs at the head of the shared workspace, 256-byte aligned (0: nothing claimed)
+  std::vector<MemRange> busy() const;  // what the taken-over reduce still reads besides the slabs: the producer's residual, or nothing
+  GnReduceSrc src(const Ctx* c, int step) const;  // the reduce as the GroupNorm kernels take it, the bias resolved for `step` (at enqueue time)
+};
+
+// GroupNorm (+ SiLU) applied on a conv's staged input (GF_GNAPPLY): the statistics partials and the affine parameters
+struct GnOnLoad { const float *part = nullptr, *gamma = nullptr, *beta = nullptr; float eps = 0.f; int nchunk = 0, cpg = 0; };
+// what only some conv3() calls need
+struct Conv3Opts {
+  int extra_flags = 0;
+  void* out_override = nullptr; int ldc_override = 0;  // write here with this row pitch (the fp32 outputs) instead of a planned fp16 buffer
+  const T* tail = nullptr;       // the operand of the 1x1 shortcut fused as a 10th tap (w.cin2 channels)
+  const T* dst = nullptr;        // write into this (possibly strided) view instead of a fresh buffer
+  GnOnLoad gn;                   // with GF_GNAPPLY among extra_flags
+  static Conv3Opts into(const T& view) { Conv3Opts o; o.dst = &view; return o; }
+  static Conv3Opts f32_out(float* out, int ldc) { Conv3Opts o; o.extra_flags = GF_OUT_F32; o.out_override = out; o.ldc_override = ldc; return o; }
+};
 
 struct Builder {
   Ctx* c;
@@ -441,18 +468,16 @@ struct Builder {
   T alloc(int B, int H, int W, int C);
   void release(const T& t);
   int gn(const T& x, const NormW& n, float eps, bool silu, T& y);
-  bool claim_reduce(const T& x, GemmParams& gp, int& bias_step_off, bool allow_concat = false);
+  ReduceClaim claim_reduce(const T& x, bool allow_concat = false);
   bool claim_stats(const T& x, float** partials, int* nchunk);
   bool gn_linear_supported(const T& x, const ConvW& w) const;
   int gn_linear(const T& x, const NormW& n, float eps, const ConvW& w, T& y, RowStats* emit);
   // GroupNorm + SiLU + 3x3 conv (stride 1, pad 1); the apply pass rides on the conv's staged input where the halo kernel can take it
   int gn_conv3(const T& x, const NormW& n, float eps, const ConvW& w, const T* resid, int bias_step_off, T& y, const T* tail, const T* dst);
-  struct { bool active = false; const float *part = nullptr, *gamma = nullptr, *beta = nullptr; float eps = 0.f; int nchunk = 0, cpg = 0; } gn_fused;
   int ln(const T& x, const NormW& n, T& y);
   // conv3x3; bias_step_off >= 0 selects the per-step bias slice from the temb table instead of w.b
-  int conv3(const T& x, const ConvW& w, int stride, int pad, bool ups, int Ho, int Wo, const T* resid, int bias_step_off,
-            T& y, int extra_flags = 0, void* out_override = nullptr, int ldc_override = 0, const T* tail = nullptr,
-            const T* dst = nullptr);  // dst: write into this (possibly strided) view instead of a fresh buffer
+  int conv3(const T& x, const ConvW& w, int stride, int pad, bool ups, int Ho, int Wo, const T* resid, int bias_step_off, T& y,
+            const Conv3Opts& o = Conv3Opts());
   int linear(const T& x, const ConvW& w, const T* resid, int flags, T& y, RowStats* emit = nullptr, const RowStats* use = nullptr,
              const T* dst = nullptr);
   // option fp8_operands: an e4m3 tensor from the pool shaped like `like` with C columns and a calibrated (a new calibration slot) or
@@ -484,13 +509,15 @@ int get_dec_prog(Ctx* c, int B, VaeDecProg** out);
 int launch_vae_sample(Ctx* c, const float* mom, const float* eps, float* out, int B, float scale, hipStream_t s, const float* eps3 = nullptr,
                       int n_eps = -1);
 int launch_post_quant(Ctx* c, const float* z, int nhwc, float in_scale, f16* out, int B, hipStream_t s);
-int ensure_ws(Ctx* c);
-int ensure_w8(Ctx* c, ConvW& w);
-// fp8 calibration: new scale / amax-slot pair for a Linear (returns the scale's address, sets *slot1), and the pass itself
+int ensure_ws(Ctx* c);              // engine.hip
+int ensure_w8(Ctx* c, ConvW& w);    // engine.hip: build the e4m3 copy of a Linear's packed weights (once)
+// fp8 calibration (builder.hip): new scale / amax-slot pair for a Linear (returns the scale's address, sets *slot1), and the pass itself
 float* fp8_new_linear_scale(Ctx* c, int* slot1);
-int fp8_calibrate(Ctx* c, UNetProg* up, hipStream_t s, int step);  // build the e4m3 copy of a Linear's packed weights (once)
+int fp8_calibrate(Ctx* c, UNetProg* up, hipStream_t s, int step);
+// ---- tune.hip: the persisted (shape -> tile, splits) table; tune_gemm: (*tile, *sp) is the caller's configuration on entry, the one to use on return
 void tune_cache_load(Ctx* c);
 void tune_cache_save(Ctx* c);
+int tune_gemm(Ctx* c, const GemmParams& p, int* tile, int* sp);
 int ensure_temb(Ctx* c, const std::vector<float>& timesteps);  // fills temb_table rows 0..n-1
 
 // ---- context.hip

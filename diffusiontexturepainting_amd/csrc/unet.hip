@@ -569,10 +569,10 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
   T x;
   if (dupB > 0) {  // de-duplicated prefix: conv_in on samples [dupB, N) only (struct Dup)
     const T x0s = samples(x0, dupB, N - dupB), sk0s = samples(skipv[sk], dupB, N - dupB);
-    RC(b.conv3(x0s, u.conv_in, 1, 1, false, h, h, nullptr, -1, x, 0, nullptr, 0, nullptr, &sk0s));
+    RC(b.conv3(x0s, u.conv_in, 1, 1, false, h, h, nullptr, -1, x, Conv3Opts::into(sk0s)));
     ++sk;
   } else {
-    RC(b.conv3(x0, u.conv_in, 1, 1, false, h, h, nullptr, -1, x, 0, nullptr, 0, nullptr, &skipv[sk++]));
+    RC(b.conv3(x0, u.conv_in, 1, 1, false, h, h, nullptr, -1, x, Conv3Opts::into(skipv[sk++])));
   }
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < 2; ++j) {
@@ -602,7 +602,7 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
     }
     if (i < 3) {
       T y;
-      RC(b.conv3(x, u.down_conv[i], 2, 1, false, (x.H + 1) / 2, (x.W + 1) / 2, nullptr, -1, y, 0, nullptr, 0, nullptr, &skipv[sk++]));
+      RC(b.conv3(x, u.down_conv[i], 2, 1, false, (x.H + 1) / 2, (x.W + 1) / 2, nullptr, -1, y, Conv3Opts::into(skipv[sk++])));
       x = y;
     }
   }
@@ -637,7 +637,7 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
     if (i < 3) {
       T y;
       // nearest upsample to the skip's size (2 n or 2 n - 1): the x2 window of GF_UPS2, cropped by the output size
-      RC(b.conv3(x, u.up_conv[i], 1, 1, true, xslot[pk].H, xslot[pk].W, nullptr, -1, y, 0, nullptr, 0, nullptr, &xslot[pk]));
+      RC(b.conv3(x, u.up_conv[i], 1, 1, true, xslot[pk].H, xslot[pk].W, nullptr, -1, y, Conv3Opts::into(xslot[pk])));
       b.release(x);
       x = y;
     }
@@ -645,7 +645,7 @@ int build_unet_prog(Ctx* c, int N, int dupB, UNetProg& up) {
   T t, o;
   RC(b.gn(x, u.norm_out, 1e-5f, true, t));
   b.release(x);
-  RC(b.conv3(t, u.conv_out, 1, 1, false, h, h, nullptr, -1, o, GF_OUT_F32, up.out32, 4));
+  RC(b.conv3(t, u.conv_out, 1, 1, false, h, h, nullptr, -1, o, Conv3Opts::f32_out(up.out32, 4)));
   b.release(t);
   up.cal_end = c->fp8_cals.size();
   tune_cache_save(c);

@@ -169,7 +169,7 @@ int build_vae_enc_prog(Ctx* c, int B, VaeEncProg& pr) {
   RC(b.resnet(z, v.enc_mid[1], 1e-6f, false, w2)); b.release(z);
   RC(b.gn(w2, v.enc_norm_out, 1e-6f, true, t)); b.release(w2);
   T o;
-  RC(b.conv3(t, v.enc_out, 1, 1, false, c->h, c->h, nullptr, -1, o, GF_OUT_F32, pr.moments + (size_t)b0 * c->h * c->h * 8, 8));
+  RC(b.conv3(t, v.enc_out, 1, 1, false, c->h, c->h, nullptr, -1, o, Conv3Opts::f32_out(pr.moments + (size_t)b0 * c->h * c->h * 8, 8)));
   b.release(t);
   }
   tune_cache_save(c);
@@ -211,7 +211,7 @@ int build_vae_dec_prog(Ctx* c, int B, VaeDecProg& pr) {
   }
   T t, o;
   RC(b.gn(x, v.dec_norm_out, 1e-6f, true, t)); b.release(x);
-  RC(b.conv3(t, v.dec_out, 1, 1, false, R, R, nullptr, -1, o, GF_OUT_F32, pr.out32 + (size_t)b0 * R * R * 4, 4));
+  RC(b.conv3(t, v.dec_out, 1, 1, false, R, R, nullptr, -1, o, Conv3Opts::f32_out(pr.out32 + (size_t)b0 * R * R * 4, 4)));
   b.release(t);
   }
   tune_cache_save(c);

@@ -85,6 +85,62 @@ def test_unet_register_chains_vs_oracle(monkeypatch, tmp_path):
     assert e < 1e-2
 
 
+# The launch builder's GroupNorm claim path (csrc/builder.hip): a launch label carries one of these markers for every way a GroupNorm
+# takes over its producer's split-K reduce or gets its statistics from the producer's epilogue.
+CLAIM_MARKERS = ("(reduce in gn)", "reduce+gn B=", "reduce(front", "reduce+gn-stats", "(+gn stats)", "gn-apply", "(apply in proj_in)", "gn-fold")
+# What a switch, set alone, takes out of the program -- from the code: fuse_reduce_gn gates claim_reduce; reduce_in_concat_gn its
+# concatenation form; gn_epilogue gates claim_stats; without gna_lnlin gn_linear folds the GroupNorm into per-sample weights instead of
+# applying it in proj_in; without fold_gn_linear gn_linear is not used at all (plain gn + linear)
+CLAIM_REMOVED = {
+    "default": (),
+    "DTP_NO_FUSE_REDUCE_GN": ("(reduce in gn)", "reduce+gn B=", "reduce(front", "reduce+gn-stats"),
+    "DTP_NO_GN_EPILOGUE": ("(+gn stats)", "gn-apply"),
+    "DTP_NO_REDUCE_IN_CONCAT_GN": ("reduce(front",),
+    "DTP_NO_GNA_LNLIN": ("(apply in proj_in)",),
+    "DTP_NO_FOLD_GN": ("(apply in proj_in)", "gn-fold", "reduce+gn-stats"),
+}
+# STILL TO BE FILLED IN: which markers ARE there per case.  That table depends on the shipped tune table and has to be recorded from a
+# run of the library built from the parent of the engine.hip split (python tools/program_dump.py prints it), together with the check that
+# every marker is present in at least one case; no GPU could be had when this test was written (profiles/engine_split_ab.txt).
+
+
+@pytest.fixture(scope="module")
+def claim_oracle():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from diffusiontexturepainting_amd import weights as W
+    from oracle import nets
+    sd = dict(unet=W.synthetic_unet(1), lora=W.synthetic_lora(1), vae=W.synthetic_vae(1))
+    n, t, h = 3, 301.0, 256 // 8
+    g = torch.Generator().manual_seed(n)
+    sample = torch.randn(n, 9, h, h, generator=g)
+    ctx = torch.randn(n, 14, 768, generator=g).half()
+    ref = nets.unet_forward(nets.merge_lora(sd["unet"], sd["lora"]), sample, torch.tensor(t), ctx.float())
+    return dict(sd=sd, sample=sample, ctx=ctx, t=t, ref=ref)
+
+
+@pytest.mark.parametrize("case", list(CLAIM_REMOVED))
+def test_unet_groupnorm_claims_vs_oracle(monkeypatch, tmp_path, claim_oracle, case):
+    """One 256^2 UNet evaluation (n = 3) against the fp32 oracle, by default and with each switch of the GroupNorm claim path set alone
+    (a context reads them when it is created); the claim markers a switch removes must be gone from the launch labels.  The oracle
+    evaluation is shared by the six cases.  Not yet run on a GPU, and the present-marker table is missing: see above."""
+    from diffusiontexturepainting_amd.inpainter import MI355ConditionalInpainter
+    if case != "default":
+        monkeypatch.setenv(case, "1")
+    model = MI355ConditionalInpainter(256, device=0, weights=claim_oracle["sd"], max_batch=1)
+    model.profile(True)
+    got = model.unet(claim_oracle["sample"], claim_oracle["t"], claim_oracle["ctx"])
+    dump = tmp_path / "launches.csv"
+    model.profile_dump(dump)
+    model.profile(False)
+    labels = [ln.split(",", 4)[4] for ln in dump.read_text().splitlines()[1:]]
+    found = tuple(m for m in CLAIM_MARKERS if any(m in lb for lb in labels))
+    e = rel_err(got, claim_oracle["ref"])
+    print("unet", case, "rel err", e, "claim markers", found)
+    assert e < 1e-2
+    assert not set(found) & set(CLAIM_REMOVED[case])
+
+
 def test_vae_encode_vs_oracle(env):
     from oracle import nets
     g = torch.Generator().manual_seed(5)

@@ -9,7 +9,7 @@ PKG = os.path.join(ROOT, "diffusiontexturepainting_amd")
 
 
 def _engine_constants():
-    eng = open(os.path.join(PKG, "csrc", "engine.hip")).read()
+    eng = open(os.path.join(PKG, "csrc", "tune.hip")).read()  # the file that holds tune_gemm
     prefix = re.search(r'snprintf\(key, sizeof\(key\), "(k\d+\|)%d', eng).group(1)
     common = open(os.path.join(PKG, "csrc", "common.h")).read()
     ntiles = int(re.search(r"constexpr int DTP_TILE_IDS = (\d+);", common).group(1))
