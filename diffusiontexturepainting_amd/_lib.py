@@ -130,6 +130,7 @@ SYMBOLS = {
     "dtp_op_quantize_w8": (_i, [_vp, _i, _i, _i, _vp, _i, C.POINTER(_f), _vp]),
     "dtp_op_pack_conv_cb": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "dtp_op_groupnorm_apply": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "dtp_op_groupnorm_stats_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "dtp_op_pack_conv_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "dtp_op_pack_conv_ws_elems": (C.c_longlong, [_i, _i, _i]),
     "dtp_op_pack_linear_ws": (_i, [_vp, _i, _vp, _i, _i, _vp]),

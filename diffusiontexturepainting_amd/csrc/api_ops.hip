@@ -196,13 +196,12 @@ int dtp_op_groupnorm(const void* x, int ldx, void* y, int ldy, const float* gamm
   if (rc) return rc;
   rc = ops_ws(dtp_groupnorm_ws_bytes(B, HW, C, groups));
   if (rc) return rc;
-  return dtp_launch_groupnorm((const f16*)x, ldx, (f16*)y, ldy, gamma, beta, g_ops.ws, B, HW, C, groups, eps, silu,
-                              (hipStream_t)s);
+  return dtp_launch_groupnorm(GnParams{(const f16*)x, ldx, (f16*)y, ldy, gamma, beta, B, HW, C, groups, eps, silu}, g_ops.ws, (hipStream_t)s);
 }
 
 int dtp_op_groupnorm_apply(const void* x, int ldx, void* y, int ldy, const float* gamma, const float* beta, const float* partial, int nchunk,
                            int B, int HW, int C, int groups, float eps, int silu, dtp_stream s) {
-  return dtp_launch_groupnorm_apply((const f16*)x, ldx, (f16*)y, ldy, gamma, beta, partial, nchunk, B, HW, C, groups, eps, silu, (hipStream_t)s);
+  return dtp_launch_groupnorm_apply(GnParams{(const f16*)x, ldx, (f16*)y, ldy, gamma, beta, B, HW, C, groups, eps, silu}, partial, nchunk, (hipStream_t)s);
 }
 
 int dtp_op_reduce_groupnorm_cx(const float* part, int splits, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
@@ -215,8 +214,8 @@ int dtp_op_reduce_groupnorm_cx(const float* part, int splits, const float* bias,
   // cx < C: the slabs hold the FIRST cx channels ([splits][B*HW][cx]); channels >= cx are already in conv_out (the other half of a
   // zero-copy concatenation) -- the round-5 form of the launch (engine.hip Builder::claim_reduce)
   if (cx <= 0 || cx > C) { dtp_set_error("reduce_groupnorm: cx %d outside (0, C = %d]", cx, C); return DTP_ERR_ARG; }
-  return dtp_launch_reduce_groupnorm(part, splits, (long long)B * HW * cx, cx, bias, (const f16*)resid, cx, (f16*)conv_out, C, (f16*)y, C, gamma, beta, B, HW, C,
-                                     groups, eps, silu, g_ops.ws, (hipStream_t)s, cx);
+  const GnReduceSrc rd = {part, splits, (long long)B * HW * cx, cx, bias, (const f16*)resid, cx};
+  return dtp_launch_reduce_groupnorm(GnParams{(const f16*)conv_out, C, (f16*)y, C, gamma, beta, B, HW, C, groups, eps, silu}, rd, cx, g_ops.ws, (hipStream_t)s);
 }
 
 int dtp_op_reduce_groupnorm(const float* part, int splits, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
@@ -231,11 +230,28 @@ int dtp_op_gn_fold_weights(const void* x, const void* W, int ldw, const float* b
   if (rc) return rc;
   rc = ops_ws(dtp_groupnorm_ws_bytes(B, HW, C, groups));
   if (rc) return rc;
-  rc = dtp_launch_groupnorm_stats((const f16*)x, C, g_ops.ws, B, HW, C, groups, nullptr, (hipStream_t)s);
+  const GnParams gp = {(const f16*)x, C, nullptr, 0, gamma, beta, B, HW, C, groups, eps, 0};
+  rc = dtp_launch_groupnorm_stats(gp, g_ops.ws, nullptr, (hipStream_t)s);
   if (rc) return rc;
   const int rows = (Nout + 127) / 128 * 128;
-  return dtp_launch_gn_fold_weights((const f16*)W, ldw, bias, gamma, beta, g_ops.ws, B, HW, C, Nout, groups, eps, (f16*)Wout, (long long)rows * ldw, bias_out,
-                                    rows, (hipStream_t)s);
+  return dtp_launch_gn_fold_weights(gp, g_ops.ws, 0, (const f16*)W, ldw, bias, Nout, (f16*)Wout, (long long)rows * ldw, bias_out, rows, (hipStream_t)s);
+}
+
+// The statistics pass with the producing conv's split-K reduce riding in it (part: fp32 slabs [splits][B*HW][C], + bias, + residual; it
+// writes x) or over x as it is (part == nullptr), then the apply pass from its partials: what gn_linear / gn_conv3 run on a claim
+int dtp_op_groupnorm_stats_apply(const float* part, int splits, const float* bias, const void* resid, void* x, void* y, const float* gamma,
+                                 const float* beta, int B, int HW, int C, int groups, float eps, int silu, dtp_stream s) {
+  if (part && splits < 1) { dtp_set_error("groupnorm_stats_apply: %d slabs", splits); return DTP_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(g_ops_mu);
+  int rc = ops_init();
+  if (rc) return rc;
+  rc = ops_ws(dtp_groupnorm_ws_bytes(B, HW, C, groups));
+  if (rc) return rc;
+  const GnParams gp = {(const f16*)x, C, (f16*)y, C, gamma, beta, B, HW, C, groups, eps, silu};
+  const GnReduceSrc rd = {part, splits, (long long)B * HW * C, C, bias, (const f16*)resid, C};
+  rc = dtp_launch_groupnorm_stats(gp, g_ops.ws, part ? &rd : nullptr, (hipStream_t)s);
+  if (rc) return rc;
+  return dtp_launch_groupnorm_apply(gp, g_ops.ws, dtp_groupnorm_stat_chunks(HW), (hipStream_t)s);
 }
 
 int dtp_op_gn_linear(const void* x, const void* W, int ldw, const float* bias, const float* gamma, const float* beta, int B, int HW, int C,
@@ -248,7 +264,7 @@ int dtp_op_gn_linear(const void* x, const void* W, int ldw, const float* bias, c
   if (groups != 32) { dtp_set_error("gn_linear: 32 groups (got %d)", groups); return DTP_ERR_ARG; }
   rc = ops_ws(dtp_groupnorm_ws_bytes(B, HW, C, groups));
   if (rc) return rc;
-  rc = dtp_launch_groupnorm_stats((const f16*)x, C, g_ops.ws, B, HW, C, groups, nullptr, (hipStream_t)s);
+  rc = dtp_launch_groupnorm_stats(GnParams{(const f16*)x, C, nullptr, 0, gamma, beta, B, HW, C, groups, eps, 0}, g_ops.ws, nullptr, (hipStream_t)s);
   if (rc) return rc;
   GemmParams p = {};
   p.A = (const f16*)x; p.lda = C; p.W = (const f16*)W; p.ldw = ldw; p.nkb = ldw / 64;

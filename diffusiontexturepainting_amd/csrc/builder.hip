@@ -106,10 +106,8 @@ ReduceClaim Builder::claim_reduce(const T& x, bool allow_concat) {
   if (!(c->fuse_reduce_gn && lg.valid && lg.p.splits > 1 && (f16*)lg.p.C == x.p && lg.p.ldc == x.ld && lg.p.M == (int)x.rows() && (whole || front) &&
         !(lg.p.flags & ~GF_CLAIMABLE) && lg.p.batch <= 1 && (x.C & 7) == 0))
     return ReduceClaim();
-  {  // what the GroupNorm-side reduce kernels accept (norm.hip): checked here, where the separate reduce is still the fallback
-    const int cpg = x.C / 32;
-    if ((x.C % 32) || cpg < 4 || (cpg < 8 && cpg != 4) || (lg.p.N & 3) || x.C / 8 > 1024 || (x.ld & 7) || ((lg.p.flags & GF_RESID) && (lg.p.ldr & 7))) return ReduceClaim();
-  }
+  // what the GroupNorm-side launches accept, asked here, where the separate reduce is still the fallback
+  if (!dtp_groupnorm_reduce_accepts(x.C, 32, x.ld, lg.p.N, (lg.p.flags & GF_RESID) ? lg.p.ldr : 0)) return ReduceClaim();
   ReduceClaim claim = {true, lg.p, lg.bias_step_off};
   claim.p.flags |= GF_NOREDUCE;
   prog->ops[lg.op_index] = Op();  // rebuilt below through the profiling wrapper
@@ -137,16 +135,21 @@ static void* block_clear_of_claim(Ctx* c, size_t bytes, const ReduceClaim& claim
   return p;
 }
 
+// The 32-group GroupNorm over x as the launchers take it (y: the normalised tensor, if the launch writes one), and its launch label
+static GnParams gn_params(const T& x, const NormW& n, float eps, bool silu, const T* y = nullptr) {
+  return {x.p, x.ld, y ? y->p : nullptr, y ? y->ld : 0, n.g, n.b, x.B, x.H * x.W, x.C, 32, eps, silu ? 1 : 0};
+}
+static std::string gn_label(const GnParams& gp) { return " B=" + std::to_string(gp.B) + " HW=" + std::to_string(gp.HW) + " C=" + std::to_string(gp.C); }
+
 // The statistics pass of the two-launch GroupNorm over x, the claimed reduce riding in it.  `part`: a planned partials buffer that outlives
 // the launch, or null: the shared workspace behind the claim's slabs (good until the next split launch).
-static void push_gn_stats(Builder& b, const T& x, float* part, const ReduceClaim& claim, const char* label_suffix) {
+static void push_gn_stats(Builder& b, const GnParams& gp, float* part, const ReduceClaim& claim, const char* label_suffix) {
   Ctx* cc = b.c;
-  const T xx = x;
   const size_t slab_bytes = claim.slab_bytes();
-  b.push(PK_GN, 0.0, 2.0 * (double)xx.rows() * xx.C, [=](hipStream_t s, int step) {
+  b.push(PK_GN, 0.0, 2.0 * (double)gp.B * gp.HW * gp.C, [=](hipStream_t s, int step) {
     const GnReduceSrc rd = claim.src(cc, step);
-    return dtp_launch_groupnorm_stats(xx.p, xx.ld, part ? part : (float*)((char*)cc->ws + slab_bytes), xx.B, xx.H * xx.W, xx.C, 32, claim ? &rd : nullptr, s);
-  }, std::string(claim ? "reduce+gn-stats" : "gn-stats") + " B=" + std::to_string(x.B) + " HW=" + std::to_string(x.H * x.W) + " C=" + std::to_string(x.C) + label_suffix);
+    return dtp_launch_groupnorm_stats(gp, part ? part : (float*)((char*)cc->ws + slab_bytes), claim ? &rd : nullptr, s);
+  }, (claim ? "reduce+gn-stats" : "gn-stats") + gn_label(gp) + label_suffix);
 }
 
 // Let the GEMM p emit the per-row (sum, sumsq) partials of its output into `emit` (GF_ROWSTATS); false: nothing to emit into.  The table
@@ -197,31 +200,24 @@ int Builder::gn(const T& x, const NormW& n, float eps, bool silu, T& y) {
   if (!y.p) return DTP_ERR_HIP;
   const size_t slab_bytes = claim.slab_bytes();
   cc->ws_need = std::max(cc->ws_need, slab_bytes + dtp_groupnorm_ws_bytes(x.B, x.H * x.W, x.C, 32));
-  const T xx = x, yy = y;
-  const NormW nn = n;
+  const GnParams gp = gn_params(x, n, eps, silu, &y);
+  const double bytes = 4.0 * (double)x.rows() * x.C;
   if (claim) {
     // small maps: one launch does it all; large maps: the reduce rides in the statistics pass, whose partial sums live behind the slabs
-    const int Cx = claim.p.N, splits = claim.p.splits;  // the producer wrote channels [0, Cx) of x (fewer than x.C: a concatenation's front)
-    push(PK_GN, 0.0, 4.0 * (double)xx.rows() * xx.C, [=](hipStream_t s, int step) {
-      const GnReduceSrc rd = claim.src(cc, step);
-      return dtp_launch_reduce_groupnorm(rd.part, rd.splits, rd.slab, rd.ldp, rd.bias, rd.R, rd.ldr,
-                                         xx.p, xx.ld, yy.p, yy.ld, nn.g, nn.b, xx.B, xx.H * xx.W, xx.C, 32, eps, silu ? 1 : 0,
-                                         (float*)((char*)cc->ws + slab_bytes), s, Cx);
-    }, std::string(Cx < x.C ? "reduce(front " + std::to_string(Cx) + ")+gn B=" : "reduce+gn B=") + std::to_string(x.B) + " HW=" + std::to_string(x.H * x.W) + " C=" + std::to_string(x.C) + " splits=" + std::to_string(splits));
+    const int Cx = claim.p.N;  // the producer wrote channels [0, Cx) of x (fewer than x.C: a concatenation's front)
+    push(PK_GN, 0.0, bytes, [=](hipStream_t s, int step) {
+      return dtp_launch_reduce_groupnorm(gp, claim.src(cc, step), Cx, (float*)((char*)cc->ws + slab_bytes), s);
+    }, (Cx < x.C ? "reduce(front " + std::to_string(Cx) + ")+gn" : std::string("reduce+gn")) + gn_label(gp) + " splits=" + std::to_string(claim.p.splits));
     return DTP_OK;
   }
   float* partials = nullptr;
   int nchunk = 0;
   if (claim_stats(x, &partials, &nchunk)) {  // statistics from the producing conv's epilogue: the apply pass alone
-    push(PK_GN, 0.0, 4.0 * (double)xx.rows() * xx.C, [=](hipStream_t s, int) {
-      return dtp_launch_groupnorm_apply(xx.p, xx.ld, yy.p, yy.ld, nn.g, nn.b, partials, nchunk, xx.B, xx.H * xx.W, xx.C, 32, eps, silu ? 1 : 0, s);
-    }, "gn-apply B=" + std::to_string(x.B) + " HW=" + std::to_string(x.H * x.W) + " C=" + std::to_string(x.C));
+    push(PK_GN, 0.0, bytes, [=](hipStream_t s, int) { return dtp_launch_groupnorm_apply(gp, partials, nchunk, s); }, "gn-apply" + gn_label(gp));
     ctx_pool_put(cc, partials);
     return DTP_OK;
   }
-  push(PK_GN, 0.0, 4.0 * (double)xx.rows() * xx.C, [=](hipStream_t s, int) {
-    return dtp_launch_groupnorm(xx.p, xx.ld, yy.p, yy.ld, nn.g, nn.b, cc->ws, xx.B, xx.H * xx.W, xx.C, 32, eps, silu ? 1 : 0, s);
-  }, "gn B=" + std::to_string(x.B) + " HW=" + std::to_string(x.H * x.W) + " C=" + std::to_string(x.C));
+  push(PK_GN, 0.0, bytes, [=](hipStream_t s, int) { return dtp_launch_groupnorm(gp, cc->ws, s); }, "gn" + gn_label(gp));
   return DTP_OK;
 }
 
@@ -238,6 +234,7 @@ bool Builder::gn_linear_supported(const T& x, const ConvW& w) const {
 int Builder::gn_linear(const T& x, const NormW& n, float eps, const ConvW& w, T& y, RowStats* emit) {
   Ctx* cc = c;
   const int HW = x.H * x.W, C = x.C, N = x.B, Cp = (w.cout + 127) / 128 * 128;
+  const GnParams gp = gn_params(x, n, eps, false);
   const ReduceClaim claim = claim_reduce(x);
   float* ep_part = nullptr;  // statistics emitted by the producing conv's epilogue (claim_stats): no statistics launch at all
   int ep_chunks = 0;
@@ -265,7 +262,7 @@ int Builder::gn_linear(const T& x, const NormW& n, float eps, const ConvW& w, T&
       if (!from_epilogue) {
         part = (float*)block_clear_of_claim(cc, dtp_groupnorm_ws_bytes(N, HW, C, 32), claim, "gn_linear", "partials");
         if (!part) return DTP_ERR_HIP;
-        push_gn_stats(*this, x, part, claim, " (apply in proj_in)");
+        push_gn_stats(*this, gp, part, claim, " (apply in proj_in)");
       }
       g.gn_part = part;
       y = alloc(x.B, x.H, x.W, w.cout);
@@ -281,13 +278,11 @@ int Builder::gn_linear(const T& x, const NormW& n, float eps, const ConvW& w, T&
   RC(ctx_pool_get(cc, (size_t)N * Cp * sizeof(float), &pb));
   f16* Wf = (f16*)pw;
   float* bf = (float*)pb;
-  const NormW nn = n;
   const ConvW ww = w;
-  if (!from_epilogue) push_gn_stats(*this, x, nullptr, claim, "");  // into the shared workspace behind the slabs: the fold below reads them next
+  if (!from_epilogue) push_gn_stats(*this, gp, nullptr, claim, "");  // into the shared workspace behind the slabs: the fold below reads them next
   push(PK_GN, 0.0, 2.0 * (double)N * w.cout * C * 2, [=](hipStream_t s, int) {
     const float* part = from_epilogue ? ep_part : (const float*)((char*)cc->ws + slab_bytes);
-    return dtp_launch_gn_fold_weights(ww.w, ww.ldw, ww.b, nn.g, nn.b, part, N, HW, C, ww.cout, 32, eps, Wf, (long long)Cp * ww.ldw, bf, Cp, s,
-                                      from_epilogue ? ep_chunks : 0);
+    return dtp_launch_gn_fold_weights(gp, part, from_epilogue ? ep_chunks : 0, ww.w, ww.ldw, ww.b, ww.cout, Wf, (long long)Cp * ww.ldw, bf, Cp, s);
   }, std::string(from_epilogue ? "gn-fold (stats from conv) B=" : "gn-fold B=") + std::to_string(N) + " C=" + std::to_string(C) + " N=" + std::to_string(w.cout));
   if (from_epilogue) ctx_pool_put(cc, ep_part);
   y = alloc(x.B, x.H, x.W, w.cout);
@@ -476,7 +471,7 @@ int Builder::gn_conv3(const T& x, const NormW& n, float eps, const ConvW& w, con
   float* partials = (float*)block_clear_of_claim(cc, dtp_groupnorm_ws_bytes(x.B, HW, C, 32), claim, "gn_conv3", "partials");
   if (!partials) return DTP_ERR_HIP;
   cc->ws_need = std::max(cc->ws_need, claim.slab_bytes());
-  push_gn_stats(*this, x, partials, claim, " (apply in conv)");
+  push_gn_stats(*this, gn_params(x, n, eps, true), partials, claim, " (apply in conv)");  // (the statistics pass reads x and the shape alone)
   opts.extra_flags = GF_GNAPPLY; opts.gn = {partials, n.g, n.b, eps, dtp_groupnorm_stat_chunks(HW), C / 32};
   const int rc = conv3(x, w, 1, 1, false, x.H, x.W, resid, bias_step_off, y, opts);
   ctx_pool_put(cc, partials);

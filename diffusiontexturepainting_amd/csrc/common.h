@@ -366,31 +366,36 @@ size_t dtp_gemm_workspace_bytes(const GemmParams& p);
 void dtp_gemm_pick(GemmParams& p, int* tile, int num_cu);  // sets splits/kb_per_split
 
 // ---------------------------------------------------------------- norms (norm.hip)
-// GroupNorm over NHWC [B][HW][C] (row stride ld), optional fused SiLU, fp32 statistics.
-int dtp_launch_groupnorm(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, float* stats_ws,
-                         int B, int HW, int C, int groups, float eps, int silu, hipStream_t s);
-size_t dtp_groupnorm_ws_bytes(int B, int HW, int C, int groups);
-int dtp_groupnorm_stat_chunks(int HW);
-// the apply pass alone, on partial sums [B][nchunk][groups][2] that somebody else produced (a convws_kernel launch with GF_GNSTATS)
-int dtp_launch_groupnorm_apply(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, const float* partial, int nchunk,
-                               int B, int HW, int C, int groups, float eps, int silu, hipStream_t s);  // pixel chunks per sample of dtp_launch_groupnorm_stats (partials [B][chunks][groups][2])
-// split-K reduce (+ bias, + residual) of a conv output fused with the GroupNorm (+SiLU) that consumes it: writes the fp16 conv
-// output c_out AND the normalised tensor y -- in one launch where dtp_reduce_groupnorm_supported() (HW <= 256), otherwise the
-// reduce rides in the statistics pass of the two-launch GroupNorm (needs stats_ws, dtp_groupnorm_ws_bytes)
-bool dtp_reduce_groupnorm_supported(int HW, int C, int groups);
-int dtp_launch_reduce_groupnorm(const float* part, int splits, long long slab, int ldp, const float* bias, const f16* R, int ldr,
-                                f16* c_out, int ldc, f16* y, int ldy, const float* gamma, const float* beta, int B, int HW, int C,
-                                int groups, float eps, int silu, float* stats_ws, hipStream_t s, int Cx = 0);  // Cx: channels [0, Cx) from the slabs, the rest (a concatenation's other half) already in c_out; 0 = all
-// the split-K slabs of the conv that produced a GroupNorm's input (its reduce rides in the statistics pass)
+// GroupNorm over NHWC [B][HW][C] (row strides ldx / ldy), optional fused SiLU, fp32 statistics: the problem every launcher takes.
+// (x is const for all but the two launches with a GnReduceSrc: those sum the slabs and WRITE x before they normalise it)
+struct GnParams {
+  const f16* x; int ldx; f16* y; int ldy; const float *gamma, *beta; int B, HW, C, groups; float eps; int silu;
+};
+// the split-K slabs of the conv that produced a GroupNorm's input: the GroupNorm-side kernel sums them (+ bias, + residual R) and writes x
 struct GnReduceSrc {
   const float* part; int splits; long long slab; int ldp; const float* bias; const f16* R; int ldr;
 };
-// GroupNorm (no activation) folded into the Linear that consumes it: statistics pass (+ optional split-K reduce), then per-sample
-// weights / biases for a grouped GEMM on the raw tensor (norm.hip gn_fold_weights_kernel)
-int dtp_launch_groupnorm_stats(const f16* x, int ldx, float* ws, int B, int HW, int C, int groups, const GnReduceSrc* rd, hipStream_t s);
-int dtp_launch_gn_fold_weights(const f16* W, int ldw, const float* bias, const float* gamma, const float* beta, const float* ws, int B, int HW,
-                               int C, int Nout, int groups, float eps, f16* Wout, long long w_bs, float* bias_out, int bias_bs, hipStream_t s,
-                               int nchunk = 0);  // nchunk > 0: ws holds that many partials per sample (not the statistics pass's own count)
+int dtp_launch_groupnorm(const GnParams& p, float* stats_ws, hipStream_t s);
+size_t dtp_groupnorm_ws_bytes(int B, int HW, int C, int groups);
+int dtp_groupnorm_stat_chunks(int HW);  // pixel chunks per sample of dtp_launch_groupnorm_stats (partials [B][chunks][groups][2])
+// the apply pass alone, on partial sums [B][nchunk][groups][2] that somebody else produced (a convws_kernel launch with GF_GNSTATS)
+int dtp_launch_groupnorm_apply(const GnParams& p, const float* partial, int nchunk, hipStream_t s);
+// the statistics pass alone (partial sums -> ws; y, gamma, beta unused), with rd the producing conv's split-K reduce rides in it
+int dtp_launch_groupnorm_stats(const GnParams& p, float* ws, const GnReduceSrc* rd, hipStream_t s);
+// split-K reduce (+ bias, + residual) of a conv output fused with the GroupNorm (+SiLU) that consumes it: writes the fp16 conv
+// output p.x AND the normalised tensor p.y -- in one launch where dtp_reduce_groupnorm_supported() (HW <= 256), otherwise the
+// reduce rides in the statistics pass of the two-launch GroupNorm (needs stats_ws, dtp_groupnorm_ws_bytes).  Cx: channels [0, Cx)
+// come from the slabs, the rest (a concatenation's other half) are already in p.x; 0 = all
+bool dtp_reduce_groupnorm_supported(int HW, int C, int groups);
+int dtp_launch_reduce_groupnorm(const GnParams& p, const GnReduceSrc& rd, int Cx, float* stats_ws, hipStream_t s);
+// may a GroupNorm over [..][C] rows of pitch ldx take over the reduce of slabs of pitch ldp (residual pitch ldr, 0 = none)?  What BOTH
+// launchers with a reduce source accept: a claim (Builder::claim_reduce) may end in either
+bool dtp_groupnorm_reduce_accepts(int C, int groups, int ldx, int ldp, int ldr);
+// GroupNorm (no activation) folded into the Linear that consumes it: per-sample weights W diag(a_b) / biases bias + W d_b for a grouped
+// GEMM on the raw tensor, from the partial sums of the statistics pass (p: gamma, beta, B, HW, C, groups, eps; norm.hip
+// gn_fold_weights_kernel).  nchunk: partials per sample in `partial`, 0 = the statistics pass's own count
+int dtp_launch_gn_fold_weights(const GnParams& p, const float* partial, int nchunk, const f16* W, int ldw, const float* bias, int Nout, f16* Wout,
+                               long long w_bs, float* bias_out, int bias_bs, hipStream_t s);
 int dtp_launch_layernorm(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, int rows, int C,
                          float eps, hipStream_t s);
 int dtp_launch_softmax_rows(const f16* x, int ldx, f16* y, int ldy, int rows, int cols, float scale, hipStream_t s);

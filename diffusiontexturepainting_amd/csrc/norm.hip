@@ -706,12 +706,8 @@ static int gn_slab_channels(int HW, int C, int cpg) {
   return (C % cs) == 0 ? cs : C;
 }
 
-static int gn_chunks(int HW) {  // pixel chunks per batch item for the statistics pass (more chunks = more loads in flight)
-  int n = HW / 64;
-  if (n < 1) n = 1;
-  if (n > 128) n = 128;
-  return n;
-}
+// pixel chunks per batch item for the statistics pass (more chunks = more loads in flight)
+static int gn_chunks(int HW) { return std::max(1, std::min(128, HW / 64)); }
 
 int dtp_groupnorm_stat_chunks(int HW) { return gn_chunks(HW); }
 
@@ -719,141 +715,130 @@ size_t dtp_groupnorm_ws_bytes(int B, int HW, int C, int groups) {
   return (size_t)B * std::max(gn_chunks(HW), gn_chunks_reduce(HW)) * groups * 2 * sizeof(float);
 }
 
-// the two-launch GroupNorm; with `rd` the statistics pass also sums the producing conv's split-K slabs and writes x
-static int groupnorm_two_pass(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, float* ws, int B, int HW, int C,
-                              int groups, float eps, int silu, const GnReduceSrc* rd, hipStream_t s);
-
-int dtp_launch_groupnorm(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, float* ws, int B,
-                         int HW, int C, int groups, float eps, int silu, hipStream_t s) {
-  if ((C & 7) || (C % groups) || (ldx & 7) || (ldy & 7) || groups > 64) {
-    dtp_set_error("groupnorm: C=%d groups=%d ldx=%d ldy=%d unsupported", C, groups, ldx, ldy);
-    return DTP_ERR_ARG;
-  }
+// THE shape rule of every GroupNorm launcher: whole 16-byte chunks per row and per pitch (pass 0 for a pitch the launch has not), whole
+// groups of 4 or >= 8 channels (any_cpg: of any size -- the fold launcher, whose statistics come checked), at most max_groups of them (64
+// where a block owns a group slab, 32 where a block keeps the statistics of them all)
+static bool gn_shape_ok(int C, int groups, int max_groups, int ld_a, int ld_b, bool any_cpg = false) {
+  if ((C & 7) || (C % groups) || groups > max_groups || ((ld_a | ld_b) & 7)) return false;
   const int cpg = C / groups;
-  if (cpg < 4 || (cpg < 8 && cpg != 4)) { dtp_set_error("groupnorm: channels/group=%d unsupported", cpg); return DTP_ERR_ARG; }
-  if (HW <= 256) {
-    int G = 1;
-    while ((G * cpg) & 7) G *= 2;  // smallest slab of whole 16-byte chunks: cpg even -> G in {1, 2, 4}
-    if (G <= 4 && groups % G == 0) {
-      const float inv = 1.0f / ((float)HW * cpg);
-      dim3 grid(groups / G, B);
-      const int items = HW * ((G * cpg) >> 3);  // 16-byte chunks per block: one or two per thread
-      const dim3 blk(items >= 2048 ? 1024 : (items >= 512 ? 512 : 256));
-      if (G == 1) hipLaunchKernelGGL((gn_fused_kernel<1>), grid, blk, 0, s, x, ldx, y, ldy, gamma, beta, HW, cpg, silu, inv, eps);
-      else if (G == 2) hipLaunchKernelGGL((gn_fused_kernel<2>), grid, blk, 0, s, x, ldx, y, ldy, gamma, beta, HW, cpg, silu, inv, eps);
-      else hipLaunchKernelGGL((gn_fused_kernel<4>), grid, blk, 0, s, x, ldx, y, ldy, gamma, beta, HW, cpg, silu, inv, eps);
-      return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
-    }
-  }
-  return groupnorm_two_pass(x, ldx, y, ldy, gamma, beta, ws, B, HW, C, groups, eps, silu, nullptr, s);
+  return any_cpg || cpg == 4 || cpg >= 8;
+}
+// ... and of the two launchers that take a reduce source (slab pitch ldp, residual pitch ldr; 0 = none).  A claim is taken before its
+// consumer is known, so it must suit both -- and C / 8 <= 1024: the statistics pass of gn_linear / gn_conv3 puts a whole row of C
+// channels into one block, one thread per 8 channels (gn_launch_stats refuses more: "C too large")
+static bool gn_stats_accepts(int C, int groups, int ldx, int ldp) { return gn_shape_ok(C, groups, 32, ldx, 0) && !(ldp & 3); }
+static bool gn_reduce_accepts(int C, int groups, int ldx, int ldy, int ldp, int ldr) { return gn_shape_ok(C, groups, 64, ldx, ldy) && !(ldp & 3) && !(ldr & 7); }
+bool dtp_groupnorm_reduce_accepts(int C, int groups, int ldx, int ldp, int ldr) {
+  return gn_stats_accepts(C, groups, ldx, ldp) && gn_reduce_accepts(C, groups, ldx, 0, ldp, ldr) && C / 8 <= 1024;
 }
 
-static int groupnorm_two_pass(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, float* ws, int B, int HW, int C,
-                              int groups, float eps, int silu, const GnReduceSrc* rd, hipStream_t s) {
-  const int cpg = C / groups;
-  const int cs = rd ? gn_slab_channels(HW, C, cpg) : C;       // channels per block of the statistics pass
-  const int nch = cs / 8;
-  const int nchunk = rd ? gn_chunks_reduce(HW) : gn_chunks(HW);
-  const int ppc = (HW + nchunk - 1) / nchunk;
-  // few, fat blocks: up to 1024 threads so that many 16-byte loads are in flight per block while the number of
-  // partial sums the apply kernel has to re-reduce stays small
-  int rows = 1024 / nch;
-  if (rows > ppc) rows = ppc;
-  if (rows < 1) rows = 1;
-  const int threads = nch * rows;
-  if (threads > 1024) { dtp_set_error("groupnorm: C too large"); return DTP_ERR_ARG; }
-  if (rd)
-    hipLaunchKernelGGL(gn_stats_reduce_kernel, dim3(nchunk, B, C / cs), dim3(threads), 0, s, rd->part, rd->splits, rd->slab, rd->ldp, rd->bias, rd->R,
-                       rd->ldr, (f16*)x, ldx, ws, HW, cs, cpg, groups, ppc);
-  else
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(threads), 0, s, x, ldx, ws, HW, C, cpg, groups, ppc);
-  const long long per_batch = (long long)HW * (C / 8);
-  // one fat block per CU (tools/diag_gn.py sweep: 1024 threads x <= 256 blocks is 5-7 % ahead of 256 x 768): every block
-  // re-reduces the partials of its batch item first, so fewer blocks re-read them less often
-  const int at = 1024;
-  long long bx = (per_batch + at - 1) / at;
-  const long long cap = std::max<long long>(1, 256 / B);
-  if (bx > cap) bx = cap;
-  const int hoist = gn_apply_grid(&bx, C / 8);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3((int)bx, B), dim3(at), 0, s, x, ldx, y, ldy, gamma, beta, ws, nchunk, HW, C, cpg,
-                     groups, silu, 1.0f / ((float)HW * cpg), eps, hoist);
-  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
-}
-
-int dtp_launch_groupnorm_apply(const f16* x, int ldx, f16* y, int ldy, const float* gamma, const float* beta, const float* partial, int nchunk,
-                               int B, int HW, int C, int groups, float eps, int silu, hipStream_t s) {
-  if ((C & 7) || (C % groups) || (ldx & 7) || (ldy & 7) || groups > 32 || nchunk < 1 || C / groups < 4 || (C / groups < 8 && C / groups != 4)) {
-    dtp_set_error("groupnorm apply: C=%d groups=%d ldx=%d ldy=%d nchunk=%d unsupported", C, groups, ldx, ldy, nchunk);
-    return DTP_ERR_ARG;
-  }
-  const long long per_batch = (long long)HW * (C / 8);
-  long long bx = (per_batch + 1023) / 1024;
-  const long long cap = std::max<long long>(1, 256 / B);
-  if (bx > cap) bx = cap;
-  const int hoist = gn_apply_grid(&bx, C / 8);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3((int)bx, B), dim3(1024), 0, s, x, ldx, y, ldy, gamma, beta, partial, nchunk, HW, C, C / groups, groups, silu,
-                     1.0f / ((float)HW * (C / groups)), eps, hoist);
-  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
-}
-
-// statistics pass alone (partial sums -> ws), optionally with the producing conv's split-K reduce folded in (rd): first half of
-// GroupNorm-folded-into-its-Linear (gn_fold_weights_kernel)
-int dtp_launch_groupnorm_stats(const f16* x, int ldx, float* ws, int B, int HW, int C, int groups, const GnReduceSrc* rd, hipStream_t s) {
-  if ((C & 7) || (C % groups) || (ldx & 7) || groups > 32 || C / groups < 4 || (C / groups < 8 && C / groups != 4) || (rd && (rd->ldp & 3))) {
-    dtp_set_error("groupnorm stats: C=%d groups=%d ldx=%d unsupported", C, groups, ldx);
-    return DTP_ERR_ARG;
-  }
-  // the consumer (gn_fold_weights_kernel) reads gn_chunks(HW) partials per sample: keep the plain chunking and whole-C blocks here
-  const int cpg = C / groups, nch = C / 8, nchunk = gn_chunks(HW), ppc = (HW + nchunk - 1) / nchunk;
-  int rows = 1024 / nch;
-  if (rows > ppc) rows = ppc;
-  if (rows < 1) rows = 1;
-  const int threads = nch * rows;
-  if (threads > 1024) { dtp_set_error("groupnorm: C too large"); return DTP_ERR_ARG; }
-  if (rd)
-    hipLaunchKernelGGL(gn_stats_reduce_kernel, dim3(nchunk, B, 1), dim3(threads), 0, s, rd->part, rd->splits, rd->slab, rd->ldp, rd->bias, rd->R, rd->ldr,
-                       (f16*)x, ldx, ws, HW, C, cpg, groups, ppc);
-  else
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, B), dim3(threads), 0, s, x, ldx, ws, HW, C, cpg, groups, ppc);
-  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
-}
-
-// second half: per-sample weights W diag(a_b) and biases bias + W d_b from the partial sums `ws` of dtp_launch_groupnorm_stats
-int dtp_launch_gn_fold_weights(const f16* W, int ldw, const float* bias, const float* gamma, const float* beta, const float* ws, int B, int HW,
-                               int C, int Nout, int groups, float eps, f16* Wout, long long w_bs, float* bias_out, int bias_bs, hipStream_t s, int nchunk) {
-  if ((C & 7) || C > 2048 || (C % groups) || groups > 32 || (ldw & 7) || C / 8 > 256) {
-    dtp_set_error("gn fold: C=%d groups=%d ldw=%d unsupported", C, groups, ldw);
-    return DTP_ERR_ARG;
-  }
-  hipLaunchKernelGGL(gn_fold_weights_kernel, dim3((Nout + 7) / 8, B), dim3(256), 0, s, W, ldw, bias, gamma, beta, ws, nchunk > 0 ? nchunk : gn_chunks(HW), C, C / groups, groups,
-                     1.0f / ((float)HW * (C / groups)), eps, Nout, Wout, w_bs, bias_out, bias_bs);
-  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
-}
-
-// Can the split-K reduce of a [B*HW][C] conv output be folded into the GroupNorm that consumes it?  (single-launch GroupNorm
-// shapes only; at most 4 items of 8 channels per thread)
-bool dtp_reduce_groupnorm_supported(int HW, int C, int groups) {
-  if (HW > 256 || (C & 7) || (C % groups) || groups > 64) return false;
-  const int cpg = C / groups;
-  if (cpg < 4 || (cpg < 8 && cpg != 4)) return false;
+// The single-launch kernels' block: G groups = the smallest slab of whole 16-byte chunks (cpg even -> G in {1, 2, 4}; G = 0: no such
+// slab divides the groups), `items` chunks per block at one or two per thread -- 1024 threads from `wide` items on
+struct GnSlab { int G, items, threads; };
+static GnSlab gn_slab(int HW, int cpg, int groups, int wide) {
   int G = 1;
   while ((G * cpg) & 7) G *= 2;
-  if (G > 4 || groups % G) return false;
+  if (G > 4 || groups % G) return {0, 0, 0};
   const int items = HW * ((G * cpg) >> 3);
-  const int blk = items >= 1024 ? 1024 : (items >= 512 ? 512 : 256);  // reduce kernel: as many waves as items allow (latency-bound slab reads)
-  return (items + blk - 1) / blk <= 4;
+  return {G, items, items >= wide ? 1024 : (items >= 512 ? 512 : 256)};
 }
 
-int dtp_launch_reduce_groupnorm(const float* part, int splits, long long slab, int ldp, const float* bias, const f16* R, int ldr,
-                                f16* c_out, int ldc, f16* y, int ldy, const float* gamma, const float* beta, int B, int HW, int C,
-                                int groups, float eps, int silu, float* stats_ws, hipStream_t s, int Cx) {
+// statistics pass: nchunk pixel chunks per sample, cs channels per block; with `rd` it also sums the producing conv's split-K slabs and writes x
+static int gn_launch_stats(const GnParams& p, float* ws, const GnReduceSrc* rd, int nchunk, int cs, hipStream_t s) {
+  const int cpg = p.C / p.groups, nch = cs / 8, ppc = (p.HW + nchunk - 1) / nchunk;
+  // few, fat blocks: up to 1024 threads so that many 16-byte loads are in flight per block while the number of
+  // partial sums the apply kernel has to re-reduce stays small
+  const int threads = nch * std::max(1, std::min(1024 / nch, ppc));
+  if (threads > 1024) { dtp_set_error("groupnorm: C too large"); return DTP_ERR_ARG; }
+  if (rd)
+    hipLaunchKernelGGL(gn_stats_reduce_kernel, dim3(nchunk, p.B, p.C / cs), dim3(threads), 0, s, rd->part, rd->splits, rd->slab, rd->ldp, rd->bias, rd->R,
+                       rd->ldr, (f16*)p.x, p.ldx, ws, p.HW, cs, cpg, p.groups, ppc);
+  else
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, p.B), dim3(threads), 0, s, p.x, p.ldx, ws, p.HW, p.C, cpg, p.groups, ppc);
+  return DTP_OK;  // (launched: the caller asks hipGetLastError once, behind its last launch)
+}
+
+// apply pass on nchunk partials per sample
+static int gn_launch_apply(const GnParams& p, const float* partial, int nchunk, hipStream_t s) {
+  const int cpg = p.C / p.groups;
+  // one fat block per CU (tools/diag_gn.py sweep: 1024 threads x <= 256 blocks is 5-7 % ahead of 256 x 768): every block
+  // re-reduces the partials of its batch item first, so fewer blocks re-read them less often
+  long long bx = std::min<long long>(((long long)p.HW * (p.C / 8) + 1023) / 1024, std::max(1, 256 / p.B));
+  const int hoist = gn_apply_grid(&bx, p.C / 8);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3((int)bx, p.B), dim3(1024), 0, s, p.x, p.ldx, p.y, p.ldy, p.gamma, p.beta, partial, nchunk, p.HW, p.C, cpg,
+                     p.groups, p.silu, 1.0f / ((float)p.HW * cpg), p.eps, hoist);
+  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
+}
+
+// the two-launch GroupNorm; with `rd` the reduce rides in a statistics pass cut along pixels AND channels
+static int groupnorm_two_pass(const GnParams& p, float* ws, const GnReduceSrc* rd, hipStream_t s) {
+  const int nchunk = rd ? gn_chunks_reduce(p.HW) : gn_chunks(p.HW);
+  const int rc = gn_launch_stats(p, ws, rd, nchunk, rd ? gn_slab_channels(p.HW, p.C, p.C / p.groups) : p.C, s);
+  return rc ? rc : gn_launch_apply(p, ws, nchunk, s);
+}
+
+int dtp_launch_groupnorm(const GnParams& p, float* ws, hipStream_t s) {
+  if (!gn_shape_ok(p.C, p.groups, 64, p.ldx, p.ldy)) {
+    dtp_set_error("groupnorm: C=%d groups=%d ldx=%d ldy=%d unsupported", p.C, p.groups, p.ldx, p.ldy);
+    return DTP_ERR_ARG;
+  }
+  const int cpg = p.C / p.groups;
+  const GnSlab b = gn_slab(p.HW, cpg, p.groups, 2048);
+  if (p.HW > 256 || !b.G) return groupnorm_two_pass(p, ws, nullptr, s);
+  const float inv = 1.0f / ((float)p.HW * cpg);
+  const dim3 grid(p.groups / b.G, p.B), blk(b.threads);
+#define DTP_GN(GG) hipLaunchKernelGGL((gn_fused_kernel<GG>), grid, blk, 0, s, p.x, p.ldx, p.y, p.ldy, p.gamma, p.beta, p.HW, cpg, p.silu, inv, p.eps)
+  if (b.G == 1) DTP_GN(1); else if (b.G == 2) DTP_GN(2); else DTP_GN(4);
+#undef DTP_GN
+  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
+}
+
+int dtp_launch_groupnorm_apply(const GnParams& p, const float* partial, int nchunk, hipStream_t s) {
+  if (!gn_shape_ok(p.C, p.groups, 32, p.ldx, p.ldy) || nchunk < 1) {
+    dtp_set_error("groupnorm apply: C=%d groups=%d ldx=%d ldy=%d nchunk=%d unsupported", p.C, p.groups, p.ldx, p.ldy, nchunk);
+    return DTP_ERR_ARG;
+  }
+  return gn_launch_apply(p, partial, nchunk, s);
+}
+
+int dtp_launch_groupnorm_stats(const GnParams& p, float* ws, const GnReduceSrc* rd, hipStream_t s) {
+  if (!gn_stats_accepts(p.C, p.groups, p.ldx, rd ? rd->ldp : 0)) {
+    dtp_set_error("groupnorm stats: C=%d groups=%d ldx=%d unsupported", p.C, p.groups, p.ldx);
+    return DTP_ERR_ARG;
+  }
+  // the consumers (gn_fold_weights_kernel, GF_GNAPPLY) read gn_chunks(HW) partials per sample: keep the plain chunking and whole-C blocks here
+  const int rc = gn_launch_stats(p, ws, rd, gn_chunks(p.HW), p.C, s);
+  return rc ? rc : (hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP);
+}
+
+int dtp_launch_gn_fold_weights(const GnParams& p, const float* partial, int nchunk, const f16* W, int ldw, const float* bias, int Nout, f16* Wout,
+                               long long w_bs, float* bias_out, int bias_bs, hipStream_t s) {
+  if (!gn_shape_ok(p.C, p.groups, 32, ldw, 0, true) || p.C > 2048) {
+    dtp_set_error("gn fold: C=%d groups=%d ldw=%d unsupported", p.C, p.groups, ldw);
+    return DTP_ERR_ARG;
+  }
+  const int cpg = p.C / p.groups;
+  hipLaunchKernelGGL(gn_fold_weights_kernel, dim3((Nout + 7) / 8, p.B), dim3(256), 0, s, W, ldw, bias, p.gamma, p.beta, partial, nchunk > 0 ? nchunk : gn_chunks(p.HW),
+                     p.C, cpg, p.groups, 1.0f / ((float)p.HW * cpg), p.eps, Nout, Wout, w_bs, bias_out, bias_bs);
+  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
+}
+
+// Can the split-K reduce of a [B*HW][C] conv output be folded into the GroupNorm that consumes it in ONE launch?  (small maps; at most
+// 4 items of 8 channels per thread; the reduce kernel takes as many waves as the items allow: latency-bound slab reads)
+bool dtp_reduce_groupnorm_supported(int HW, int C, int groups) {
+  if (HW > 256 || !gn_shape_ok(C, groups, 64, 0, 0)) return false;
+  const GnSlab b = gn_slab(HW, C / groups, groups, 1024);
+  return b.G && (b.items + b.threads - 1) / b.threads <= 4;
+}
+
+int dtp_launch_reduce_groupnorm(const GnParams& p, const GnReduceSrc& rd, int Cx, float* stats_ws, hipStream_t s) {
+  const int HW = p.HW, C = p.C, groups = p.groups;
   if (Cx <= 0 || Cx > C) Cx = C;
   if (Cx < C && ((Cx & 7) || !dtp_reduce_groupnorm_supported(HW, C, groups))) {
     dtp_set_error("reduce+groupnorm over a concatenation: HW=%d C=%d Cx=%d unsupported (single-launch shapes only)", HW, C, Cx);
     return DTP_ERR_ARG;
   }
-  if ((ldp & 3) || (ldc & 7) || (ldy & 7) || (R && (ldr & 7)) || (C & 7) || (C % groups) || groups > 64 || C / groups < 4 ||
-      (C / groups < 8 && C / groups != 4)) {
+  if (!gn_reduce_accepts(C, groups, p.ldx, p.ldy, rd.ldp, rd.R ? rd.ldr : 0)) {
     dtp_set_error("reduce+groupnorm: HW=%d C=%d groups=%d unsupported", HW, C, groups);
     return DTP_ERR_ARG;
   }
@@ -868,18 +853,14 @@ int dtp_launch_reduce_groupnorm(const float* part, int splits, long long slab, i
 #endif
   if (Cx == C && (!dtp_reduce_groupnorm_supported(HW, C, groups) || (!small_fused && stats_ws && HW >= 32))) {  // reduce folded into the statistics pass, then the apply pass
     if (!stats_ws) { dtp_set_error("reduce+groupnorm: the two-pass form needs the statistics workspace"); return DTP_ERR_ARG; }
-    const GnReduceSrc rd = {part, splits, slab, ldp, bias, R, ldr};
-    return groupnorm_two_pass(c_out, ldc, y, ldy, gamma, beta, stats_ws, B, HW, C, groups, eps, silu, &rd, s);
+    return groupnorm_two_pass(p, stats_ws, &rd, s);
   }
   const int cpg = C / groups;
-  int G = 1;
-  while ((G * cpg) & 7) G *= 2;
+  const GnSlab b = gn_slab(HW, cpg, groups, 1024);
   const float inv = 1.0f / ((float)HW * cpg);
-  dim3 grid(groups / G, B);
-  const int items = HW * ((G * cpg) >> 3);
-  const dim3 blk(items >= 1024 ? 1024 : (items >= 512 ? 512 : 256));
-#define DTP_RGN(GG) hipLaunchKernelGGL((gn_reduce_fused_kernel<GG, 4>), grid, blk, 0, s, part, splits, slab, ldp, bias, R, ldr, c_out, ldc, y, ldy, gamma, beta, HW, cpg, silu, inv, eps, Cx)
-  if (G == 1) DTP_RGN(1); else if (G == 2) DTP_RGN(2); else DTP_RGN(4);
+  const dim3 grid(groups / b.G, p.B), blk(b.threads);
+#define DTP_RGN(GG) hipLaunchKernelGGL((gn_reduce_fused_kernel<GG, 4>), grid, blk, 0, s, rd.part, rd.splits, rd.slab, rd.ldp, rd.bias, rd.R, rd.ldr, (f16*)p.x, p.ldx, p.y, p.ldy, p.gamma, p.beta, HW, cpg, p.silu, inv, p.eps, Cx)
+  if (b.G == 1) DTP_RGN(1); else if (b.G == 2) DTP_RGN(2); else DTP_RGN(4);
 #undef DTP_RGN
   return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
 }

@@ -290,6 +290,18 @@ def reduce_groupnorm(part, gamma, beta, bias=None, resid=None, groups=32, eps=1e
     return out, y
 
 
+def groupnorm_stats_apply(gamma, beta, x=None, part=None, bias=None, resid=None, groups=32, eps=1e-5, silu=False):
+    """The statistics pass, then the apply pass from its partial sums.  part f32 [splits, B, HW, C] split-K slabs of a conv (+ bias, + resid):
+    the statistics pass sums them -> (conv output f16 [B,HW,C], GroupNorm(+SiLU) of it); part None: GroupNorm of x f16 [B,HW,C] -> (x, y)."""
+    lib = _lib.load()
+    sp, (b, hw, c) = (part.shape[0], part.shape[1:]) if part is not None else (0, x.shape)
+    out = x if part is None else torch.empty(b, hw, c, dtype=torch.float16, device=part.device)
+    y = torch.empty_like(out)
+    check(lib.dtp_op_groupnorm_stats_apply(ptr(part), sp, ptr(bias), ptr(resid), ptr(out), ptr(y), ptr(gamma), ptr(beta), b, hw, c, groups, eps, int(silu),
+                                           _stream()), "groupnorm_stats_apply")
+    return out, y
+
+
 def xattn(x, w1, b1, lns1, st_in, w2, b2, n_samples, sm_valid=14, ln_eps=1e-5, row_stats=False, ct=0):
     """Fused cross-attention GEMM pair (xattn.hip): x f16 [N*S, C]; w1 f16 [N*128, C]; b1 / lns1 f32 [N*128]; st_in f32 [parts, N*S, 2];
     w2 f16 [N*roundup(C,128), 128]; b2 f32 [C] -> y f16 [N*S, C] (and the [ceil(C/128), N*S, 2] row-statistics partials).

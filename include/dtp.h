@@ -516,6 +516,11 @@ int dtp_op_groupnorm(const void* x, int ldx, void* y, int ldy, const float* gamm
  * with DTP_GF_GNSTATS): y = GroupNorm(x) (+SiLU) without a statistics pass over x */
 int dtp_op_groupnorm_apply(const void* x, int ldx, void* y, int ldy, const float* gamma, const float* beta, const float* partial, int nchunk,
                            int B, int HW, int C, int groups, float eps, int silu, dtp_stream s);
+/* the two halves as the engine runs them on a claimed reduce: the statistics pass sums the split-K slabs part f32 [splits][B*HW][C]
+ * (+ bias[C], + resid f16 [B*HW][C]) and writes x f16 [B*HW][C] (part == NULL: plain statistics of x as it is), then the apply pass
+ * normalises from its partial sums: y = GroupNorm(x) (+SiLU) */
+int dtp_op_groupnorm_stats_apply(const float* part, int splits, const float* bias, const void* resid, void* x, void* y, const float* gamma,
+                                 const float* beta, int B, int HW, int C, int groups, float eps, int silu, dtp_stream s);
 /* measured ceilings of this GPU (bench.py roofline.peak_measured): dense fp16 MFMA TFLOP/s with random operands on every SIMD, and
  * the HBM GB/s (read + write) of a 512 MiB float4 copy; blocking, ~50 ms */
 int dtp_op_measure_peaks(double* mfma_f16_tflops, double* hbm_copy_gbs);

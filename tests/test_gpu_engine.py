@@ -99,9 +99,17 @@ CLAIM_REMOVED = {
     "DTP_NO_GNA_LNLIN": ("(apply in proj_in)",),
     "DTP_NO_FOLD_GN": ("(apply in proj_in)", "gn-fold", "reduce+gn-stats"),
 }
-# STILL TO BE FILLED IN: which markers ARE there per case.  That table depends on the shipped tune table and has to be recorded from a
-# run of the library built from the parent of the engine.hip split (python tools/program_dump.py prints it), together with the check that
-# every marker is present in at least one case; no GPU could be had when this test was written (profiles/engine_split_ab.txt).
+# What IS there per case at 256^2, n = 3 with the shipped tune table (tools/program_dump.py prints the counts; recorded from the library
+# before the launchers took GnParams, profiles/gn_launchers_ab.txt: the least frequent are gn-apply, 2 launches, and reduce+gn-stats /
+# (apply in proj_in), 3).  The default program has no gn-fold: the fold is what gn_linear does without gna_lnlin.
+CLAIM_PRESENT = {
+    "default": ("(reduce in gn)", "reduce+gn B=", "reduce(front", "reduce+gn-stats", "(+gn stats)", "gn-apply", "(apply in proj_in)"),
+    "DTP_NO_FUSE_REDUCE_GN": ("(+gn stats)", "gn-apply", "(apply in proj_in)"),
+    "DTP_NO_GN_EPILOGUE": ("(reduce in gn)", "reduce+gn B=", "reduce(front", "reduce+gn-stats", "(apply in proj_in)"),
+    "DTP_NO_REDUCE_IN_CONCAT_GN": ("(reduce in gn)", "reduce+gn B=", "reduce+gn-stats", "(+gn stats)", "gn-apply", "(apply in proj_in)"),
+    "DTP_NO_GNA_LNLIN": ("(reduce in gn)", "reduce+gn B=", "reduce(front", "reduce+gn-stats", "(+gn stats)", "gn-apply", "gn-fold"),
+    "DTP_NO_FOLD_GN": ("(reduce in gn)", "reduce+gn B=", "reduce(front", "(+gn stats)", "gn-apply"),
+}
 
 
 @pytest.fixture(scope="module")
@@ -123,7 +131,7 @@ def claim_oracle():
 def test_unet_groupnorm_claims_vs_oracle(monkeypatch, tmp_path, claim_oracle, case):
     """One 256^2 UNet evaluation (n = 3) against the fp32 oracle, by default and with each switch of the GroupNorm claim path set alone
     (a context reads them when it is created); the claim markers a switch removes must be gone from the launch labels.  The oracle
-    evaluation is shared by the six cases.  Not yet run on a GPU, and the present-marker table is missing: see above."""
+    evaluation is shared by the six cases."""
     from diffusiontexturepainting_amd.inpainter import MI355ConditionalInpainter
     if case != "default":
         monkeypatch.setenv(case, "1")
@@ -139,6 +147,11 @@ def test_unet_groupnorm_claims_vs_oracle(monkeypatch, tmp_path, claim_oracle, ca
     print("unet", case, "rel err", e, "claim markers", found)
     assert e < 1e-2
     assert not set(found) & set(CLAIM_REMOVED[case])
+    assert set(CLAIM_PRESENT[case]) <= set(found)
+
+
+def test_every_claim_marker_is_expected_in_some_case():
+    assert set().union(*CLAIM_PRESENT.values()) == set(CLAIM_MARKERS)
 
 
 def test_vae_encode_vs_oracle(env):

@@ -868,6 +868,100 @@ def test_groupnorm_applied_on_the_resident_fragments_of_the_linear(ops, b, hw, c
     assert torch.allclose(tot[:, 0], gf.sum(dim=1), rtol=1e-4, atol=1e-2) and torch.allclose(tot[:, 1], (gf * gf).sum(dim=1), rtol=1e-4, atol=1e-2)
 
 
+def _slabs_sum(b, hw, c, splits, bias, resid, seed):
+    """split-K slabs (+ bias, + residual) of a conv output and fp16(their sum), the fp32 additions in the kernels' order"""
+    g = torch.Generator().manual_seed(seed)
+    part = torch.randn(splits, b, hw, c, generator=g) * 0.7
+    bv = torch.randn(c, generator=g) if bias else None
+    rv = rnd(b, hw, c, seed=seed + 1) if resid else None
+    acc = part[0].clone()
+    for z in range(1, splits):
+        acc += part[z]
+    if bias:
+        acc += bv
+    if resid:
+        acc += rv.float()
+    return part, bv, rv, acc.half()
+
+
+def _gn_ref(x, gamma, beta, eps=1e-5, groups=32):
+    return F.group_norm(x.float().permute(0, 2, 1), groups, gamma, beta, eps).permute(0, 2, 1)
+
+
+@pytest.mark.parametrize("b,hw,c,splits,bias,resid", [(2, 1024, 320, 2, True, True),    # base
+                                                      (1, 1000, 640, 3, False, True),   # 15 chunks of 67 pixels, the last one short
+                                                      (3, 16, 1280, 4, True, False),    # one chunk, the thread-row clamp
+                                                      (2, 64, 128, 0, False, False)])   # no slabs, 4 channels per group
+def test_groupnorm_stats_with_reduce_then_apply(ops, b, hw, c, splits, bias, resid):
+    """What gn_linear / gn_conv3 run on a claimed reduce: the statistics pass alone with the producer's split-K slabs as its source (it
+    writes the conv output, BIT-exactly fp16(sum of slabs + bias + residual), and partial sums that outlive the launch), then the apply
+    pass from those partials.  No slabs: the plain statistics pass."""
+    g = torch.Generator().manual_seed(245)
+    gamma, beta = 1 + 0.2 * torch.randn(c, generator=g), 0.2 * torch.randn(c, generator=g)
+    if splits:
+        part, bv, rv, conv = _slabs_sum(b, hw, c, splits, bias, resid, seed=246)
+        out, y = ops.groupnorm_stats_apply(gamma.cuda(), beta.cuda(), part=part.cuda(), bias=bv.cuda() if bias else None, resid=rv.cuda() if resid else None)
+    else:
+        conv = rnd(b, hw, c, seed=246) * 2 + 0.5
+        out, y = ops.groupnorm_stats_apply(gamma.cuda(), beta.cuda(), x=conv.cuda())
+    assert torch.equal(out.cpu(), conv)
+    close(y, _gn_ref(conv, gamma, beta))
+
+
+def test_groupnorm_launchers_refuse_what_they_do_not_take(ops):
+    """The acceptance set of every GroupNorm launcher, pinned from both sides: a shape just outside it raises (DTP_ERR_ARG before any launch),
+    its neighbour inside -- a shape of the tests above, 32 groups -- still runs.  (A residual pitch that is no multiple of 8 cannot be
+    expressed through reduce_groupnorm(): the wrapper's residual has the pitch of the slabs.)"""
+    from diffusiontexturepainting_amd._lib import DtpError
+    g = torch.Generator().manual_seed(345)
+
+    def affine(c):
+        return (1 + 0.2 * torch.randn(c, generator=g)).cuda(), (0.2 * torch.randn(c, generator=g)).cuda()
+
+    def x16(b, hw, c):
+        return (rnd(b, hw, c, seed=346) * 2 + 0.5).cuda()
+
+    for c, groups in [(48, 8), (36, 9), (520, 65), (320, 7)]:  # 6 channels per group; C % 8; more than 64 groups; C % groups
+        with pytest.raises(DtpError):
+            ops.groupnorm(x16(1, 64, c), *affine(c), groups=groups)
+    x, (gamma, beta) = x16(1, 1024, 128), affine(128)  # 4 channels per group
+    close(ops.groupnorm(x, gamma, beta), _gn_ref(x.cpu(), gamma.cpu(), beta.cpu()))
+
+    x, (gamma, beta) = x16(2, 256, 640), affine(640)
+    xf = x.float().view(2, 256, 32, 20)
+    partial = torch.stack([xf.sum(dim=(1, 3)), (xf * xf).sum(dim=(1, 3))], dim=-1).view(2, 1, 32, 2).contiguous()
+    with pytest.raises(DtpError):  # the apply pass keeps the statistics of at most 32 groups
+        ops.groupnorm_apply(x16(1, 64, 512), *affine(512), torch.zeros(1, 1, 64, 2, device="cuda"), groups=64)
+    with pytest.raises(DtpError):  # no partials
+        ops.groupnorm_apply(x, gamma, beta, partial[:, :0])
+    close(ops.groupnorm_apply(x, gamma, beta, partial), _gn_ref(x.cpu(), gamma.cpu(), beta.cpu()))
+
+    part, _, _, front = _slabs_sum(1, 1024, 640, 2, False, False, seed=347)
+    with pytest.raises(DtpError):  # a concatenation outside the single-launch shapes
+        ops.reduce_groupnorm(part.cuda(), *affine(960), skip=x16(1, 1024, 320))
+    part, _, _, front = _slabs_sum(1, 64, 640, 3, False, False, seed=347)
+    skip, (gamma, beta) = x16(1, 64, 320), affine(960)
+    out, y = ops.reduce_groupnorm(part.cuda(), gamma, beta, skip=skip)
+    cat = torch.cat([front, skip.cpu()], dim=-1)
+    assert torch.equal(out.cpu(), cat)
+    close(y, _gn_ref(cat, gamma.cpu(), beta.cpu()))
+
+    # the fold holds at most 2048 channels.  C = 2056 never reaches it through the wrapper: the statistics pass in front refuses 2056 % 32;
+    # C = 2112 (66 per group) does: that statistics pass runs, then the fold launcher refuses
+    for c in (2056, 2112):
+        with pytest.raises(DtpError, match="groupnorm stats" if c == 2056 else "gn fold"):
+            ops.gn_fold_weights(x16(1, 64, c), torch.zeros(128, c, dtype=torch.float16, device="cuda"), 128, None, *affine(c))
+    x, (gamma, beta) = x16(2, 1024, 640), affine(640)
+    w = rnd(640, 640, seed=348, scale=640 ** -0.5).float()
+    wf, bf = ops.gn_fold_weights(x, ops.pack_linear(w.cuda()), 640, torch.zeros(640, device="cuda"), gamma, beta, eps=1e-5)
+    from diffusiontexturepainting_amd._lib import GF_BIAS
+    got = ops.gemm(x.view(2 * 1024, 640), wf.view(-1, wf.shape[-1]), 640, 640, bias=bf.view(-1), flags=GF_BIAS, batch=2)
+    close(got.view(2, 1024, 640), F.linear(_gn_ref(x.cpu(), gamma.cpu(), beta.cpu()), w), tol=4e-3)
+
+    with pytest.raises(DtpError):  # 6 channels per group (its accepted neighbours: test_groupnorm_stats_with_reduce_then_apply)
+        ops.groupnorm_stats_apply(*affine(48), x=x16(1, 64, 48), groups=8)
+
+
 @pytest.mark.parametrize("rows,c", [(1000, 320), (333, 640), (64, 1280), (14, 768), (5, 2048)])
 def test_layernorm(ops, rows, c):
     x = rnd(rows, c, seed=50) * 1.5 + 0.3
