@@ -175,6 +175,10 @@ SYMBOLS = {
     "dtp_mesh_stroke": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(MeshStamp), _i, C.POINTER(Settings), C.POINTER(MeshStrokeOpts), _vp, _vp]),
     "dtp_op_mesh_render": (_i, [_vp, C.POINTER(_f * 12), _f, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "dtp_op_mesh_backproject": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "dtp_mesh_stroke_bleed": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(MeshStamp), _i, C.POINTER(Settings), C.POINTER(MeshStrokeOpts), _vp, _i, _vp]),
+    "dtp_mesh_bleed": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i * 4), _vp]),
+    "dtp_op_mesh_coverage": (_i, [_vp, _i, _i, _vp, _vp]),
+    "dtp_mesh_bleed_offsets": (_i, [_i, C.POINTER(_i), C.POINTER(C.c_byte)]),
 }
 
 

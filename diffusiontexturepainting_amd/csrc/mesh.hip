@@ -5,6 +5,8 @@
 // these are written from the contract of include/dtp.h: coverage in exact integer arithmetic on vertices snapped to 1/256 pixel,
 // interpolation in fp32 one rounded operation at a time (contraction is off for this whole file), a winner per pixel that does not depend
 // on the order in which faces are visited.  Plain HIP: vector loads, stores and atomics only.
+// The bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed) pads the UV charts after a backprojection: the texels no face of
+// the mesh covers take the nearest covered texel, by the same integer coverage.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stdio.h>
@@ -15,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "mesh_host.h"
 #include "stamp.h"
 
 namespace {
@@ -22,14 +25,15 @@ namespace {
 constexpr int SNAP_MAX = 1 << 26;  // snapped coordinates are clamped to +-2^26: every edge function fits an int64 with room to spare
 constexpr int CHUNK = 256;         // faces staged in LDS per round of a tile
 constexpr int MAX_FACES = 1 << 20, MAX_TEX = 32768, MAX_WIN = 4096;  // (the pixel and texel ranges of a face are packed in 16 bits)
+constexpr int SMALL_BOX = 1024;    // coverage build: a face whose texel box holds at most this many centres is rasterised by one wave
 
 enum { MF_RASTER = 1, MF_FRONT = 2, MF_UPRIGHT = 4 };  // finite with a non-zero area; unit normal z >= 0; >= 0.5 (not steep)
 
 // what one stamp's projection leaves per face: window position snapped to 1/256 pixel, camera z, NDC (the backprojection's feature)
 struct FaceRec { int X[3], Y[3]; float z[3], nx[3], ny[3]; int flags; };
 // per mesh, on the device: the faces that can cover a pixel centre of the window, those that are backprojected, and the texel bounding box
-// of the latter (x0, y0, x1, y1)
-struct MeshState { int n_win, n_val, bb[4]; };
+// of the latter (x0, y0, x1, y1); n_big: the faces a coverage build hands to its tile pass
+struct MeshState { int n_win, n_val, bb[4], n_big; };
 struct MeshCam { float m[12], fov; };  // travels as a kernel argument
 
 struct Mesh {
@@ -43,6 +47,10 @@ struct Mesh {
   int4* win = nullptr;     // [F] {face, px0 | px1 << 16, py0 | py1 << 16, 0}
   int4* val = nullptr;     // [F] the same in texels
   MeshState* state = nullptr;
+  // the texels of a cov_H x cov_W texture that any face covers, 1 bit per texel in rows of (cov_W + 31) / 32 words, followed by the
+  // table of bleed offsets (2 * MESH_MAX_OFF bytes); built at the first use of a size, one per mesh
+  unsigned int* cov = nullptr;
+  int cov_H = 0, cov_W = 0;
   double lo[3], hi[3];     // the vertices' bounding box (host): a window it misses is skipped without a launch
 };
 
@@ -328,6 +336,129 @@ __global__ void mesh_disc_kernel(unsigned char* __restrict__ mask, int R) {
   }
 }
 
+// ---------------------------------------------------------------- device: coverage and the bleed pass
+// a face in texture space: false for a zero area or a texel box without a centre
+__device__ __forceinline__ bool face_texels(const float* __restrict__ uv, int H, int W, int X[3], int Y[3], int& x0, int& x1, int& y0, int& y1) {
+  snap_uvs(uv, H, W, X, Y);
+  if (orient(X[0], Y[0], X[1], Y[1], X[2], Y[2]) == 0) return false;
+  centre_range(min3(X[0], X[1], X[2]), max3(X[0], X[1], X[2]), W, x0, x1);
+  centre_range(min3(Y[0], Y[1], Y[2]), max3(Y[0], Y[1], Y[2]), H, y0, y1);
+  return x0 <= x1 && y0 <= y1;
+}
+
+// Coverage build, pass 1: one wave per face, ALL faces of the mesh.  A face whose texel box is small is rasterised here, the lanes
+// striding over the box; any other is appended to `big` for the tile pass.  The result is a union of bits: order-free.
+__global__ __launch_bounds__(256) void mesh_cover_faces_kernel(const float* __restrict__ uvs, int F, int H, int W, unsigned int* __restrict__ cov,
+                                                               int4* __restrict__ big, MeshState* st) {
+  const int f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (f >= F) return;
+  int X[3], Y[3], x0, x1, y0, y1;
+  if (!face_texels(uvs + (size_t)6 * f, H, W, X, Y, x0, x1, y0, y1)) return;
+  const int bw = x1 - x0 + 1, n = bw * (y1 - y0 + 1);  // (at most 2^30)
+  if (n > SMALL_BOX) {
+    if (lane == 0) {
+      const int at = atomicAdd(&st->n_big, 1);
+      if (at < F) big[at] = make_int4(f, x0 | (x1 << 16), y0 | (y1 << 16), 0);
+    }
+    return;
+  }
+  const size_t wp = (size_t)((W + 31) >> 5);
+  for (int i = lane; i < n; i += 64) {
+    const int col = x0 + i % bw, row = y0 + i / bw;
+    float w[3];
+    if (cover(X, Y, 256 * col + 128, 256 * row + 128, w)) atomicOr(&cov[row * wp + (col >> 5)], 1u << (col & 31));
+  }
+}
+
+// Coverage build, pass 2: one workgroup per 16 x 16 texel tile, one thread per texel; the big faces stream through LDS CHUNK at a time, as
+// in the backprojection.  A wave holds four rows of 16 texels: its ballot gives the 16 bits of each row, which lie in one word.
+__global__ __launch_bounds__(256) void mesh_cover_tiles_kernel(const int4* __restrict__ big, const MeshState* st, int F, const float* __restrict__ uvs,
+                                                               int H, int W, unsigned int* __restrict__ cov) {
+  __shared__ int s_n, s_X[CHUNK][3], s_Y[CHUNK][3];
+  const int n_big = min(st->n_big, F);
+  if (n_big == 0) return;  // (uniform)
+  const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
+  const int col = col0 + (t & 15), row = row0 + (t >> 4);
+  const bool live = col < W && row < H;
+  const int px = 256 * col + 128, py = 256 * row + 128;
+  bool in = false;
+  for (int base = 0; base < n_big; base += CHUNK) {
+    if (t == 0) s_n = 0;
+    __syncthreads();
+    if (base + t < n_big) {
+      const int4 e = big[base + t];
+      if (ranges_meet(e.y, col0, col0 + 15) && ranges_meet(e.z, row0, row0 + 15)) {
+        const int slot = atomicAdd(&s_n, 1);
+        snap_uvs(uvs + (size_t)6 * e.x, H, W, s_X[slot], s_Y[slot]);
+      }
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (live)
+      for (int i = 0; i < n && !in; ++i) {
+        float w[3];
+        in = cover(s_X[i], s_Y[i], px, py, w);
+      }
+    __syncthreads();
+  }
+  const unsigned long long rows = __ballot(in);  // bit l: row (l >> 4) of the wave's four, column l & 15 of the tile
+  if ((t & 63) == 0) {
+    const size_t wp = (size_t)((W + 31) >> 5);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const unsigned int bits = (unsigned int)(rows >> (16 * r)) & 0xffffu;
+      if (bits) atomicOr(&cov[(row + r) * wp + (col0 >> 5)], bits << (col0 & 31));  // (a texel outside the texture has no bit)
+    }
+  }
+}
+
+// the coverage as bytes 0 / 1 (dtp_op_mesh_coverage)
+__global__ __launch_bounds__(256) void mesh_cover_bytes_kernel(const unsigned int* __restrict__ cov, int H, int W, unsigned char* __restrict__ out) {
+  const size_t wp = (size_t)((W + 31) >> 5), n = (size_t)H * W;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const size_t row = i / W;
+    const int col = (int)(i - row * W);
+    out[i] = (unsigned char)((cov[row * wp + (col >> 5)] >> (col & 31)) & 1u);
+  }
+}
+
+// The bleed pass: one workgroup per 16 x 16 texels of the whole texture; a tile that misses the rectangle leaves at once.  The rectangle
+// is `rect` (x0, y0, x1, y1, clipped by the host), or with `st` the texel bounding box of the stamp backprojected last grown by k and
+// clipped here (no valid face: no pass).  The coverage flags of the tile and a k-texel halo are staged in LDS (0 outside the texture:
+// no wrap-around), with the first n_off offsets of the table; an uncovered texel takes the four bytes of the first covered candidate.
+// Only covered texels are read and only uncovered ones written, so the launch needs no second buffer and no order.
+__global__ __launch_bounds__(256) void mesh_bleed_kernel(const unsigned int* __restrict__ cov, const signed char* __restrict__ table, int n_off, int k,
+                                                         const MeshState* st, int F, int4 rect, unsigned int* tex, int H, int W) {
+  __shared__ unsigned char s_cov[(16 + 2 * MESH_MAX_BLEED) * (16 + 2 * MESH_MAX_BLEED)];
+  __shared__ signed char s_off[2 * MESH_MAX_OFF];
+  const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
+  int x0 = rect.x, y0 = rect.y, x1 = rect.z, y1 = rect.w;
+  if (st) {
+    if (min(st->n_val, F) == 0) return;
+    x0 = max(st->bb[0] - k, 0); y0 = max(st->bb[1] - k, 0); x1 = min(st->bb[2] + k, W - 1); y1 = min(st->bb[3] + k, H - 1);
+  }
+  if (col0 > x1 || col0 + 15 < x0 || row0 > y1 || row0 + 15 < y0) return;  // (uniform)
+  const int n = 16 + 2 * k;
+  const size_t wp = (size_t)((W + 31) >> 5);
+  for (int i = t; i < n * n; i += 256) {
+    const int r = row0 - k + i / n, c = col0 - k + i % n;
+    s_cov[i] = (r >= 0 && r < H && c >= 0 && c < W) ? (unsigned char)((cov[r * wp + (c >> 5)] >> (c & 31)) & 1u) : (unsigned char)0;
+  }
+  for (int i = t; i < 2 * n_off; i += 256) s_off[i] = table[i];
+  __syncthreads();
+  const int col = col0 + (t & 15), row = row0 + (t >> 4);
+  if (col < x0 || col > x1 || row < y0 || row > y1) return;  // (x1 < W, y1 < H)
+  const int ly = (t >> 4) + k, lx = (t & 15) + k;
+  if (s_cov[ly * n + lx]) return;
+  for (int o = 0; o < n_off; ++o) {
+    const int di = s_off[2 * o], dj = s_off[2 * o + 1];  // |di|, |dj| <= k: inside the staged square
+    if (s_cov[(ly + di) * n + (lx + dj)]) {
+      tex[(size_t)row * W + col] = tex[(size_t)(row + di) * W + (col + dj)];
+      return;
+    }
+  }
+}
+
 // ---------------------------------------------------------------- host
 inline int launch_ok() { return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP; }
 bool known_mode(int m) { return m == DTP_STROKE_INPAINT || m == DTP_STROKE_ERASE || m == DTP_STROKE_OVERPAINT; }
@@ -395,7 +526,7 @@ bool mesh_alive(const Mesh* m) {
 
 void mesh_free(Mesh* m) {
   (void)hipFree(m->verts); (void)hipFree(m->faces); (void)hipFree(m->uvs); (void)hipFree(m->rec); (void)hipFree(m->owned);
-  (void)hipFree(m->win); (void)hipFree(m->val); (void)hipFree(m->state);
+  (void)hipFree(m->win); (void)hipFree(m->val); (void)hipFree(m->state); (void)hipFree(m->cov);
   delete m;
 }
 
@@ -437,6 +568,47 @@ int enqueue_backproject(Mesh* m, const float* dec, int finished, const unsigned 
   return launch_ok();
 }
 
+int check_bleed(const char* who, int bleed) {
+  if (bleed < 0 || bleed > MESH_MAX_BLEED) { dtp_set_error("%s: bleed=%d outside 0..%d", who, bleed, MESH_MAX_BLEED); return DTP_ERR_ARG; }
+  return DTP_OK;
+}
+
+// The coverage of an H x W texture by all faces of the mesh, built at the first use of the size: one allocation (the bits and the offset
+// table behind them) and its kernels; the call waits for them once, so that every later use, on any stream, only reads.  Another size
+// frees the mask and builds it again.  `val` holds the big faces meanwhile: the next backprojection rewrites it before it reads it.
+int ensure_coverage(Mesh* m, int H, int W, hipStream_t s) {
+  if (m->cov && m->cov_H == H && m->cov_W == W) return DTP_OK;
+  if (m->cov) { (void)hipFree(m->cov); m->cov = nullptr; }  // (waits for the work that still reads it)
+  const size_t bits = (size_t)((W + 31) >> 5) * H * 4;
+  unsigned int* cov = nullptr;
+  hipError_t e = hipMalloc((void**)&cov, bits + 2 * MESH_MAX_OFF);
+  if (e == hipSuccess) e = hipMemsetAsync(cov, 0, bits, s);
+  if (e == hipSuccess) e = hipMemsetAsync(&m->state->n_big, 0, sizeof(int), s);
+  if (e == hipSuccess) e = hipMemcpyAsync((char*)cov + bits, mesh_bleed_table().d, 2 * MESH_MAX_OFF, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mesh_cover_faces_kernel, dim3((m->F + 3) / 4), dim3(256), 0, s, m->uvs, m->F, H, W, cov, m->val, m->state);
+    hipLaunchKernelGGL(mesh_cover_tiles_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->val, m->state, m->F, m->uvs, H, W, cov);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    dtp_set_error("mesh coverage of a %d x %d texture: %s", H, W, hipGetErrorString(e));
+    (void)hipFree(cov);
+    return DTP_ERR_HIP;
+  }
+  m->cov = cov; m->cov_H = H; m->cov_W = W;
+  return DTP_OK;
+}
+
+// the bleed pass at radius k over `rect` (clipped, not empty), or with rect null over the box of the stamp backprojected last on this mesh
+int enqueue_bleed(Mesh* m, unsigned char* texture, int H, int W, int k, const int* rect, hipStream_t s) {
+  const signed char* table = (const signed char*)m->cov + (size_t)((W + 31) >> 5) * H * 4;
+  const int4 r = rect ? make_int4(rect[0], rect[1], rect[2], rect[3]) : make_int4(0, 0, -1, -1);
+  hipLaunchKernelGGL(mesh_bleed_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->cov, table, mesh_bleed_table().count[k], k,
+                     rect ? (const MeshState*)nullptr : m->state, m->F, r, (unsigned int*)texture, H, W);
+  return launch_ok();
+}
+
 int disc_mask(Ctx* c, hipStream_t s, const unsigned char** out) {
   if (!c->mesh_disc) {
     void* p;
@@ -458,6 +630,87 @@ struct MeshStep {
   int slot = 0;
   StampPlan plan;
 };
+
+// dtp_mesh_stroke (bleed 0) and dtp_mesh_stroke_bleed: `who` names the entry point in a refusal
+int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
+                const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s_) {
+  Ctx* c = (Ctx*)ctx;
+  Mesh* m = (Mesh*)mesh;
+  hipStream_t s = (hipStream_t)s_;
+  // ---- every check, before anything is enqueued
+  RC(check_bleed(who, bleed));
+  if (!c || !m || !texture || !stamps || !st || !o) {
+    dtp_set_error("%s: NULL argument (ctx, mesh, texture, stamps, st and o are required)", who);
+    return DTP_ERR_ARG;
+  }
+  if (!c->finalized) { dtp_set_error("%s: weights not finalized", who); return DTP_ERR_STATE; }
+  if (!mesh_alive(m)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
+  if (m->ctx != c) { dtp_set_error("%s: the mesh belongs to another handle", who); return DTP_ERR_ARG; }
+  const int R = c->R;
+  RC(check_texture(who, texture, H, W));
+  if (n < 1) { dtp_set_error("%s: n=%d stamps (at least 1)", who, n); return DTP_ERR_ARG; }
+  if (R > MAX_WIN) { dtp_set_error("%s: resolution %d above %d", who, R, MAX_WIN); return DTP_ERR_ARG; }
+  if (o->margin < 0 || o->margin >= R / 2) { dtp_set_error("%s: margin=%d outside [0, %d)", who, o->margin, R / 2); return DTP_ERR_ARG; }
+  std::vector<MeshStep> steps(n);
+  int evals = 0;
+  bool any_erase = false, any_stamp = false;
+  for (int i = 0; i < n; ++i) {
+    const dtp_mesh_stamp& t = stamps[i];
+    MeshStep& q = steps[i];
+    if (!known_mode(t.mode)) {
+      dtp_set_error("%s: stamp %d has unknown mode %d (INPAINT = 0, ERASE = 1, OVERPAINT = 2)", who, i, t.mode);
+      return DTP_ERR_ARG;
+    }
+    RC(check_over(who, i, t.mode, o->over_y, o->over_x, R));
+    RC(make_camera(who, i, t.pos, t.normal, t.prev, t.fov, q.cam));
+    q.skip = !box_meets_window(m, q.cam, t.fov, R);
+    if (t.mode == DTP_STROKE_ERASE) { any_erase = any_erase || !q.skip; continue; }  // (runs no stamp: its slot and seed are unused)
+    if (t.slot < 0 || t.slot >= DTP_MAX_SLOTS) { dtp_set_error("%s: slot %d of stamp %d outside 0..%d", who, t.slot, i, DTP_MAX_SLOTS - 1); return DTP_ERR_ARG; }
+    if (!c->slot_set[t.slot]) {
+      dtp_set_error("%s: stamp %d: no brush set in slot %d (call dtp_set_brush / dtp_set_conditioning)", who, i, t.slot);
+      return DTP_ERR_STATE;
+    }
+    // the stamp, as dtp_stamp_seeded would stage it, with the two hooks
+    q.st = *st; q.seed = t.seed; q.slot = t.slot;
+    StampPlan& p = q.plan;
+    p.st = &q.st; p.B = 1; p.slot_ids = &q.slot; p.strength = o->strength;
+    p.seeded = true; p.seeds = &q.seed; p.sample_vae = o->sample_vae != 0;
+    p.canvas_staged = true;
+    p.paste = [](const float*, int, int, hipStream_t) { return DTP_OK; };  // (set for the checks; the launcher proper follows below)
+    const int rc = stamp_plan(c, p);
+    if (rc) {  // dtp_stamp_seeded's refusal and code, with the stamp it is about
+      const std::string why = dtp_last_error();
+      dtp_set_error("%s: stamp %d: %s", who, i, why.c_str());
+      return rc;
+    }
+    if (!q.skip) { evals += p.E; any_stamp = true; }
+  }
+  // ---- enqueue: per stamp reset -> project -> render -> stamp -> valid -> backproject (-> bleed); the stream orders the stamps
+  HIP_CHECK(hipSetDevice(c->device));
+  if (bleed && (any_stamp || any_erase)) RC(ensure_coverage(m, H, W, s));
+  const unsigned char *square = paste_mask, *disc = paste_mask;
+  if (!paste_mask && any_stamp) RC(stroke_default_mask(c, o->margin, s, &square));
+  if (!paste_mask && any_erase) RC(disc_mask(c, s, &disc));
+  int* face_idx = c->mesh_face_idx;
+  for (int i = 0; i < n; ++i) {
+    const dtp_mesh_stamp& t = stamps[i];
+    MeshStep& q = steps[i];
+    if (q.skip) continue;
+    RC(enqueue_render(m, q.cam, t.fov, o->flip_normals != 0, texture, H, W, R, t.mode, o->over_y, o->over_x, c->canvas32, face_idx, s));
+    if (t.mode == DTP_STROKE_ERASE) {
+      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s));
+      if (bleed) RC(enqueue_bleed(m, texture, H, W, bleed, nullptr, s));
+      continue;
+    }
+    q.plan.paste = [=](const float* dec, int, int, hipStream_t q_s) {
+      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s));
+      return bleed ? enqueue_bleed(m, texture, H, W, bleed, nullptr, q_s) : DTP_OK;
+    };
+    RC(stamp_enqueue(c, q.plan, s));
+  }
+  c->last_stroke_stamps = n; c->last_stroke_groups = n; c->last_stroke_evals = evals;
+  return DTP_OK;
+}
 
 }  // namespace
 
@@ -548,74 +801,49 @@ int dtp_mesh_destroy(dtp_mesh* mesh) {
 }
 
 int dtp_mesh_stroke(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
-                    const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, dtp_stream s_) {
-  Ctx* c = (Ctx*)ctx;
-  Mesh* m = (Mesh*)mesh;
-  hipStream_t s = (hipStream_t)s_;
-  // ---- every check, before anything is enqueued
-  if (!c || !m || !texture || !stamps || !st || !o) {
-    dtp_set_error("dtp_mesh_stroke: NULL argument (ctx, mesh, texture, stamps, st and o are required)");
-    return DTP_ERR_ARG;
-  }
-  if (!c->finalized) { dtp_set_error("dtp_mesh_stroke: weights not finalized"); return DTP_ERR_STATE; }
-  if (!mesh_alive(m)) { dtp_set_error("dtp_mesh_stroke: the mesh is not a live mesh (destroyed?)"); return DTP_ERR_ARG; }
-  if (m->ctx != c) { dtp_set_error("dtp_mesh_stroke: the mesh belongs to another handle"); return DTP_ERR_ARG; }
-  const int R = c->R;
-  RC(check_texture("dtp_mesh_stroke", texture, H, W));
-  if (n < 1) { dtp_set_error("dtp_mesh_stroke: n=%d stamps (at least 1)", n); return DTP_ERR_ARG; }
-  if (R > MAX_WIN) { dtp_set_error("dtp_mesh_stroke: resolution %d above %d", R, MAX_WIN); return DTP_ERR_ARG; }
-  if (o->margin < 0 || o->margin >= R / 2) { dtp_set_error("dtp_mesh_stroke: margin=%d outside [0, %d)", o->margin, R / 2); return DTP_ERR_ARG; }
-  std::vector<MeshStep> steps(n);
-  int evals = 0;
-  bool any_erase = false, any_stamp = false;
-  for (int i = 0; i < n; ++i) {
-    const dtp_mesh_stamp& t = stamps[i];
-    MeshStep& q = steps[i];
-    if (!known_mode(t.mode)) {
-      dtp_set_error("dtp_mesh_stroke: stamp %d has unknown mode %d (INPAINT = 0, ERASE = 1, OVERPAINT = 2)", i, t.mode);
-      return DTP_ERR_ARG;
-    }
-    RC(check_over("dtp_mesh_stroke", i, t.mode, o->over_y, o->over_x, R));
-    RC(make_camera("dtp_mesh_stroke", i, t.pos, t.normal, t.prev, t.fov, q.cam));
-    q.skip = !box_meets_window(m, q.cam, t.fov, R);
-    if (t.mode == DTP_STROKE_ERASE) { any_erase = any_erase || !q.skip; continue; }  // (runs no stamp: its slot and seed are unused)
-    if (t.slot < 0 || t.slot >= DTP_MAX_SLOTS) { dtp_set_error("dtp_mesh_stroke: slot %d of stamp %d outside 0..%d", t.slot, i, DTP_MAX_SLOTS - 1); return DTP_ERR_ARG; }
-    if (!c->slot_set[t.slot]) {
-      dtp_set_error("dtp_mesh_stroke: stamp %d: no brush set in slot %d (call dtp_set_brush / dtp_set_conditioning)", i, t.slot);
-      return DTP_ERR_STATE;
-    }
-    // the stamp, as dtp_stamp_seeded would stage it, with the two hooks
-    q.st = *st; q.seed = t.seed; q.slot = t.slot;
-    StampPlan& p = q.plan;
-    p.st = &q.st; p.B = 1; p.slot_ids = &q.slot; p.strength = o->strength;
-    p.seeded = true; p.seeds = &q.seed; p.sample_vae = o->sample_vae != 0;
-    p.canvas_staged = true;
-    p.paste = [](const float*, int, int, hipStream_t) { return DTP_OK; };  // (set for the checks; the launcher proper follows below)
-    const int rc = stamp_plan(c, p);
-    if (rc) {  // dtp_stamp_seeded's refusal and code, with the stamp it is about
-      const std::string why = dtp_last_error();
-      dtp_set_error("dtp_mesh_stroke: stamp %d: %s", i, why.c_str());
-      return rc;
-    }
-    if (!q.skip) { evals += p.E; any_stamp = true; }
-  }
-  // ---- enqueue: per stamp reset -> project -> render -> stamp -> valid -> backproject; the stream orders the stamps
-  HIP_CHECK(hipSetDevice(c->device));
-  const unsigned char *square = paste_mask, *disc = paste_mask;
-  if (!paste_mask && any_stamp) RC(stroke_default_mask(c, o->margin, s, &square));
-  if (!paste_mask && any_erase) RC(disc_mask(c, s, &disc));
-  int* face_idx = c->mesh_face_idx;
-  for (int i = 0; i < n; ++i) {
-    const dtp_mesh_stamp& t = stamps[i];
-    MeshStep& q = steps[i];
-    if (q.skip) continue;
-    RC(enqueue_render(m, q.cam, t.fov, o->flip_normals != 0, texture, H, W, R, t.mode, o->over_y, o->over_x, c->canvas32, face_idx, s));
-    if (t.mode == DTP_STROKE_ERASE) { RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s)); continue; }
-    q.plan.paste = [=](const float* dec, int, int, hipStream_t q_s) { return enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s); };
-    RC(stamp_enqueue(c, q.plan, s));
-  }
-  c->last_stroke_stamps = n; c->last_stroke_groups = n; c->last_stroke_evals = evals;
+                    const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, dtp_stream s) {
+  return mesh_stroke("dtp_mesh_stroke", ctx, mesh, texture, H, W, stamps, n, st, o, paste_mask, 0, s);
+}
+
+int dtp_mesh_stroke_bleed(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
+                          const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s) {
+  return mesh_stroke("dtp_mesh_stroke_bleed", ctx, mesh, texture, H, W, stamps, n, st, o, paste_mask, bleed, s);
+}
+
+int dtp_mesh_bleed_offsets(int radius, int* count, signed char* di_dj) {
+  if (!count) { dtp_set_error("dtp_mesh_bleed_offsets: count is NULL"); return DTP_ERR_ARG; }
+  if (radius < 1 || radius > MESH_MAX_BLEED) { dtp_set_error("dtp_mesh_bleed_offsets: radius=%d outside 1..%d", radius, MESH_MAX_BLEED); return DTP_ERR_ARG; }
+  const MeshBleedTable& t = mesh_bleed_table();
+  *count = t.count[radius];
+  if (di_dj) memcpy(di_dj, t.d, (size_t)2 * t.count[radius]);
   return DTP_OK;
+}
+
+int dtp_mesh_bleed(dtp_mesh* mesh, uint8_t* texture, int H, int W, int bleed, const int* rect, dtp_stream s) {
+  Mesh* m = (Mesh*)mesh;
+  if (!m || !texture) { dtp_set_error("dtp_mesh_bleed: NULL argument (mesh and texture are required)"); return DTP_ERR_ARG; }
+  RC(check_bleed("dtp_mesh_bleed", bleed));
+  RC(check_texture("dtp_mesh_bleed", texture, H, W));
+  int r[4];
+  const int clipped = mesh_clip_rect(rect, H, W, r);
+  if (clipped < 0) { dtp_set_error("dtp_mesh_bleed: rect (%d, %d, %d, %d) has x0 > x1 or y0 > y1", rect[0], rect[1], rect[2], rect[3]); return DTP_ERR_ARG; }
+  if (!mesh_alive(m)) { dtp_set_error("dtp_mesh_bleed: the mesh is not a live mesh (destroyed?)"); return DTP_ERR_ARG; }
+  if (bleed == 0 || clipped > 0) return DTP_OK;  // nothing to do
+  HIP_CHECK(hipSetDevice(m->ctx->device));
+  RC(ensure_coverage(m, H, W, (hipStream_t)s));
+  return enqueue_bleed(m, texture, H, W, bleed, r, (hipStream_t)s);
+}
+
+int dtp_op_mesh_coverage(dtp_mesh* mesh, int H, int W, uint8_t* out, dtp_stream s) {
+  Mesh* m = (Mesh*)mesh;
+  if (!m || !out) { dtp_set_error("dtp_op_mesh_coverage: NULL argument"); return DTP_ERR_ARG; }
+  if (H < 1 || W < 1 || H > MAX_TEX || W > MAX_TEX) { dtp_set_error("dtp_op_mesh_coverage: a %d x %d texture (each side 1..%d)", H, W, MAX_TEX); return DTP_ERR_ARG; }
+  if (!mesh_alive(m)) { dtp_set_error("dtp_op_mesh_coverage: the mesh is not a live mesh (destroyed?)"); return DTP_ERR_ARG; }
+  HIP_CHECK(hipSetDevice(m->ctx->device));
+  RC(ensure_coverage(m, H, W, (hipStream_t)s));
+  const size_t n = (size_t)H * W;
+  hipLaunchKernelGGL(mesh_cover_bytes_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)s, m->cov, H, W, out);
+  return launch_ok();
 }
 
 int dtp_op_mesh_render(dtp_mesh* mesh, const float cam[12], float fov, int flip_normals, const uint8_t* texture, int H, int W, int R, int mode,

@@ -431,7 +431,8 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         return _mesh.Mesh(self._h, vertices, faces, face_uvs, keep=self)
 
     def paint_mesh_stroke(self, mesh, texture, positions, normals, prev_positions, fov, seeds=None, modes=None, slots=None,
-                          flip_normals=False, margin=1, overpaint_margins=(10, 25), mask=None, sample_vae=True, strength=1.0, **settings):
+                          flip_normals=False, margin=1, overpaint_margins=(10, 25), mask=None, sample_vae=True, strength=1.0, bleed=0,
+                          **settings):
         """Paint a stroke on a textured mesh without a host round trip per stamp: TexturePainterManager.stamp (manager.py:199-271) as one
         dtp_mesh_stroke call.  Per stamp, in order: an orthographic look-at camera from positions[i] + normals[i] at positions[i] with
         up = prev_positions[i] - positions[i] (mesh_camera), the render of `mesh` with `texture` (uint8 [H,W,4] on the model's device,
@@ -439,7 +440,11 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         texture through the faces the window shows.  fov: half the window's width in world units, one float or one per stamp (the Kit
         app's fov_distance * fov_scale).  seeds, modes, slots, mask, overpaint_margins, sample_vae, strength, settings: as paint_stroke;
         margin=1 is the Kit app's stamp mask; an "erase" stamp without `mask` uses the analytic disc.  flip_normals: a left-handed mesh.
-        Strictly serial: stamp i + 1 renders what stamp i painted.  The call only enqueues."""
+        Strictly serial: stamp i + 1 renders what stamp i painted.  The call only enqueues.  bleed: a radius 1..16 in texels; after
+        every stamp the texels no face of the mesh covers (the gutter between UV charts) take the nearest covered texel within that
+        radius, inside the stamp's texel bounding box grown by the radius, so that the next stamp's render and any filtered view of the
+        texture see no unpainted line along the seams (dtp_mesh_stroke_bleed; the first use with a texture size builds the mesh's
+        coverage mask and waits for it once).  0: no pass, dtp_mesh_stroke exactly."""
         if not self._slots:
             raise _lib.DtpError("no brush set: call set_brush() first")
         R = self._resolution
@@ -464,14 +469,41 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
                 raise ValueError(f"mask must be {R} x {R}, got {tuple(mask.shape)}")
             mask = (mask.detach().to(self._device) > 0).to(torch.uint8).contiguous()
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
-        check(self._lib.dtp_mesh_stroke(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n, C.byref(st),
-                                        C.byref(opts), ptr(mask), self._s()), "dtp_mesh_stroke")
+        if int(bleed) == 0:
+            check(self._lib.dtp_mesh_stroke(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n, C.byref(st),
+                                            C.byref(opts), ptr(mask), self._s()), "dtp_mesh_stroke")
+        else:
+            check(self._lib.dtp_mesh_stroke_bleed(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n,
+                                                  C.byref(st), C.byref(opts), ptr(mask), int(bleed), self._s()), "dtp_mesh_stroke_bleed")
         torch.cuda.current_stream(self._device).wait_stream(self.stream)
         for t in (texture, mask):  # keep them alive until the stream has consumed them
             if t is not None:
                 t.record_stream(self.stream)
         if self._check_finite and not self.last_stamp_finite():
             raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
+        return texture
+
+    def bleed_texture(self, mesh, texture, bleed, rect=None):
+        """The bleed pass of paint_mesh_stroke on its own (dtp_mesh_bleed), for a texture that was loaded from a file or painted without
+        it, or before an export: every texel of `texture` (uint8 [H,W,4] on the model's device, contiguous; changed in place and
+        returned) that no face of `mesh` covers takes the four bytes of the nearest covered texel within `bleed` texels (1..16; ties go
+        to the smaller row offset, then the smaller column offset; no wrap-around).  rect: (x0, y0, x1, y1) inclusive texel bounds of
+        the pass, clipped to the texture; None = the whole texture.  Covered texels are only read.  The call only enqueues."""
+        if not isinstance(mesh, _mesh.Mesh):
+            raise ValueError("mesh must come from load_mesh()")
+        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
+                and texture.device == self._device and texture.is_contiguous()):
+            raise ValueError(f"texture must be a contiguous uint8 [H, W, 4] tensor on {self._device} (it is changed in place)")
+        r = None
+        if rect is not None:
+            if len(rect) != 4:
+                raise ValueError(f"rect must be (x0, y0, x1, y1), got {rect!r}")
+            r = C.byref((C.c_int * 4)(*[int(v) for v in rect]))
+        self.stream.wait_stream(torch.cuda.current_stream(self._device))
+        check(self._lib.dtp_mesh_bleed(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], int(bleed), r, self._s()),
+              "dtp_mesh_bleed")
+        torch.cuda.current_stream(self._device).wait_stream(self.stream)
+        texture.record_stream(self.stream)
         return texture
 
     def stroke_info(self):

@@ -1,6 +1,7 @@
 """The Python side of the mesh strokes (include/dtp.h: dtp_mesh_*): the device-resident mesh, the host-only camera and
 the stamp array of a stroke.  The stroke itself is MI355ConditionalInpainter.paint_mesh_stroke; the two kernels' op-level entry points
-are ops.mesh_render / ops.mesh_backproject."""
+are ops.mesh_render / ops.mesh_backproject.  The bleed pass that pads the UV charts is paint_mesh_stroke(bleed=k) and
+MI355ConditionalInpainter.bleed_texture; ops.mesh_coverage / ops.mesh_bleed_offsets show what it works from."""
 import ctypes as C
 
 import torch

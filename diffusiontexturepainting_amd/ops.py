@@ -596,3 +596,24 @@ def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None):
     check(lib.dtp_op_mesh_backproject(mesh.handle, ptr(dec), int(finished), ptr(mask), ptr(face_idx), face_idx.shape[0], ptr(texture),
                                       texture.shape[0], texture.shape[1], _stream()), "mesh_backproject")
     return texture
+
+
+def mesh_coverage(mesh, H, W):
+    """dtp_op_mesh_coverage: the texels of an H x W texture whose centre at least one of all faces of `mesh` (a mesh.Mesh) covers in
+    texture space, by the backprojection's integer rule -> bool [H, W] on the mesh's device.  The first call for a size builds the mask the
+    bleed pass uses."""
+    lib = _lib.load()
+    out = torch.empty(int(H), int(W), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    check(lib.dtp_op_mesh_coverage(mesh.handle, int(H), int(W), ptr(out), _stream()), "mesh_coverage")
+    return out.bool()
+
+
+def mesh_bleed_offsets(k):
+    """dtp_mesh_bleed_offsets (host only, needs no GPU): the candidate offsets (di, dj) of a gutter texel's source at radius k in 1..16,
+    sorted by (di^2 + dj^2, di, dj) -> int8 [n, 2].  The table of a smaller radius is a prefix of it."""
+    lib = _lib.load()
+    n = C.c_int(0)
+    check(lib.dtp_mesh_bleed_offsets(int(k), C.byref(n), None), "mesh_bleed_offsets")
+    buf = (C.c_byte * (2 * n.value))()
+    check(lib.dtp_mesh_bleed_offsets(int(k), C.byref(n), buf), "mesh_bleed_offsets")
+    return torch.tensor(list(buf), dtype=torch.int8).reshape(n.value, 2)

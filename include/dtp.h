@@ -23,7 +23,8 @@ extern "C" {
 /* Stays 3: the seeded entry points below (dtp_stamp_seeded, dtp_op_stamp_noise, dtp_philox4x32), the LoRA refit (dtp_refit_stage,
  * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) and the strokes (dtp_stroke, dtp_stroke_plan, dtp_last_stroke_info,
  * dtp_op_stroke_gather, dtp_op_stroke_paste) and the mesh strokes (dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_camera, dtp_mesh_stroke,
- * dtp_op_mesh_render, dtp_op_mesh_backproject) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
+ * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
+ * dtp_op_mesh_coverage) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
  * caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -310,6 +311,44 @@ int dtp_mesh_destroy(dtp_mesh* mesh);
 int dtp_mesh_camera(const float pos[3], const float normal[3], const float prev[3], float fov, float out[12]);
 int dtp_mesh_stroke(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
                     const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, dtp_stream s);
+
+/* ---------------------------------------------------------------- bleeding painted texels across UV chart borders
+ * The backprojection writes a texel only when its centre lies inside the UV triangle of a valid face, so the texels between the charts
+ * of an atlas (the gutter) keep what they had, and every bilinear tap that straddles a chart border mixes a painted texel with an
+ * unpainted one: the next stamp's render sees a line of partly unknown pixels along every seam, and so does any renderer that filters
+ * the texture.  The bleed pass pads the charts (Blender's texture paint: "Bleed").  Everything below is exact integer arithmetic.
+ *
+ * Coverage of (mesh, H, W): texel (row i, column j) is covered when its centre (256 j + 128, 256 i + 128) is covered by at least one of
+ * ALL F faces of the mesh in texture space, by the backprojection's rule: X = rint((u W) 256), Y = rint(((1 - v) H) 256), the +-2^26
+ * clamp, int64 edge functions, both windings, the top-left fill rule (a centre on an edge two faces share belongs to one of them: no
+ * hole), a face of zero area excluded.  It depends on no camera.
+ * Source of a gutter texel at radius k, 1 <= k <= 16: for an uncovered texel g = (i, j), s(g) is the covered texel (i + di, j + dj) INSIDE
+ * the texture (no wrap-around) with 0 < di^2 + dj^2 <= k^2 that minimises (di^2 + dj^2, di, dj) lexicographically; no candidate: no
+ * source.
+ * The pass over a texel rectangle: every uncovered texel of the rectangle that has a source receives all four bytes of texture[s(g)].
+ * It reads only covered texels and writes only uncovered ones, so one launch needs no second buffer, its result does not depend on
+ * scheduling, and applying it twice is applying it once.
+ *
+ * dtp_mesh_stroke_bleed is dtp_mesh_stroke with `bleed` = the radius: after the backprojection of every stamp that ran (INPAINT, OVERPAINT
+ * and ERASE alike, which bleeds its zeros) the pass runs over that stamp's texel bounding box -- the union of the texel ranges of its
+ * valid faces, kept on the device -- grown by `bleed` and clipped to the texture; no valid face, no pass; no host read.  Stamp i + 1
+ * renders what stamp i bled.  Gutter texels outside those rectangles are NOT touched: a texture that was painted before, or loaded from
+ * a file, is padded as a whole with dtp_mesh_bleed.  bleed == 0 is dtp_mesh_stroke exactly, the same launches and the same bytes; bleed
+ * outside 0..16 is DTP_ERR_ARG naming "bleed", checked with everything else before anything is enqueued.  The first use of an (H, W)
+ * with a mesh builds its coverage: one allocation (1 bit per texel) and its kernels, and the call waits for them once; later strokes
+ * allocate nothing and never wait.  A mesh keeps ONE coverage mask: another size frees it and builds it again; it is freed with the mesh.
+ * dtp_mesh_bleed: the pass on its own over rect = {x0, y0, x1, y1}, inclusive, clipped to the texture (NULL = the whole texture; nothing
+ * of it inside the texture, or bleed == 0: nothing is done).  DTP_ERR_ARG for a NULL mesh or texture, bleed outside 0..16, H or W outside
+ * 1..32768, x0 > x1 or y0 > y1, a mesh that is not alive.
+ * dtp_op_mesh_coverage: the coverage as bytes 0 / 1, out u8 [H][W] on the device.
+ * dtp_mesh_bleed_offsets (host only): *count = the number of candidates of `radius` (1..16) and, unless di_dj is NULL, di_dj[2 o],
+ * di_dj[2 o + 1] = (di, dj) of candidate o in the order above (796 pairs at radius 16).  The table of radius k is the prefix with
+ * di^2 + dj^2 <= k^2 of the table of radius 16.  DTP_ERR_ARG for a radius outside 1..16 or count NULL. */
+int dtp_mesh_stroke_bleed(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
+                          const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s);
+int dtp_mesh_bleed(dtp_mesh* mesh, uint8_t* texture, int H, int W, int bleed, const int* rect, dtp_stream s);
+int dtp_op_mesh_coverage(dtp_mesh* mesh, int H, int W, uint8_t* out, dtp_stream s);
+int dtp_mesh_bleed_offsets(int radius, int* count, signed char* di_dj);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod

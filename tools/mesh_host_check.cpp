@@ -1,6 +1,7 @@
-// Stand-alone host check of csrc/mesh.hip for a sanitizer build: the part of it that needs no device -- dtp_mesh_camera and the argument
-// checks of dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_stroke and the two ops, all of which return before their first HIP call --
-// driven from its own main().  The rest of the library is replaced by the stubs below; none of them may be reached.  Build and run:
+// Stand-alone host check of csrc/mesh.hip for a sanitizer build: the part of it that needs no device -- dtp_mesh_camera, the argument
+// checks of dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_stroke and the two ops, all of which return before their first HIP call, and
+// the host side of the bleed pass (the offset table, the rectangle clipping of csrc/mesh_host.h, the argument checks) -- driven from its
+// own main().  The rest of the library is replaced by the stubs below; none of them may be reached.  Build and run:
 //   hipcc --offload-arch=gfx950 -std=c++17 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -I include -I diffusiontexturepainting_amd/csrc diffusiontexturepainting_amd/csrc/mesh.hip tools/mesh_host_check.cpp -o mesh_host_check
 //   ./mesh_host_check
@@ -11,6 +12,7 @@
 #include <string.h>
 #include <vector>
 
+#include "mesh_host.h"
 #include "stamp.h"
 
 static char g_err[1024];
@@ -89,6 +91,67 @@ int main() {
   dtp_mesh_stroke_opts o = {};
   dtp_mesh_stamp stamp = {};
   EXPECT(dtp_mesh_stroke(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, nullptr) == DTP_ERR_ARG);
+
+  // ---- the bleed pass: the offset table at every radius into a buffer of exactly its size, against the definition
+  std::vector<signed char> last;
+  for (int k = 1; k <= 16; ++k) {
+    int want = 0;
+    for (int di = -k; di <= k; ++di)
+      for (int dj = -k; dj <= k; ++dj) want += (di * di + dj * dj > 0 && di * di + dj * dj <= k * k);
+    int count = -1;
+    EXPECT(dtp_mesh_bleed_offsets(k, &count, nullptr) == DTP_OK && count == want);
+    std::vector<signed char> d(2 * (size_t)count);
+    EXPECT(dtp_mesh_bleed_offsets(k, &count, d.data()) == DTP_OK && count == want);
+    for (int o = 0; o < count; ++o) {
+      const int di = d[2 * o], dj = d[2 * o + 1], d2 = di * di + dj * dj;
+      EXPECT(d2 > 0 && d2 <= k * k);
+      if (o > 0) {  // the key (d2, di, dj) rises strictly
+        const int pi = d[2 * o - 2], pj = d[2 * o - 1], p2 = pi * pi + pj * pj;
+        EXPECT(p2 < d2 || (p2 == d2 && (pi < di || (pi == di && pj < dj))));
+      }
+    }
+    EXPECT(last.size() <= d.size() && (last.empty() || memcmp(last.data(), d.data(), last.size()) == 0));  // a prefix of the next
+    last = d;
+  }
+  EXPECT(last.size() == 2 * (size_t)MESH_MAX_OFF);
+  EXPECT(last[0] == -1 && last[1] == 0 && last[2] == 0 && last[3] == -1 && last[4] == 0 && last[5] == 1 && last[6] == 1 && last[7] == 0);
+  int count = -5;
+  signed char one[2] = {9, 9};
+  EXPECT(dtp_mesh_bleed_offsets(0, &count, one) == DTP_ERR_ARG && dtp_mesh_bleed_offsets(17, &count, one) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_bleed_offsets(-3, &count, one) == DTP_ERR_ARG && dtp_mesh_bleed_offsets(4, nullptr, one) == DTP_ERR_ARG);
+  EXPECT(count == -5 && one[0] == 9 && one[1] == 9);
+
+  // the rectangle of dtp_mesh_bleed
+  int r[4];
+  EXPECT(mesh_clip_rect(nullptr, 96, 160, r) == 0 && r[0] == 0 && r[1] == 0 && r[2] == 159 && r[3] == 95);
+  const int inside[4] = {70, 30, 90, 47}, over[4] = {-7, -3, 11, 200}, right[4] = {160, 0, 300, 10}, above[4] = {0, -9, 10, -1};
+  const int inverted_x[4] = {5, 0, 4, 9}, inverted_y[4] = {0, 9, 9, 8}, texel[4] = {159, 95, 159, 95};
+  const int far[4] = {-2147483647 - 1, -2147483647 - 1, 2147483647, 2147483647};
+  EXPECT(mesh_clip_rect(inside, 96, 160, r) == 0 && r[0] == 70 && r[1] == 30 && r[2] == 90 && r[3] == 47);
+  EXPECT(mesh_clip_rect(over, 96, 160, r) == 0 && r[0] == 0 && r[1] == 0 && r[2] == 11 && r[3] == 95);
+  EXPECT(mesh_clip_rect(right, 96, 160, r) == 1 && mesh_clip_rect(above, 96, 160, r) == 1);
+  EXPECT(mesh_clip_rect(inverted_x, 96, 160, r) == -1 && mesh_clip_rect(inverted_y, 96, 160, r) == -1);
+  EXPECT(mesh_clip_rect(texel, 96, 160, r) == 0 && r[0] == 159 && r[1] == 95 && r[2] == 159 && r[3] == 95);
+  EXPECT(mesh_clip_rect(far, 1, 1, r) == 0 && r[0] == 0 && r[1] == 0 && r[2] == 0 && r[3] == 0);
+
+  // the entry points: every refusal comes before the mesh is followed or a device is touched
+  EXPECT(dtp_mesh_bleed(nullptr, tex, 1, 1, 1, nullptr, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, nullptr, 1, 1, 1, nullptr, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, tex, 1, 1, 17, nullptr, nullptr) == DTP_ERR_ARG && strstr(g_err, "bleed=17"));
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, tex, 1, 1, -1, nullptr, nullptr) == DTP_ERR_ARG && strstr(g_err, "bleed=-1"));
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, tex, 0, 1, 1, nullptr, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, tex, 1, 1, 1, inverted_x, nullptr) == DTP_ERR_ARG && strstr(g_err, "x0 > x1"));
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, tex, 1, 1, 1, nullptr, nullptr) == DTP_ERR_ARG && strstr(g_err, "not a live mesh"));
+  EXPECT(dtp_mesh_bleed((dtp_mesh*)not_a_mesh, tex, 1, 1, 0, right, nullptr) == DTP_ERR_ARG && strstr(g_err, "not a live mesh"));
+  EXPECT(dtp_op_mesh_coverage(nullptr, 1, 1, tex, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_op_mesh_coverage((dtp_mesh*)not_a_mesh, 1, 1, nullptr, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_op_mesh_coverage((dtp_mesh*)not_a_mesh, 1, 32769, tex, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_op_mesh_coverage((dtp_mesh*)not_a_mesh, 1, 1, tex, nullptr) == DTP_ERR_ARG && strstr(g_err, "not a live mesh"));
+  EXPECT(dtp_mesh_stroke_bleed(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 17, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "dtp_mesh_stroke_bleed: bleed=17"));
+  EXPECT(dtp_mesh_stroke_bleed(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, -1, nullptr) == DTP_ERR_ARG);
+  EXPECT(dtp_mesh_stroke_bleed(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 2, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "NULL"));
   printf("mesh_host_check: %d checks passed\n", g_checks);
   return 0;
 }
