@@ -141,6 +141,19 @@ static __device__ __forceinline__ void sum_pairs_strided_d(const float* __restri
       if (q + e < n) { s1 += (double)t[e][0]; s2 += (double)t[e][1]; }
   }
 }
+// LayerNorm fold, the mean term: out = rstd * (x W^T - mean * lns) + bias.  The kernels that stage their accumulators through an fp16
+// tile (gemm_kernel, gemm_wide, xattn) subtract mean * lns from the fp32 accumulator BEFORE that rounding and multiply by rstd behind it:
+// rounded first, the two terms of a row whose mean is not small against its sigma cancel only to 2^-11 of |x W^T|, and rstd (up to
+// eps^-1/2 = 1000 on a constant row) multiplies what is left -- 1.1 at eps = 1e-5, 3.5 at 1e-6 on a constant -3 row
+// (tests/test_gpu_norm_eps.py).  col4: four per-column fp32 values (weight row sums, biases) of columns n .. n + 3 (n % 4 == 0), zeros beyond N.
+static __device__ __forceinline__ f32x4 col4(const float* __restrict__ v, int n, int N) {
+  if (n + 4 <= N) return *(const f32x4*)(v + n);
+  f32x4 r = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (n + e < N) r[e] = v[n + e];
+  return r;
+}
 static __device__ __forceinline__ double shfl_xor_d(double v, int o) {
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __shfl_xor(lo, o); hi = __shfl_xor(hi, o);

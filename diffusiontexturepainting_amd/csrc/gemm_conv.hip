@@ -99,29 +99,29 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
   // tiles can REQUEST them before the first DMA (HOIST; round 4) -- loaded behind the k-loop and the staging barriers they were one
   // exposed L2 round trip at the end of every latency-bound launch.  Older than every DMA piece, they do not disturb the counted vmcnt.
   const int fl = p.flags;
+  // Per-sample biases of a grouped problem join the fp32 accumulator BEFORE it is rounded into the fp16 staging tile: they are the GroupNorm
+  // fold's (norm.hip gn_fold_weights_kernel), which cancel the group means the contraction picks up through the folded weights -- with a
+  // group whose mean is not small against its sigma, |x W'^T| is tens to hundreds and its fp16 rounding would outlive the cancellation
+  // (a constant 0.5 group: 3e-2 at eps = 1e-5, 1.3e-1 at 1e-6; tests/test_gpu_norm_eps.py).  The epilogue then adds no bias.
+  const bool bias_first = (fl & GF_BIAS) && !(fl & GF_LNFOLD) && p.batch > 1 && p.bias_bs != 0;
   constexpr int NC = BN / 8;
   const bool vec_ok = ((p.ldc & 7) == 0) && !(fl & GF_OUT_F32) && (!(fl & GF_RESID) || (p.ldr & 7) == 0);
   // A thread owns the same 8-column chunk in every iteration (256 % NC == 0): its per-column vectors (bias, lns) are loaded once,
   // as whole 16-byte loads when the chunk is complete, guarded scalars on the N tail.
   const int nc = tid % NC, n = n0 + nc * 8;
   const bool full = (n + 8 <= p.N);
-  float bv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float bv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   auto load_cols = [&]() {
+    if (bias_first) return;
     if (full) {
       if (fl & GF_BIAS) {
         const f32x4 t0 = *(const f32x4*)(p.bias + n), t1 = *(const f32x4*)(p.bias + n + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { bv[e] = t0[e]; bv[4 + e] = t1[e]; }
       }
-      if (fl & GF_LNFOLD) {
-        const f32x4 t0 = *(const f32x4*)(p.lns + n), t1 = *(const f32x4*)(p.lns + n + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lv[e] = t0[e]; lv[4 + e] = t1[e]; }
-      }
     } else {
       for (int e = 0; e < 8 && n + e < p.N; ++e) {
         if (fl & GF_BIAS) bv[e] = p.bias[n + e];
-        if (fl & GF_LNFOLD) lv[e] = p.lns[n + e];
       }
     }
   };
@@ -309,37 +309,50 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
   // BM rows over the full K = C columns (16 lanes per row, 16-byte loads; the rows are L2/Infinity-Cache resident:
   // they were written by the previous kernel).  Applied in the epilogue, so the normalised tensor never exists.
   float* rowst = (float*)(smem + NS * STAGE);
-  if ((p.flags & GF_LNFOLD) && p.st_in) {
-    // statistics were emitted by the producer of A (GF_ROWSTATS): combine its per-N-tile partials
-    for (int r = tid; r < BM; r += NT) {
-      const int m = m0 + r;
-      float s1 = 0.f, s2 = 0.f;
-      if (m < p.M) sum_pairs_strided(p.st_in + ((size_t)st_m0 + m) * 2, (size_t)st_rows * 2, p.st_parts, s1, s2);
-      const float mean = s1 / (float)p.K;
-      rowst[2 * r] = mean;
-      rowst[2 * r + 1] = rsqrtf(fmaxf(s2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
-    }
-  } else if (p.flags & GF_LNFOLD) {
-    const int l16 = tid & 15, nch = p.K >> 3;
-    for (int r0 = 0; r0 < BM; r0 += NT / 16) {
-      const int r = r0 + (tid >> 4), m = m0 + r;
-      float s1 = 0.f, s2 = 0.f;
-      if (m < p.M) {
-        const f16* row = p.A + (size_t)m * p.lda;
-        for (int c = l16; c < nch; c += 16) {
-          const f16x8 v = *(const f16x8*)(row + c * 8);
+  float* lnst = rowst + 2 * BM;  // [BN] the weight row sums of this tile's columns (zeros beyond N): read when the accumulators are staged
+  if (p.flags & GF_LNFOLD) {
+    // the weight row sum of tile column `tid`: requested together with the loads of the statistics (one memory round trip for both),
+    // parked in LDS behind them and read when the accumulators are staged.  Load and store are UNCONDITIONAL (clamped column, threads
+    // beyond BN repeat the last one): a load whose only use sits behind a second branch leaves, on the path around that use, a pending
+    // destination register that the k-loop reuses -- and hipcc then waits vmcnt(0) in every k-block of every launch (+40 % on the
+    // four-stage tiles)
+    static_assert(BN <= NT, "one row sum per thread");
+    const int lc = min(tid, BN - 1);
+    float lnv = p.lns[min(n0 + lc, p.N - 1)];
+    if (n0 + lc >= p.N) lnv = 0.f;
+    if (p.st_in) {
+      // statistics were emitted by the producer of A (GF_ROWSTATS): combine its per-N-tile partials
+      for (int r = tid; r < BM; r += NT) {
+        const int m = m0 + r;
+        float s1 = 0.f, s2 = 0.f;
+        if (m < p.M) sum_pairs_strided(p.st_in + ((size_t)st_m0 + m) * 2, (size_t)st_rows * 2, p.st_parts, s1, s2);
+        const float mean = s1 / (float)p.K;
+        rowst[2 * r] = mean;
+        rowst[2 * r + 1] = rsqrtf(fmaxf(s2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
+      }
+    } else {
+      const int l16 = tid & 15, nch = p.K >> 3;
+      for (int r0 = 0; r0 < BM; r0 += NT / 16) {
+        const int r = r0 + (tid >> 4), m = m0 + r;
+        float s1 = 0.f, s2 = 0.f;
+        if (m < p.M) {
+          const f16* row = p.A + (size_t)m * p.lda;
+          for (int c = l16; c < nch; c += 16) {
+            const f16x8 v = *(const f16x8*)(row + c * 8);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s1 += f; s2 += f * f; }
+            for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s1 += f; s2 += f * f; }
+          }
+        }
+        s1 = group_allsum<16>(s1); s2 = group_allsum<16>(s2);  // (DPP, common.h: no LDS round trips)
+        if (l16 == 0) {
+          const float mean = s1 / (float)p.K;
+          const float var = fmaxf(s2 / (float)p.K - mean * mean, 0.f);
+          rowst[2 * r] = mean;
+          rowst[2 * r + 1] = rsqrtf(var + p.ln_eps);
         }
       }
-      s1 = group_allsum<16>(s1); s2 = group_allsum<16>(s2);  // (DPP, common.h: no LDS round trips)
-      if (l16 == 0) {
-        const float mean = s1 / (float)p.K;
-        const float var = fmaxf(s2 / (float)p.K - mean * mean, 0.f);
-        rowst[2 * r] = mean;
-        rowst[2 * r + 1] = rsqrtf(var + p.ln_eps);
-      }
     }
+    lnst[lc] = lnv;
   }
   int cur = 0, nxt = NS - 1;  // LDS buffer of k-block t / of k-block t+NS-1
   // One k-block: all 4 k-steps' fragments are requested up front (back-to-back ds_read_b128), then each step's MFMAs start
@@ -495,19 +508,48 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
   // therefore carries fp16 precision unless the launch is split (the slabs above are fp32).  DESIGN.md section 4; tests/test_gpu_exact.py
   // bounds its unsplit cases to |accumulator| <= 2048 for this reason.
   f16* stg = (f16*)smem;
-  if (kh == 0)
+  if (kh == 0) {
+    if ((fl & GF_LNFOLD) || bias_first) {
+      // something leaves (or joins) the accumulator in fp32, before the rounding: the mean term of the LayerNorm fold, mean * lns (the row
+      // sums wait in LDS; common.h, col4), or a per-sample bias as x - (-1) b (bias_first above)
+      float mean[TM];
 #pragma unroll
-  for (int i = 0; i < TN; ++i)
+      for (int j = 0; j < TM; ++j) mean[j] = (fl & GF_LNFOLD) ? rowst[2 * (wm0 + j * 32 + frow)] : -1.f;
 #pragma unroll
-    for (int j = 0; j < TM; ++j) {
-      const int ml = wm0 + j * 32 + frow;
+      for (int i = 0; i < TN; ++i) {
+        f32x4 l[4];  // this lane's 16 columns of n-block i: read once, before the staging stores (which the compiler must assume alias them)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
-        f16x4 v = {(f16)acc[i][j][4 * q], (f16)acc[i][j][4 * q + 1], (f16)acc[i][j][4 * q + 2], (f16)acc[i][j][4 * q + 3]};
-        *(f16x4*)(stg + ml * SLD + nl) = v;
+        for (int q = 0; q < 4; ++q) {
+          const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
+          l[q] = (fl & GF_LNFOLD) ? *(const f32x4*)(lnst + nl) : col4(p.bias, n0 + nl, p.N);
+        }
+#pragma unroll
+        for (int j = 0; j < TM; ++j) {
+          const int ml = wm0 + j * 32 + frow;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
+            f16x4 v = {(f16)(acc[i][j][4 * q] - mean[j] * l[q][0]), (f16)(acc[i][j][4 * q + 1] - mean[j] * l[q][1]),
+                       (f16)(acc[i][j][4 * q + 2] - mean[j] * l[q][2]), (f16)(acc[i][j][4 * q + 3] - mean[j] * l[q][3])};
+            *(f16x4*)(stg + ml * SLD + nl) = v;
+          }
+        }
       }
+    } else {
+#pragma unroll
+      for (int i = 0; i < TN; ++i)
+#pragma unroll
+        for (int j = 0; j < TM; ++j) {
+          const int ml = wm0 + j * 32 + frow;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
+            f16x4 v = {(f16)acc[i][j][4 * q], (f16)acc[i][j][4 * q + 1], (f16)acc[i][j][4 * q + 2], (f16)acc[i][j][4 * q + 3]};
+            *(f16x4*)(stg + ml * SLD + nl) = v;
+          }
+        }
     }
+  }
   __syncthreads();
 
   if (fl & GF_GEGLU) {
@@ -517,18 +559,12 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
     // a thread owns the same 8-column chunk in every iteration (256 % HC == 0): its bias / lns vectors are loaded once, as whole
     // 16-byte vectors (per-element conditional loads make hipcc wait vmcnt(0) after every dword; N % 128 == 0 here)
     const int nc = tid % HC;
-    float ba[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, la[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (fl & GF_BIAS) {
+    float ba[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((fl & GF_BIAS) && !bias_first) {
       const f32x4 t0 = *(const f32x4*)(p.bias + n0 + nc * 8), t1 = *(const f32x4*)(p.bias + n0 + nc * 8 + 4);
       const f32x4 u0 = *(const f32x4*)(p.bias + n0 + BN / 2 + nc * 8), u1 = *(const f32x4*)(p.bias + n0 + BN / 2 + nc * 8 + 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) { ba[e] = t0[e]; ba[4 + e] = t1[e]; bg[e] = u0[e]; bg[4 + e] = u1[e]; }
-    }
-    if (fl & GF_LNFOLD) {
-      const f32x4 t0 = *(const f32x4*)(p.lns + n0 + nc * 8), t1 = *(const f32x4*)(p.lns + n0 + nc * 8 + 4);
-      const f32x4 u0 = *(const f32x4*)(p.lns + n0 + BN / 2 + nc * 8), u1 = *(const f32x4*)(p.lns + n0 + BN / 2 + nc * 8 + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { la[e] = t0[e]; la[4 + e] = t1[e]; lg[e] = u0[e]; lg[4 + e] = u1[e]; }
     }
     for (int idx = tid; idx < BM * HC; idx += NT) {
       const int ml = idx / HC;
@@ -536,13 +572,12 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
       if (m >= p.M) continue;
       const f16x8 a = *(const f16x8*)(stg + ml * SLD + nc * 8);
       const f16x8 g = *(const f16x8*)(stg + ml * SLD + BN / 2 + nc * 8);
-      float mean = 0.f, rstd = 1.f;
-      if (fl & GF_LNFOLD) { mean = rowst[2 * ml]; rstd = rowst[2 * ml + 1]; }
+      const float rstd = (fl & GF_LNFOLD) ? rowst[2 * ml + 1] : 1.f;  // (the mean term left the accumulators before they were staged)
       f16x8 o;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float av = rstd * ((float)a[e] - mean * la[e]) + ba[e];
-        const float gv = rstd * ((float)g[e] - mean * lg[e]) + bg[e];
+        const float av = rstd * (float)a[e] + ba[e];
+        const float gv = rstd * (float)g[e] + bg[e];
         o[e] = (f16)(av * gelu_erf(gv));
       }
       *(f16x8*)(C + (size_t)m * p.ldc + tile_n * (BN / 2) + nc * 8) = o;
@@ -568,10 +603,10 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
       float x[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] = (float)v[e];
-      if (fl & GF_LNFOLD) {
-        const float mean = rowst[2 * ml], rstd = rowst[2 * ml + 1];
+      if (fl & GF_LNFOLD) {  // (the mean term left the accumulators before they were staged)
+        const float rstd = rowst[2 * ml + 1];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = rstd * (x[e] - mean * lv[e]);
+        for (int e = 0; e < 8; ++e) x[e] *= rstd;
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] += bv[e];
@@ -731,6 +766,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_rows_kernel(const GemmParam
   if (lane == 0) { p.st_out[(size_t)m * 2] = s1; p.st_out[(size_t)m * 2 + 1] = s2; }
 }
 
+// the pipeline stages + the per-row LayerNorm statistics (mean, rstd) + the weight row sums of the tile's columns (GF_LNFOLD)
+constexpr int gemm_lds_bytes(int BM, int BN, int NS) { return NS * (BM + BN) * 128 + BM * 8 + BN * 4; }
+
 template <int BM, int BN, int NS, int KH, int LW, bool CONV>
 int launch_tile_mode(const GemmParams& pin, hipStream_t s) {
   GemmParams p = pin;
@@ -738,8 +776,8 @@ int launch_tile_mode(const GemmParams& pin, hipStream_t s) {
   static const bool xcd_off = [] { const char* e = getenv("DTP_NO_XCD_SPLIT"); return e && e[0] && e[0] != '0'; }();
   const bool xs = !xcd_off && p.batch <= 1 && dtp_xcd_split_ok(tiles, p.splits);
   if (xs) p.flags |= GF_XCDSPLIT;
-  constexpr int lds = NS * (BM + BN) * 128 + BM * 8;  // + per-row LayerNorm statistics
-  static_assert(lds - BM * 8 >= BM * (BN + 8) * 2, "staging tile must fit in the pipeline buffers");
+  constexpr int lds = gemm_lds_bytes(BM, BN, NS);
+  static_assert(NS * (BM + BN) * 128 >= BM * (BN + 8) * 2, "staging tile must fit in the pipeline buffers");
   static_assert(lds <= 160 * 1024, "LDS budget");
   const dim3 grid = xs ? dim3(tiles * p.splits, 1, 1) : dim3(tiles, p.batch > 1 ? p.batch : 1, p.splits);
   hipLaunchKernelGGL((gemm_kernel<BM, BN, NS, KH, LW, CONV>), grid, dim3(256 * KH + 64 * LW), lds, s, p);
@@ -772,18 +810,18 @@ int launch_tile(const GemmParams& p, hipStream_t s) {
 
 void dtp_gemm_init() {  // raise the dynamic-LDS limit once, outside any stream capture
 #define SET_ATTR(BM, BN, NS) \
-  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NS*(BM + BN) * 128 + BM * 8); \
-  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NS*(BM + BN) * 128 + BM * 8);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(BM, BN, NS)); \
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(BM, BN, NS));
   FOR_ALL_VARIANTS(SET_ATTR)
 #undef SET_ATTR
 #define SET_ATTR2(BM, BN, NS) \
-  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 2, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NS*(BM + BN) * 128 + BM * 8); \
-  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NS*(BM + BN) * 128 + BM * 8);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 2, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(BM, BN, NS)); \
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(BM, BN, NS));
   FOR_ALL_KH2(SET_ATTR2)
 #undef SET_ATTR2
 #define SET_ATTR3(BM, BN, NS, LW) \
-  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, LW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, NS*(BM + BN) * 128 + BM * 8); \
-  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, LW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, NS*(BM + BN) * 128 + BM * 8);
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, LW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(BM, BN, NS)); \
+  (void)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, NS, 1, LW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(BM, BN, NS));
   FOR_ALL_LW(SET_ATTR3)
 #undef SET_ATTR3
 }

@@ -179,36 +179,49 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
 
   // ---- LayerNorm fold: per-row mean / rstd of this tile's BM rows (from the producer's partial sums, or computed here)
   float* rowst = (float*)(smem + 2 * STAGE);
+  float* lnst = rowst + 2 * BM;  // [BN] the weight row sums of this tile's columns (zeros beyond N): read when the accumulators are staged
   const int st_rows = p.st_rows > 0 ? p.st_rows : p.M;
-  if ((p.flags & GF_LNFOLD) && p.st_in) {
-    for (int r = tid; r < BM; r += NT) {
-      const int m = m0 + r;
-      float s1 = 0.f, s2 = 0.f;
-      if (m < p.M) sum_pairs_strided(p.st_in + (size_t)m * 2, (size_t)st_rows * 2, p.st_parts, s1, s2);
-      const float mean = s1 / (float)p.K;
-      rowst[2 * r] = mean;
-      rowst[2 * r + 1] = rsqrtf(fmaxf(s2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
-    }
-  } else if (p.flags & GF_LNFOLD) {
-    const int l16 = tid & 15, nch = p.K >> 3;
-    for (int r0 = 0; r0 < BM; r0 += NT / 16) {
-      const int r = r0 + (tid >> 4), m = m0 + r;
-      float s1 = 0.f, s2 = 0.f;
-      if (m < p.M) {
-        const f16* row = p.A + (size_t)m * p.lda;
-        for (int c = l16; c < nch; c += 16) {
-          const f16x8 v = *(const f16x8*)(row + c * 8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s1 += f; s2 += f * f; }
-        }
-      }
-      s1 = group_allsum<16>(s1); s2 = group_allsum<16>(s2);
-      if (l16 == 0) {
+  if (p.flags & GF_LNFOLD) {
+    // the weight row sum of tile column `tid`: requested together with the loads of the statistics (one memory round trip for both),
+    // parked in LDS behind them and read when the accumulators are staged.  Load and store are UNCONDITIONAL (clamped column, threads
+    // beyond BN repeat the last one): a load whose only use sits behind a second branch leaves, on the path around that use, a pending
+    // destination register that the k-loop reuses -- and hipcc then waits vmcnt(0) in every k-block of every launch (+40 % on the
+    // four-stage tiles)
+    static_assert(BN <= NT, "one row sum per thread");
+    const int lc = min(tid, BN - 1);
+    float lnv = p.lns[min(n0 + lc, p.N - 1)];
+    if (n0 + lc >= p.N) lnv = 0.f;
+    if (p.st_in) {
+      for (int r = tid; r < BM; r += NT) {
+        const int m = m0 + r;
+        float s1 = 0.f, s2 = 0.f;
+        if (m < p.M) sum_pairs_strided(p.st_in + (size_t)m * 2, (size_t)st_rows * 2, p.st_parts, s1, s2);
         const float mean = s1 / (float)p.K;
         rowst[2 * r] = mean;
         rowst[2 * r + 1] = rsqrtf(fmaxf(s2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
       }
+    } else {
+      const int l16 = tid & 15, nch = p.K >> 3;
+      for (int r0 = 0; r0 < BM; r0 += NT / 16) {
+        const int r = r0 + (tid >> 4), m = m0 + r;
+        float s1 = 0.f, s2 = 0.f;
+        if (m < p.M) {
+          const f16* row = p.A + (size_t)m * p.lda;
+          for (int c = l16; c < nch; c += 16) {
+            const f16x8 v = *(const f16x8*)(row + c * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s1 += f; s2 += f * f; }
+          }
+        }
+        s1 = group_allsum<16>(s1); s2 = group_allsum<16>(s2);
+        if (l16 == 0) {
+          const float mean = s1 / (float)p.K;
+          rowst[2 * r] = mean;
+          rowst[2 * r + 1] = rsqrtf(fmaxf(s2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
+        }
+      }
     }
+    lnst[lc] = lnv;
   }
 
   int cur = 0;
@@ -285,18 +298,43 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
   for (int e = 0; e < EP; ++e) {
     __syncthreads();  // pass 0: every wave finished reading the last stage; pass 1: the staging tile was consumed
     if (wm0 / ROWS_EP == e) {
+      if (fl & GF_LNFOLD) {
+        // the mean term of the LayerNorm fold, mean * lns, leaves the accumulator in fp32, before the rounding (the row sums wait in LDS;
+        // common.h, col4)
+        float mean[TM];
 #pragma unroll
-      for (int i = 0; i < TN; ++i)
+        for (int j = 0; j < TM; ++j) mean[j] = rowst[2 * (wm0 + j * 32 + frow)];
 #pragma unroll
-        for (int j = 0; j < TM; ++j) {
-          const int ml = wm0 - e * ROWS_EP + j * 32 + frow;
+        for (int i = 0; i < TN; ++i) {
+          f32x4 l[4];  // this lane's 16 columns of n-block i: read once, before the staging stores (which the compiler must assume alias them)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
-            f16x4 v = {(f16)acc[i][j][4 * q], (f16)acc[i][j][4 * q + 1], (f16)acc[i][j][4 * q + 2], (f16)acc[i][j][4 * q + 3]};
-            *(f16x4*)(stg + ml * SLD + nl) = v;
+          for (int q = 0; q < 4; ++q) l[q] = *(const f32x4*)(lnst + wn0 + i * 32 + 8 * q + 4 * fhalf);
+#pragma unroll
+          for (int j = 0; j < TM; ++j) {
+            const int ml = wm0 - e * ROWS_EP + j * 32 + frow;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
+              f16x4 v = {(f16)(acc[i][j][4 * q] - mean[j] * l[q][0]), (f16)(acc[i][j][4 * q + 1] - mean[j] * l[q][1]),
+                         (f16)(acc[i][j][4 * q + 2] - mean[j] * l[q][2]), (f16)(acc[i][j][4 * q + 3] - mean[j] * l[q][3])};
+              *(f16x4*)(stg + ml * SLD + nl) = v;
+            }
           }
         }
+      } else {
+#pragma unroll
+        for (int i = 0; i < TN; ++i)
+#pragma unroll
+          for (int j = 0; j < TM; ++j) {
+            const int ml = wm0 - e * ROWS_EP + j * 32 + frow;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
+              f16x4 v = {(f16)acc[i][j][4 * q], (f16)acc[i][j][4 * q + 1], (f16)acc[i][j][4 * q + 2], (f16)acc[i][j][4 * q + 3]};
+              *(f16x4*)(stg + ml * SLD + nl) = v;
+            }
+          }
+      }
     }
     __syncthreads();
     const int mbase = m0 + e * ROWS_EP;
@@ -307,18 +345,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
         static_assert(NT % IT == 0, "a thread owns one output chunk");
         const int item = tid % IT, g = item >> 3, nc = item & 7;
         const int ca = g * 128 + nc * 8, cg = ca + 64;
-        float ba[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, la[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        float ba[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fl & GF_BIAS) {
           const f32x4 t0 = *(const f32x4*)(p.bias + n0 + ca), t1 = *(const f32x4*)(p.bias + n0 + ca + 4);
           const f32x4 u0 = *(const f32x4*)(p.bias + n0 + cg), u1 = *(const f32x4*)(p.bias + n0 + cg + 4);
 #pragma unroll
           for (int x = 0; x < 4; ++x) { ba[x] = t0[x]; ba[4 + x] = t1[x]; bg[x] = u0[x]; bg[4 + x] = u1[x]; }
-        }
-        if (fl & GF_LNFOLD) {
-          const f32x4 t0 = *(const f32x4*)(p.lns + n0 + ca), t1 = *(const f32x4*)(p.lns + n0 + ca + 4);
-          const f32x4 u0 = *(const f32x4*)(p.lns + n0 + cg), u1 = *(const f32x4*)(p.lns + n0 + cg + 4);
-#pragma unroll
-          for (int x = 0; x < 4; ++x) { la[x] = t0[x]; la[4 + x] = t1[x]; lg[x] = u0[x]; lg[4 + x] = u1[x]; }
         }
         const bool col_ok = (n0 + cg + 8 <= p.N);  // N % 128 == 0 for GEGLU: whole groups are in or out
         for (int idx = tid; idx < ROWS_EP * IT; idx += NT) {
@@ -326,13 +358,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
           if (m >= p.M || !col_ok) continue;
           const f16x8 a = *(const f16x8*)(stg + ml * SLD + ca);
           const f16x8 gt = *(const f16x8*)(stg + ml * SLD + cg);
-          float mean = 0.f, rstd = 1.f;
-          if (fl & GF_LNFOLD) { mean = rowst[2 * (e * ROWS_EP + ml)]; rstd = rowst[2 * (e * ROWS_EP + ml) + 1]; }
+          const float rstd = (fl & GF_LNFOLD) ? rowst[2 * (e * ROWS_EP + ml) + 1] : 1.f;  // (the mean term left the accumulators before they were staged)
           f16x8 o;
 #pragma unroll
           for (int x = 0; x < 8; ++x) {
-            const float av = rstd * ((float)a[x] - mean * la[x]) + ba[x];
-            const float gv = rstd * ((float)gt[x] - mean * lg[x]) + bg[x];
+            const float av = rstd * (float)a[x] + ba[x];
+            const float gv = rstd * (float)gt[x] + bg[x];
             o[x] = (f16)(av * gelu_erf(gv));
           }
           *(f16x8*)((f16*)p.C + (size_t)m * p.ldc + (size_t)(tile_n * G + g) * 64 + nc * 8) = o;
@@ -344,17 +375,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
     constexpr int NTE = (NT / NC) * NC;
     const int nc = tid % NC, n = n0 + nc * 8;
     const bool col_ok = (tid < NTE) && (n + 8 <= p.N);  // N % 8 == 0 is required by the launcher
-    float bv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float bv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (col_ok) {
       if (fl & GF_BIAS) {
         const f32x4 t0 = *(const f32x4*)(p.bias + n), t1 = *(const f32x4*)(p.bias + n + 4);
 #pragma unroll
         for (int x = 0; x < 4; ++x) { bv[x] = t0[x]; bv[4 + x] = t1[x]; }
-      }
-      if (fl & GF_LNFOLD) {
-        const f32x4 t0 = *(const f32x4*)(p.lns + n), t1 = *(const f32x4*)(p.lns + n + 4);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) { lv[x] = t0[x]; lv[4 + x] = t1[x]; }
       }
     }
     // residual rows three iterations ahead (three-register ring, unconditional loads from clamped rows): see gemm_conv.hip
@@ -378,10 +404,10 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
         float x[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) x[k] = (float)v[k];
-        if (fl & GF_LNFOLD) {
-          const float mean = rowst[2 * (e * ROWS_EP + ml)], rstd = rowst[2 * (e * ROWS_EP + ml) + 1];
+        if (fl & GF_LNFOLD) {  // (the mean term left the accumulators before they were staged)
+          const float rstd = rowst[2 * (e * ROWS_EP + ml) + 1];
 #pragma unroll
-          for (int k = 0; k < 8; ++k) x[k] = rstd * (x[k] - mean * lv[k]);
+          for (int k = 0; k < 8; ++k) x[k] *= rstd;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) x[k] += bv[k];
@@ -424,7 +450,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
 }
 
 template <int BM, int BN, int WM, int WN>
-constexpr int wide_lds() { return 2 * (BM + BN) * 128 + BM * 8; }
+constexpr int wide_lds() { return 2 * (BM + BN) * 128 + BM * 8 + BN * 4; }  // stages + (mean, rstd) per row + the row sums of the columns
 
 template <int BM, int BN, int WM, int WN>
 int launch_wide(const GemmParams& p, hipStream_t s) {

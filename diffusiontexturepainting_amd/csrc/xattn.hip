@@ -76,7 +76,13 @@ __global__ __launch_bounds__(256) void xattn_kernel(const XattnParams p) {
   }
   // (epilogue 1: this thread's chunk of the per-sample score bias and weight row sums)
   const f32x4 e1b0 = *(const f32x4*)(p.b1 + (size_t)smp * 128 + nc * 8), e1b1 = *(const f32x4*)(p.b1 + (size_t)smp * 128 + nc * 8 + 4);
-  const f32x4 e1l0 = *(const f32x4*)(p.lns1 + (size_t)smp * 128 + nc * 8), e1l1 = *(const f32x4*)(p.lns1 + (size_t)smp * 128 + nc * 8 + 4);
+  // (the weight row sums of THIS LANE's 32 score columns: the mean term of the LayerNorm fold leaves the accumulators before they are staged)
+  f32x4 e1l[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      e1l[i][q] = *(const f32x4*)(p.lns1 + (size_t)smp * 128 + ((tid >> 6) & 1) * 64 + i * 32 + 8 * q + 4 * ((tid & 63) >> 5));
   f16x8 rv[EIT];
 #pragma unroll
   for (int it = 0; it < EIT; ++it) {
@@ -214,23 +220,33 @@ __global__ __launch_bounds__(256) void xattn_kernel(const XattnParams p) {
       }
     }
   };
+  {  // the mean term of the LayerNorm fold, in fp32 before the scores are rounded to fp16 (common.h, col4)
+    const float mean = rowst[2 * (wm0 + frow)];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][4 * q + e] -= mean * e1l[i][q][e];
+      }
+  }
   stage_acc();
   __syncthreads();
 
   // ---- epilogue 1: LayerNorm fold + bias + softmax over each 16-column head group (sm_valid columns) -> P (fp16) into the
   // phase-2 A-operand image.  A thread owns the same 8-column chunk in every iteration; its pair lane (nc ^ 1) holds the other half.
   {
-    float bv[8], lv[8];
+    float bv[8];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { bv[e] = e1b0[e]; bv[4 + e] = e1b1[e]; lv[e] = e1l0[e]; lv[4 + e] = e1l1[e]; }
+    for (int e = 0; e < 4; ++e) { bv[e] = e1b0[e]; bv[4 + e] = e1b1[e]; }
     const int half = (nc & 1) * 8;
     for (int idx = tid; idx < XBM * NC; idx += 256) {
       const int ml = idx / NC;
       const f16x8 v = *(const f16x8*)(stg + ml * XSLD + nc * 8);
-      const float mean = rowst[2 * ml], rstd = rowst[2 * ml + 1];
+      const float rstd = rowst[2 * ml + 1];
       float x[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = rstd * ((float)v[e] - mean * lv[e]);
+      for (int e = 0; e < 8; ++e) x[e] = rstd * (float)v[e];
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] += bv[e];
       float mx = -3.0e38f;

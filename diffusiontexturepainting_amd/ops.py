@@ -366,11 +366,17 @@ def gn_linear(x, wp, n_out, bias, gamma, beta, groups=32, eps=1e-6, col_ranges=4
 
 
 def layernorm(x, gamma, beta, eps=1e-5):
+    """x f16 [..., C] contiguous, or a 2-D row view [rows, C] of a wider / longer buffer (unit column stride, any row pitch)."""
     lib = _lib.load()
     c = x.shape[-1]
     rows = x.numel() // c
-    y = torch.empty_like(x)
-    check(lib.dtp_op_layernorm(ptr(x), c, ptr(y), c, ptr(gamma), ptr(beta), rows, c, eps, _stream()), "layernorm")
+    ldx = c
+    if not x.is_contiguous():
+        if x.dim() != 2 or x.stride(1) != 1:
+            raise ValueError(f"layernorm: a non-contiguous input must be a 2-D row view with unit column stride, got strides {x.stride()}")
+        ldx = x.stride(0)
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    check(lib.dtp_op_layernorm(ptr(x), ldx, ptr(y), c, ptr(gamma), ptr(beta), rows, c, eps, _stream()), "layernorm")
     return y
 
 
