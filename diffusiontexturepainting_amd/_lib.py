@@ -52,6 +52,22 @@ class MeshStrokeOpts(C.Structure):  # dtp_mesh_stroke_opts
                 ("strength", C.c_double)]
 
 
+class Ray(C.Structure):  # dtp_ray
+    _fields_ = [("origin", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+class MeshHit(C.Structure):  # dtp_mesh_hit
+    _fields_ = [("face", C.c_int), ("w", C.c_float * 3), ("pos", C.c_float * 3), ("normal", C.c_float * 3), ("uv", C.c_float * 2),
+                ("t", C.c_float)]
+
+
+class PathState(C.Structure):  # dtp_path_state
+    _fields_ = [("has_prev", C.c_int), ("prev", C.c_float * 3)]
+
+
+PICK_MAX_RAYS = 4096
+
+
 class ProfRow(C.Structure):
     _fields_ = [("kind", C.c_int), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -179,6 +195,10 @@ SYMBOLS = {
     "dtp_mesh_bleed": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i * 4), _vp]),
     "dtp_op_mesh_coverage": (_i, [_vp, _i, _i, _vp, _vp]),
     "dtp_mesh_bleed_offsets": (_i, [_i, C.POINTER(_i), C.POINTER(C.c_byte)]),
+    "dtp_mesh_pick": (_i, [_vp, C.POINTER(Ray), _i, _vp, _vp]),
+    "dtp_mesh_ray_frame": (_i, [C.POINTER(_f * 3), C.POINTER(_f * 3), C.POINTER(_f * 12)]),
+    "dtp_mesh_path_plan": (_i, [_vp, _i, _f, C.POINTER(PathState), _vp, _vp, _vp, _i, C.POINTER(_i)]),
+    "dtp_op_mesh_pick": (_i, [_vp, C.POINTER(Ray), _i, _vp, _vp]),
 }
 
 

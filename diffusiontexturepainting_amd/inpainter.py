@@ -173,6 +173,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         # noise: seeded once, never reseeded (trt_model.py:54, stable_diffusion_pipeline.py:154-156)
         self.generator = torch.Generator(device=self._device).manual_seed(seed)
         self.stream = torch.cuda.Stream(device=self._device)
+        self.pick_stream = torch.cuda.Stream(device=self._device)  # pick() alone runs here, beside whatever self.stream has queued
         self.conditioning = None
         self.image = None
         self._slots = {}  # conditioning slot -> (image [1,3,R,R], (cond, uncond))
@@ -482,6 +483,37 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         if self._check_finite and not self.last_stamp_finite():
             raise _lib.DtpError("stamp produced NaN/inf (check_finite): latents or decoded image are not finite")
         return texture
+
+    def pick(self, mesh, origins, directions):
+        """The closest hit of n rays on `mesh` (dtp_mesh_pick; what the Kit app asks MeshRaycast.raycast_closest for, ui/brush.py:154-156):
+        origins, directions [n, 3] (or [3]), n in 1..4096; directions need not be unit vectors.  -> a dict of CPU tensors: face i32 [n]
+        (-1: no hit, and zeros in every other field), w f32 [n, 3] the barycentric weights, pos [n, 3], normal [n, 3] the face's unit
+        normal turned towards the ray's origin, uv [n, 2], t [n] the distance along the normalised direction.  The rule is the render's
+        visibility at one sample per ray, exact and order-free; both sides of a face can be hit.  It runs on self.pick_stream and waits
+        for that stream only: it takes no part in the hand-shake of self.stream, so it answers while a queued stroke is still painting.
+        It reads the mesh's vertices, faces and UVs alone.  One pick of a mesh at a time."""
+        if not isinstance(mesh, _mesh.Mesh):
+            raise ValueError("mesh must come from load_mesh()")
+        rays, n = _mesh.rays(origins, directions)
+        rec = torch.zeros(n, _mesh.HIT_WORDS, dtype=torch.int32)
+        check(self._lib.dtp_mesh_pick(mesh.handle, C.cast(rays.data_ptr(), C.POINTER(_lib.Ray)), n, ptr(rec),
+                                      C.c_void_p(self.pick_stream.cuda_stream)), "dtp_mesh_pick")
+        return _mesh.hits_dict(rec)
+
+    def paint_mesh_path(self, mesh, texture, origins, directions, radius, stamps_per_radius=1, fov=None, state=None, **stroke_kwargs):
+        """From the pointer's rays to paint (the Kit app's BrushTool.handle_mouse_move, ui/brush.py:139-198): pick(mesh, origins,
+        directions) -> mesh.plan_path(hits, radius / stamps_per_radius, state) -> paint_mesh_stroke with the planned stamps.  radius:
+        the brush radius in world units; fov defaults to it.  state: None for a new path, or what the last call returned, so that a
+        path can be painted as the pointer events arrive.  Every other keyword is paint_mesh_stroke's (seeds, modes -- one mode for the
+        whole path --, bleed, mask, settings ...); a stamp whose camera is refused is refused by the stroke as always.  A path that
+        plans no stamp (all rays miss, or the pointer has not moved far enough) paints nothing.  -> (texture, state, stamps painted)."""
+        hits = self.pick(mesh, origins, directions)
+        positions, normals, prevs, state = _mesh.plan_path(hits, float(radius) / float(stamps_per_radius), state)
+        n = positions.shape[0]
+        if n == 0:
+            return texture, state, 0
+        self.paint_mesh_stroke(mesh, texture, positions, normals, prevs, float(radius if fov is None else fov), **stroke_kwargs)
+        return texture, state, n
 
     def bleed_texture(self, mesh, texture, bleed, rect=None):
         """The bleed pass of paint_mesh_stroke on its own (dtp_mesh_bleed), for a texture that was loaded from a file or painted without

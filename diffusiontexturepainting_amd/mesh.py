@@ -1,7 +1,9 @@
 """The Python side of the mesh strokes (include/dtp.h: dtp_mesh_*): the device-resident mesh, the host-only camera and
 the stamp array of a stroke.  The stroke itself is MI355ConditionalInpainter.paint_mesh_stroke; the two kernels' op-level entry points
 are ops.mesh_render / ops.mesh_backproject.  The bleed pass that pads the UV charts is paint_mesh_stroke(bleed=k) and
-MI355ConditionalInpainter.bleed_texture; ops.mesh_coverage / ops.mesh_bleed_offsets show what it works from."""
+MI355ConditionalInpainter.bleed_texture; ops.mesh_coverage / ops.mesh_bleed_offsets show what it works from.  Picking:
+the host-only ray frame and the stamp spacing of a pointer path live here; the pick itself is MI355ConditionalInpainter.pick and the
+pointer-to-paint call paint_mesh_path."""
 import ctypes as C
 
 import torch
@@ -28,6 +30,72 @@ def mesh_camera(position, normal, prev_position, fov):
     return torch.tensor(list(out), dtype=torch.float32).reshape(3, 4)
 
 
+def ray_frame(origin, direction):
+    """The frame of a picking ray (dtp_mesh_ray_frame: host only, needs no GPU): float32 [3, 4], rows (right, up, back) with
+    back = -normalize(direction) and right = normalize(cross(helper, back)), helper the unit axis of the smallest |direction_k|, each
+    followed by -row . origin.  The ray is the frame's -z axis through x = y = 0.  DtpError for a zero or non-finite direction, a
+    non-finite origin or a frame that does not fit fp32."""
+    out = (C.c_float * 12)()
+    check(_lib.load().dtp_mesh_ray_frame(C.byref(_vec3(origin, "origin")), C.byref(_vec3(direction, "direction")), C.byref(out)),
+          "dtp_mesh_ray_frame")
+    return torch.tensor(list(out), dtype=torch.float32).reshape(3, 4)
+
+
+def rays(origins, directions):
+    """-> (float32 [n, 6] on the host: the dtp_ray array of a pick, n).  origins, directions: [n, 3] (or [3] for one ray)."""
+    o = torch.as_tensor(origins).detach().to("cpu", torch.float32).reshape(-1, 3)
+    d = torch.as_tensor(directions).detach().to("cpu", torch.float32).reshape(-1, 3)
+    if o.shape[0] != d.shape[0]:
+        raise ValueError(f"{o.shape[0]} origins and {d.shape[0]} directions")
+    return torch.cat([o, d], dim=1).contiguous(), o.shape[0]
+
+
+HIT_WORDS = 13  # sizeof(dtp_mesh_hit) / 4
+
+
+def hits_dict(records):
+    """int32 [n, 13] (dtp_mesh_hit records as words) -> dict(face i32 [n], w f32 [n, 3], pos [n, 3], normal [n, 3], uv [n, 2], t [n])."""
+    fl = records.view(torch.float32)
+    return dict(face=records[:, 0].clone(), w=fl[:, 1:4].clone(), pos=fl[:, 4:7].clone(), normal=fl[:, 7:10].clone(), uv=fl[:, 10:12].clone(),
+                t=fl[:, 12].clone())
+
+
+def _hit_records(hits):
+    """The inverse of hits_dict, on the host; a planner needs face, pos and normal only: the other fields may be missing."""
+    face = torch.as_tensor(hits["face"]).detach().to("cpu", torch.int32).reshape(-1)
+    n = face.shape[0]
+    rec = torch.zeros(n, HIT_WORDS, dtype=torch.int32)
+    rec[:, 0] = face
+    fl = rec.view(torch.float32)
+    for key, sl in (("w", slice(1, 4)), ("pos", slice(4, 7)), ("normal", slice(7, 10)), ("uv", slice(10, 12)), ("t", slice(12, 13))):
+        if key in hits:
+            fl[:, sl] = torch.as_tensor(hits[key]).detach().to("cpu", torch.float32).reshape(n, -1)
+    return rec
+
+
+def plan_path(hits, stamp_distance, state=None):
+    """The stamps of a pointer path (dtp_mesh_path_plan: host only; the Kit app's ui/brush.py:158-198): hits the dict model.pick
+    returns (face, pos and normal are used), in pointer order; stamp_distance = radius / stamps_per_radius.  A miss is skipped, the
+    first hit only starts the path, and the chord from the previous hit to a hit at least stamp_distance away is cut into
+    int(dist / stamp_distance) equal steps: each stamp carries that hit's normal and the stamp before it as its previous position.
+    state: None for a new path, or what an earlier call returned (a path may arrive in several calls).
+    -> (positions f32 [m, 3], normals [m, 3], prev_positions [m, 3], state) for paint_mesh_stroke."""
+    lib = _lib.load()
+    rec = _hit_records(hits)
+    n = rec.shape[0]
+    st = _lib.PathState(0, (0.0, 0.0, 0.0)) if state is None else _lib.PathState(int(state["has_prev"]), tuple(float(x) for x in state["prev"]))
+    count = C.c_int(-1)
+    rc = lib.dtp_mesh_path_plan(_lib.ptr(rec), n, C.c_float(float(stamp_distance)), C.byref(st), None, None, None, 0, C.byref(count))
+    m = count.value
+    if rc != 0 and m <= 0:
+        check(rc, "dtp_mesh_path_plan")
+    out = torch.zeros(3, max(m, 0), 3, dtype=torch.float32)
+    if m > 0:
+        check(lib.dtp_mesh_path_plan(_lib.ptr(rec), n, C.c_float(float(stamp_distance)), C.byref(st), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]),
+                                     m, C.byref(count)), "dtp_mesh_path_plan")
+    return out[0], out[1], out[2], dict(has_prev=bool(st.has_prev), prev=tuple(st.prev))
+
+
 class Mesh:
     """A mesh on the device of a handle (dtp_mesh_create): vertices [V, 3] float, faces [F, 3] int, face_uvs [F, 3, 2] float (UVs in
     0..1, v up; kaolin's SurfaceMesh.face_uvs), copied from the host.  Freed by close(), by garbage collection, or with its handle."""
@@ -50,6 +118,9 @@ class Mesh:
     @property
     def handle(self):
         return self._h
+
+    ray_frame = staticmethod(ray_frame)  # host only: see the functions of this module
+    plan_path = staticmethod(plan_path)
 
     def close(self):
         if getattr(self, "_h", None):

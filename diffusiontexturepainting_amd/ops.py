@@ -614,6 +614,17 @@ def mesh_coverage(mesh, H, W):
     return out.bool()
 
 
+def mesh_pick(mesh, origins, directions):
+    """dtp_op_mesh_pick: the closest hit of n rays on `mesh` (a mesh.Mesh) with the records left on the device -> the dict of
+    MI355ConditionalInpainter.pick, as tensors on the current device.  On the current stream, which it waits for."""
+    from . import mesh as _mesh
+    lib = _lib.load()
+    rays, n = _mesh.rays(origins, directions)
+    rec = torch.zeros(n, _mesh.HIT_WORDS, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+    check(lib.dtp_op_mesh_pick(mesh.handle, C.cast(rays.data_ptr(), C.POINTER(_lib.Ray)), n, ptr(rec), _stream()), "mesh_pick")
+    return _mesh.hits_dict(rec)
+
+
 def mesh_bleed_offsets(k):
     """dtp_mesh_bleed_offsets (host only, needs no GPU): the candidate offsets (di, dj) of a gutter texel's source at radius k in 1..16,
     sorted by (di^2 + dj^2, di, dj) -> int8 [n, 2].  The table of a smaller radius is a prefix of it."""

@@ -24,7 +24,7 @@ extern "C" {
  * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) and the strokes (dtp_stroke, dtp_stroke_plan, dtp_last_stroke_info,
  * dtp_op_stroke_gather, dtp_op_stroke_paste) and the mesh strokes (dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_camera, dtp_mesh_stroke,
  * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
- * dtp_op_mesh_coverage) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
+ * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
  * caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -350,6 +350,63 @@ int dtp_mesh_bleed(dtp_mesh* mesh, uint8_t* texture, int H, int W, int bleed, co
 int dtp_op_mesh_coverage(dtp_mesh* mesh, int H, int W, uint8_t* out, dtp_stream s);
 int dtp_mesh_bleed_offsets(int radius, int* count, signed char* di_dj);
 
+/* ---------------------------------------------------------------- picking on a mesh
+ * replaces: what the Kit app's brush tool does with every pointer event (kit_app/.../python/ui/brush.py:139-198): a camera ray cast
+ * against the mesh with MeshRaycast.raycast_closest (an Omniverse extension), and the chord from the previous hit to the new one cut
+ * into stamps radius / stamps_per_radius apart.  Picking is the render's visibility rule applied to one sample per ray; nothing is
+ * compared under a tolerance.  The spacing rule was written from the source of brush.py, not captured from a Kit run.
+ *
+ * The ray frame (dtp_mesh_ray_frame; host only, in double from the fp32 origin o and direction d, rounded to fp32 once):
+ * b = -normalize(d), so the frame looks down -z as the stamp camera does; helper = the unit axis k of the smallest |d_k| (the lowest k
+ * on a tie); r = normalize(cross(helper, b)), u = cross(b, r); out = the rows (r, u, b), each followed by t = -row . o, laid out as
+ * dtp_mesh_camera's.  The ray is the frame's -z axis through x = y = 0.  DTP_ERR_ARG for a zero or non-finite direction, a non-finite
+ * origin, a frame that does not fit fp32.
+ * The grid: the eight corners of the vertices' bounding box go through the fp32 frame in double, x = ((m0 vx + m1 vy) + m2 vz) + t for
+ * rows r and u; S = 2^e with e the largest integer such that S max(|x|, |y|) over the corners is <= 2^25, clamped to -64 <= e <= 64 (all
+ * corners on the ray: 64).  S is a power of two: scaling by it is exact and no vertex of the mesh reaches the +-2^26 clamp of the snap.
+ * Per face (fp32, every operation rounded once, no contraction): the camera-space x, y, z of the three vertices as the render computes
+ * them, cam_k = ((m0 x + m1 y) + m2 z) + t; X = snap(x S), Y = snap(y S) with snap(v) = rint(v) clamped to +-2^26; the render's integer
+ * coverage at the single centre (0, 0): int64 edge functions, both windings (multiplied by the sign of the area), the top-left fill
+ * rule, so a ray through an edge or a vertex that faces of a closed surface share has exactly one of them, never none.  A face of zero
+ * snapped area or with a non-finite camera coordinate is excluded.  w_k = (float)E_k / (float)A; z = (w0 z0 + w1 z1) + w2 z2, -0 taken
+ * as +0.  A covered face with z <= 0 (not behind the origin) is a candidate.  Both sides of a face can be hit: there is no winding
+ * option.
+ * The hit is the candidate with the largest (z, -face index), the render's order: nearer wins, a tie goes to the lower index, whatever
+ * the order of faces, workgroups or launches (a 64-bit atomic max over the order-preserving bits of z and ~face).
+ * The record: face (-1: no hit, and every other field 0); w[3]; pos = (w0 p0 + w1 p1) + w2 p2 per component on the world vertices;
+ * normal = the face's unit geometric normal, n = cross(p1 - p0, p2 - p0) with each component a product minus a product,
+ * n / sqrt((nx nx + ny ny) + nz nz), negated when (nx dx + ny dy) + nz dz > 0 so that normal . d <= 0: it faces the ray's origin, which
+ * is what the stamp camera needs; uv interpolated like pos; t = 0 - z, the distance along the ray in units of |d| = 1.
+ *
+ * dtp_mesh_pick: rays host dtp_ray[n], 1 <= n <= 4096; out_host host dtp_mesh_hit[n].  Every check comes before any device call:
+ * DTP_ERR_ARG, naming the ray where there is one, for a NULL pointer, a mesh that is not alive, n outside 1..4096, a ray
+ * dtp_mesh_ray_frame refuses; a refused call writes nothing.  The call enqueues on `s` (frames in, two kernels, records out), waits
+ * for `s` ONLY, and fills out_host.  `s` should NOT be the stream of the strokes: a stroke only enqueues, and sixteen 512^2 stamps are
+ * about 1.5 s of queued device work; a pick behind them on the same stream would answer after they finish, and the pointer would lag
+ * the paint by the whole backlog.  The kernels read only what dtp_mesh_create copied (vertices, faces, face UVs); they neither read nor
+ * write the per-face records, the window and valid lists, the coverage mask or anything else a stroke in flight writes, so a pick runs
+ * beside a stroke of the same mesh.  Its own buffers (ray frames, one 64-bit slot per ray, the records, a pinned host copy) are
+ * allocated at the first pick of a mesh, grow only when n exceeds what is held (in steps of 256 rays; growing frees, which waits for
+ * the device), and are freed with the mesh; dtp_mesh_create allocates none of them.  Two picks of ONE mesh at the same time share these
+ * buffers: they are the caller's to serialise.
+ *
+ * dtp_mesh_path_plan (host only): the stamps of a pointer path, brush.py:158-198 in double from the fp32 inputs, every result rounded
+ * to fp32 once.  state = {has_prev, prev[3]} travels in and out, so a path can arrive in several calls; {0} starts one.  Per hit, in
+ * order: a miss (face < 0) is skipped and leaves the state alone; the first hit sets prev = pos and gives no stamp; a later hit with
+ * dist = |pos - prev| < stamp_distance changes nothing; otherwise num = (int)(dist / stamp_distance), step = dist / num,
+ * dir = (pos - prev) / dist, and stamp k = 0 .. num - 1 sits at c_{k+1} = step dir + c_k with c_0 = prev (the chain stays in double;
+ * the stamps lie on the chord, as in the reference), carries THIS hit's normal and prev_position = c_k; then prev = pos.  The arrays
+ * pos, normal, prev hold 3 floats per stamp and `cap` stamps; *count = the stamps planned.  DTP_ERR_ARG for a NULL pointer, n < 0,
+ * cap < 0, a stamp_distance that is <= 0 or not finite, a chord of more than 2^20 stamps, and for count > cap: then *count holds the
+ * capacity needed, nothing usable is written and the state is unchanged. */
+typedef struct { float origin[3], dir[3]; } dtp_ray;
+typedef struct { int face; float w[3], pos[3], normal[3], uv[2], t; } dtp_mesh_hit;
+typedef struct { int has_prev; float prev[3]; } dtp_path_state;
+int dtp_mesh_pick(dtp_mesh* mesh, const dtp_ray* rays, int n, dtp_mesh_hit* out_host, dtp_stream s);
+int dtp_mesh_ray_frame(const float origin[3], const float dir[3], float out[12]);
+int dtp_mesh_path_plan(const dtp_mesh_hit* hits, int n, float stamp_distance, dtp_path_state* state, float* pos, float* normal, float* prev,
+                       int cap, int* count);
+
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
  * (DDIMScheduler.set_timesteps/configure, utilities.py:408-439).  Any pointer may be NULL. */
@@ -665,6 +722,10 @@ int dtp_op_mesh_render(dtp_mesh* mesh, const float cam[12], float fov, int flip_
                        int over_y, int over_x, float* canvas, int* face_idx, dtp_stream s);
 int dtp_op_mesh_backproject(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R, uint8_t* texture, int H, int W,
                             dtp_stream s);
+/* dtp_mesh_pick with the records left on the device (the contract: see "picking on a mesh"): rays host dtp_ray[n], out device
+ * dtp_mesh_hit[n] (52 bytes each).  The same checks; it enqueues on `s` and waits for `s`, because the frames travel through the mesh's
+ * pinned buffer. */
+int dtp_op_mesh_pick(dtp_mesh* mesh, const dtp_ray* rays, int n, dtp_mesh_hit* out, dtp_stream s);
 #ifdef __cplusplus
 }
 #endif
