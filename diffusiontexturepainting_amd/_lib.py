@@ -199,6 +199,17 @@ SYMBOLS = {
     "dtp_mesh_ray_frame": (_i, [C.POINTER(_f * 3), C.POINTER(_f * 3), C.POINTER(_f * 12)]),
     "dtp_mesh_path_plan": (_i, [_vp, _i, _f, C.POINTER(PathState), _vp, _vp, _vp, _i, C.POINTER(_i)]),
     "dtp_op_mesh_pick": (_i, [_vp, C.POINTER(Ray), _i, _vp, _vp]),
+    "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "dtp_journal_destroy": (_i, [_vp]),
+    "dtp_journal_begin": (_i, [_vp, _vp]),
+    "dtp_journal_end": (_i, [_vp, _vp]),
+    "dtp_journal_touch": (_i, [_vp, C.POINTER(_i), _i, _vp]),
+    "dtp_journal_undo": (_i, [_vp, _vp]),
+    "dtp_journal_redo": (_i, [_vp, _vp]),
+    "dtp_journal_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_uint64)]),
+    "dtp_journal_record_info": (_i, [_vp, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_i)]),
+    "dtp_op_journal_tiles": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
+    "dtp_journal_window_tiles": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
 }
 
 

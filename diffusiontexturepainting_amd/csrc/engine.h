@@ -363,6 +363,7 @@ struct Ctx {
   int last_stroke_stamps = -1, last_stroke_groups = 0, last_stroke_evals = 0;  // of the last dtp_stroke / dtp_mesh_stroke (-1: none yet)
   int* mesh_face_idx = nullptr;            // dtp_mesh_stroke: i32 [R][R], the face that won each pixel of the current stamp's render (-1: none)
   unsigned char* mesh_disc = nullptr;      // dtp_mesh_stroke: the Erase stamp's default mask, u8 [R][R] (built at its first use)
+  struct Journal* journal_open = nullptr;  // the journal with an open record on this handle (dtp_journal_begin .. dtp_journal_end), or null
   bool use_graph = true;
   bool exec_imgenc_ready = false;
   bool profile = false;
@@ -395,6 +396,14 @@ int ctx_pool_get(Ctx* c, size_t bytes, void** out);
 void ctx_pool_put(Ctx* c, void* p);
 int ctx_persistent(Ctx* c, size_t bytes, void** out, bool zero);
 void mesh_drop_ctx(Ctx* c);  // mesh.hip: frees the meshes created on this handle (dtp_destroy)
+// ---- journal.hip: the undo / redo journal of a texture.  The stroke calls ask for the journal whose open record guards
+// (texture, H, W) on this handle -- null: none, and then they enqueue nothing more -- and save the tiles they are about to write.
+void journal_drop_ctx(Ctx* c);  // frees the journals created on this handle (dtp_destroy)
+struct Journal* journal_armed(Ctx* c, const void* texture, int H, int W);
+// the tiles that meet the k windows of a 2D stroke group (clipped, or the wrapped pieces), each tile once per record
+int journal_save_windows(struct Journal* j, int R, const int* xs, const int* ys, int k, int wrap, hipStream_t s);
+// the tiles that meet the device-side texel box bb = {x0, y0, x1, y1} grown by `grow` and clipped (an empty box: none)
+int journal_save_box(struct Journal* j, const int* bb, int grow, hipStream_t s);
 const Staged* ctx_find(Ctx* c, const std::string& name);
 int ctx_fetch_host(Ctx* c, const std::string& name, std::vector<float>& out);
 int ctx_upload_f32(Ctx* c, const std::vector<float>& v, float** out);

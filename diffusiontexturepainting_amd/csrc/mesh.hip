@@ -726,11 +726,13 @@ int enqueue_render(Mesh* m, const float cam[12], float fov, int flip, const unsi
   return launch_ok();
 }
 
-// valid -> backproject of the window rendered last on this mesh; dec null: erase
+// valid (-> journal) -> backproject of the window rendered last on this mesh; dec null: erase.  journal (or null): the one whose open record
+// guards this texture; the tiles of the valid faces' texel box grown by `grow` (the bleed that follows) are saved before they are written.
 int enqueue_backproject(Mesh* m, const float* dec, int finished, const unsigned char* mask, const int* face_idx, int R, unsigned char* texture, int H, int W,
-                        hipStream_t s) {
+                        hipStream_t s, Journal* journal = nullptr, int grow = 0) {
   hipLaunchKernelGGL(mesh_valid_kernel, dim3(std::min((m->F + 255) / 256, 1024)), dim3(256), 0, s, m->rec, m->owned, m->win, m->uvs, m->F, H,
                      W, m->val, m->state);
+  if (journal) RC(journal_save_box(journal, m->state->bb, grow, s));
   hipLaunchKernelGGL(mesh_backproject_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->rec, m->val, m->state, m->F, m->uvs, dec,
                      finished, mask, face_idx, R, (unsigned int*)texture, H, W);
   return launch_ok();
@@ -860,18 +862,19 @@ int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture,
   if (!paste_mask && any_stamp) RC(stroke_default_mask(c, o->margin, s, &square));
   if (!paste_mask && any_erase) RC(disc_mask(c, s, &disc));
   int* face_idx = c->mesh_face_idx;
+  Journal* journal = journal_armed(c, texture, H, W);
   for (int i = 0; i < n; ++i) {
     const dtp_mesh_stamp& t = stamps[i];
     MeshStep& q = steps[i];
     if (q.skip) continue;
     RC(enqueue_render(m, q.cam, t.fov, o->flip_normals != 0, texture, H, W, R, t.mode, o->over_y, o->over_x, c->canvas32, face_idx, s));
     if (t.mode == DTP_STROKE_ERASE) {
-      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s));
+      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s, journal, bleed));
       if (bleed) RC(enqueue_bleed(m, texture, H, W, bleed, nullptr, s));
       continue;
     }
     q.plan.paste = [=](const float* dec, int, int, hipStream_t q_s) {
-      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s));
+      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s, journal, bleed));
       return bleed ? enqueue_bleed(m, texture, H, W, bleed, nullptr, q_s) : DTP_OK;
     };
     RC(stamp_enqueue(c, q.plan, s));

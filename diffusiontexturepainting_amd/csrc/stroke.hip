@@ -250,8 +250,10 @@ int dtp_stroke(dtp_ctx* ctx, uint8_t* texture, int H, int W, const dtp_stroke_st
   HIP_CHECK(hipSetDevice(c->device));
   const unsigned char* mask = paste_mask;
   if (!mask) RC(stroke_default_mask(c, o->margin, s, &mask));
+  Journal* journal = journal_armed(c, texture, H, W);  // an open record guards this texture: the group's tiles are saved before its paste
   for (StrokeGroup& g : groups) {
     g.paste.mask = mask;
+    if (journal) RC(journal_save_windows(journal, R, g.paste.wins.x, g.paste.wins.y, g.k, wrap, s));
     if (g.erase) { RC(dtp_launch_stroke_paste(nullptr, g.paste, R, g.k, s)); continue; }
     RC(dtp_launch_stroke_gather(texture, H, W, c->canvas32, R, g.k, g.paste.wins, wrap, o->over_y, o->over_x, s));
     RC(stamp_enqueue(c, g.plan, s));

@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from . import _lib, mesh as _mesh, weights as W
+from . import _lib, journal as _journal, mesh as _mesh, weights as W
 from ._lib import Settings, check, ptr
 from .model_base import ConditionalInpainterBase
 
@@ -537,6 +537,21 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         torch.cuda.current_stream(self._device).wait_stream(self.stream)
         texture.record_stream(self.stream)
         return texture
+
+    def journal(self, texture, capacity_tiles=None, depth=10):
+        """An undo / redo journal of `texture` (uint8 [H,W,4] on the model's device, contiguous; dtp_journal_create):
+        -> journal.Journal.  Between its begin() and end() -- or inside `with j.stroke():` -- paint_stroke, paint_mesh_stroke and
+        paint_mesh_path on this texture first save the 16 x 16-texel tiles they are about to write, on the device and in stream order;
+        undo() and redo() swap them back byte for byte.  What the Kit app does with a host copy of the whole texture per stroke
+        (ui/brush.py:52-77,131-137), without the copy, and with redo.  depth: the most strokes kept (the Kit app's 10).
+        capacity_tiles: the slots of the ring, 1 KiB each; a stroke that saves more tiles than that, or whose slots later strokes have
+        overwritten, can no longer be undone (undo() raises, painting is never held up).  Default: 4 x the texture's tile count, i.e.
+        room for four whole-texture copies.  Memory, all allocated here: capacity_tiles KiB of slots + 4 bytes per slot + 4 bytes per
+        tile; for a 2048^2 texture at the default 64 MiB + 256 KiB + 64 KiB (the texture itself is 16 MiB; the Kit app's ten host
+        copies are 160 MiB before encoding).  One record open per model at a time."""
+        if capacity_tiles is None:
+            capacity_tiles = 4 * _journal.tile_count(texture.shape[0], texture.shape[1])
+        return _journal.Journal(self, texture, capacity_tiles, depth)
 
     def stroke_info(self):
         """Of the last paint_stroke: its stamps, its groups and the UNet evaluations of all groups (dtp_last_stroke_info)."""

@@ -634,3 +634,11 @@ def mesh_bleed_offsets(k):
     buf = (C.c_byte * (2 * n.value))()
     check(lib.dtp_mesh_bleed_offsets(int(k), C.byref(n), buf), "mesh_bleed_offsets")
     return torch.tensor(list(buf), dtype=torch.int8).reshape(n.value, 2)
+
+
+def journal_window_tiles(H, W, R, x, y, wrap=False):
+    """dtp_journal_window_tiles (host only, needs no GPU): the ascending indices of the 16 x 16-texel tiles that an open journal record
+    saves for ONE 2D stroke window at (x, y) of an H x W texture: every tile that meets the R x R window clipped to the texture, or with
+    wrap a wrapped piece of it.  -> list of int, tile t = (row / 16) * ceil(W / 16) + col / 16."""
+    from . import journal
+    return journal.window_tiles(H, W, R, x, y, wrap=wrap)

@@ -24,7 +24,8 @@ extern "C" {
  * dtp_refit_lora, dtp_last_refit_info, dtp_op_lora_refit) and the strokes (dtp_stroke, dtp_stroke_plan, dtp_last_stroke_info,
  * dtp_op_stroke_gather, dtp_op_stroke_paste) and the mesh strokes (dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_camera, dtp_mesh_stroke,
  * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
- * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
+ * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) and the undo / redo journal
+ * (dtp_journal_*, dtp_op_journal_tiles) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
  * caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -406,6 +407,74 @@ int dtp_mesh_pick(dtp_mesh* mesh, const dtp_ray* rays, int n, dtp_mesh_hit* out_
 int dtp_mesh_ray_frame(const float origin[3], const float dir[3], float out[12]);
 int dtp_mesh_path_plan(const dtp_mesh_hit* hits, int n, float stamp_distance, dtp_path_state* state, float* pos, float* normal, float* prev,
                        int cap, int* count);
+
+/* ---------------------------------------------------------------- undo / redo journal of a texture
+ * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
+ * the last 10 copies and uploads one on Ctrl+Z (kit_app/.../python/ui/brush.py:52-77,131-137; redo is a TODO there).  A journal keeps, on
+ * the device, the old bytes of the 16 x 16-texel tiles a stroke is about to write, and swaps them back: undo and redo, exact bytes.
+ *
+ * Tiles.  Tile t = (i / 16) * ceil(W / 16) + (j / 16) holds the texels of rows 16 (i / 16) .. + 15 and columns 16 (j / 16) .. + 15 that
+ * lie inside the texture; a slot is 1 KiB = 256 RGBA texels.  An edge tile of an H or W that is no multiple of 16 saves and restores
+ * only its texels inside the texture.
+ *
+ * dtp_journal_create: texture is the device pointer the journal guards, u8 [H][W][4], 4-byte aligned, 1 <= H, W <= 32768; capacity_tiles
+ * >= 1 slots; depth in 1..64 the most records kept (the reference's is 10).  It allocates all the journal will ever need -- the slots,
+ * one i32 per tile, one i32 per slot, the counters (capacity_tiles KiB + 4 bytes per tile and per slot) -- and belongs to its handle:
+ * dtp_destroy frees the journals still alive; dtp_journal_destroy(NULL) is a no-op.  A pointer that is not a live journal is
+ * DTP_ERR_ARG in every call here: refused, not followed.
+ *
+ * Records.  dtp_journal_begin opens a record and dtp_journal_end closes it; a stroke may arrive in several calls in between.  While a
+ * record is open, every dtp_stroke, dtp_mesh_stroke and dtp_mesh_stroke_bleed call on that handle whose texture, H and W are the
+ * journal's saves the tiles it may write before it writes them, on the stroke's stream, which must be the stream of begin:
+ *   2D stroke, per group   every tile that meets a window of the group clipped to the texture, or with `wrap` a wrapped piece of it (the
+ *                          paste mask is not consulted);
+ *   mesh stamp             every tile that meets the texel bounding box of the stamp's valid faces, as the device has it after the valid
+ *                          pass, grown by `bleed` and clipped; saved between the valid pass and the backprojection; an empty box saves
+ *                          nothing; the host reads nothing.
+ * A tile is saved once per record, however many stamps, groups, windows or wrapped pieces meet it.  A call on another texture, H or W is
+ * not journalled and is no error.  With no record open the three calls enqueue exactly the launches they always did.  A journalled
+ * stroke writes the bytes an unjournalled one writes.  dtp_journal_touch saves the tiles of n rectangles, host int[n][4] inclusive
+ * {x0, y0, x1, y1} clipped to the texture, into the open record: for a client that writes the texture itself (dtp_mesh_bleed, a fill,
+ * an upload).  begin, end, touch and the saves of the stroke calls never wait and never allocate.
+ *
+ * Storage.  The slots form a ring: a 64-bit device counter `head` only grows, and the k-th slot ever taken is slot k mod
+ * capacity_tiles.  begin stamps start = head into the record and end stamps end = head, on the device.  A record is restorable iff
+ * head - start <= capacity_tiles: nothing has landed on its first slot.  So a record larger than the capacity is not restorable, and a
+ * small ring forgets its oldest records first; painting is never blocked or refused because the journal is full.
+ *
+ * Undo / redo.  The records form a list, oldest first, with a cursor: records [0, cursor) are applied, [cursor, records) undone.
+ * dtp_journal_undo takes the newest applied record and SWAPS each of its slots with its tile: the texture's texels are then what they
+ * were at that record's begin, and the slots hold the painted state.  dtp_journal_redo swaps the oldest undone record back: the texture
+ * is then, byte for byte, what it was at that record's end.  begin drops all undone records (their redo is gone); head is NOT rewound, so
+ * their slots stay taken until the ring comes round to them.  When `depth` records exist, begin drops the oldest.  undo, redo,
+ * dtp_journal_info with a non-NULL head, dtp_journal_record_info and dtp_op_journal_tiles wait for the stream (info: the stream the
+ * journal was used on last) and read a few words back; they run at a user's Ctrl+Z, not inside a stroke.
+ *
+ * Refusals, all before anything is enqueued; a refused call leaves the texture and the journal untouched.  DTP_ERR_ARG: a NULL pointer;
+ * H or W outside 1..32768; a misaligned texture; capacity_tiles < 1; depth outside 1..64; a journal that is not alive; in touch n < 1 or
+ * a rectangle with x0 > x1 or y0 > y1, naming it.  DTP_ERR_STATE: begin with a record open on this journal or on another journal of the
+ * handle; end or touch with none open; undo or redo with a record open, with nothing to undo / redo ("nothing to undo", "nothing to
+ * redo"), or of a record that is no longer restorable: the message says it was overwritten and gives the record's tiles and the
+ * capacity, and that record and every older one are dropped.
+ *
+ * dtp_journal_info: the number of records, the cursor, whether a record is open, and head; any pointer may be NULL.
+ * dtp_journal_record_info: start, end (of an open record: head) and restorable of record 0 <= record < records.
+ * dtp_op_journal_tiles: the tile indices a restorable record saved, in slot order, into host tiles[max]; *n = their number (more than
+ * max: DTP_ERR_ARG, nothing written).  dtp_journal_window_tiles (host only, no device): the ascending tile list of ONE 2D stroke window
+ * at (x, y) by the rule above, 1 <= R <= min(H, W); *n = its length (more than max: DTP_ERR_ARG, nothing written; tiles may be NULL
+ * with max = 0). */
+typedef struct dtp_journal dtp_journal;
+int dtp_journal_create(dtp_ctx* ctx, uint8_t* texture, int H, int W, int capacity_tiles, int depth, dtp_journal** out);
+int dtp_journal_destroy(dtp_journal* j);
+int dtp_journal_begin(dtp_journal* j, dtp_stream s);
+int dtp_journal_end(dtp_journal* j, dtp_stream s);
+int dtp_journal_touch(dtp_journal* j, const int* rects, int n, dtp_stream s);
+int dtp_journal_undo(dtp_journal* j, dtp_stream s);
+int dtp_journal_redo(dtp_journal* j, dtp_stream s);
+int dtp_journal_info(dtp_journal* j, int* records, int* cursor, int* open, uint64_t* head);
+int dtp_journal_record_info(dtp_journal* j, int record, uint64_t* start, uint64_t* end, int* restorable);
+int dtp_op_journal_tiles(dtp_journal* j, int record, int* tiles_host, int max, int* n);
+int dtp_journal_window_tiles(int H, int W, int R, int wrap, int x, int y, int* tiles, int max, int* n);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
