@@ -68,6 +68,18 @@ class PathState(C.Structure):  # dtp_path_state
 PICK_MAX_RAYS = 4096
 
 
+class ViewCam(C.Structure):  # dtp_view_cam
+    _fields_ = [("m", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("near", C.c_float)]
+
+
+class ViewOpts(C.Structure):  # dtp_view_opts
+    _fields_ = [("cull", C.c_int), ("flip_normals", C.c_int), ("shade", C.c_int), ("ambient", C.c_float), ("unpainted", C.c_uint8 * 3),
+                ("background", C.c_uint8 * 4)]
+
+
+VIEW_MAX = 4096  # the largest side of a view's frame
+
+
 class ProfRow(C.Structure):
     _fields_ = [("kind", C.c_int), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -199,6 +211,10 @@ SYMBOLS = {
     "dtp_mesh_ray_frame": (_i, [C.POINTER(_f * 3), C.POINTER(_f * 3), C.POINTER(_f * 12)]),
     "dtp_mesh_path_plan": (_i, [_vp, _i, _f, C.POINTER(PathState), _vp, _vp, _vp, _i, C.POINTER(_i)]),
     "dtp_op_mesh_pick": (_i, [_vp, C.POINTER(Ray), _i, _vp, _vp]),
+    "dtp_view_camera": (_i, [C.POINTER(_f * 3), C.POINTER(_f * 3), C.POINTER(_f * 3), _f, _i, _i, _f, C.POINTER(ViewCam)]),
+    "dtp_view_rays": (_i, [C.POINTER(ViewCam), _i, _i, _vp, _i, _vp]),
+    "dtp_mesh_view": (_i, [_vp, _vp, _i, _i, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _vp]),
+    "dtp_op_mesh_view": (_i, [_vp, _vp, _i, _i, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _i, _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

@@ -1,0 +1,311 @@
+// A view of a textured mesh (dtp_mesh_view): the whole mesh through a perspective camera into an H x W RGBA frame on the
+// device, so that a client without Omniverse sees what it painted (in the reference the viewport is Omniverse RTX reading the texture
+// through update_material_texture, kit_app/.../python/manager.py:349-354).  Written from the contract of include/dtp.h: the projection in
+// fp32 one rounded operation at a time, the strokes' integer coverage (mesh_dev.h), the inverse depth interpolated on the screen, a winner
+// per pixel that does not depend on the order in which faces are visited.  The stamp's own render streams its whole window list through
+// every tile, which suits the 8 600 faces of a stamp window; a frame of 10^5..10^6 faces is binned instead: faces are counted into bins of
+// 64 x 64 pixels, the counts are scanned, the faces written into their bins' segments, and a tile of 16 x 16 pixels streams its bin's
+// segment alone -- plus the short list of faces too large to bin.  No capacity to choose, no overflow, no read-back.  The kernels read
+// the mesh's vertices, faces and UVs and write buffers of their own: nothing a stroke or a pick in flight uses.  Plain HIP: vector loads,
+// stores and atomics only.
+#pragma clang fp contract(off)
+#include <math.h>
+#include <stddef.h>
+#include <string.h>
+
+#include "engine.h"
+#include "mesh_dev.h"
+#include "view_host.h"
+
+namespace {
+
+enum { VF_SMALL = 1, VF_LARGE = 2 };  // drawn, and binned / on the list every tile streams; 0: not drawn
+
+// what a view's projection leaves per face, 64 bytes: screen position snapped to 1/256 pixel, 1 / depth per vertex, the unit normal's z,
+// the pixel ranges x0 | x1 << 16, y0 | y1 << 16
+struct ViewRec { int X[3], Y[3]; float iw[3], nzu; int flags, px, py, pad[3]; };
+static_assert(sizeof(ViewRec) == 64, "one record per 64-byte line");
+// the counters of a frame: count and n_large are zeroed on the stream before every projection
+struct ViewState { int count[VIEW_MAX_BINS], n_large, offset[VIEW_MAX_BINS + 1], cursor[VIEW_MAX_BINS]; };
+struct ViewBufs {
+  ViewRec* rec = nullptr;     // [F]
+  int* items = nullptr;       // [4 F]: the bins' segments of face indices (a small face has at most 4 entries)
+  int* large = nullptr;       // [F]
+  ViewState* st = nullptr;
+};
+struct ViewShade { int shade; float ambient, unpainted[3]; unsigned int background; };  // travels as a kernel argument
+
+// counter[key] += 1 for every lane of the wave whose key is >= 0, with ONE atomic per distinct key: the lanes that share a key elect a
+// leader, which adds their number; -> the lane's slot, the counter's value before its own add.  Neighbouring faces of a mesh mostly share
+// a bin, and a frame seen from afar has few bins: one atomic per face on the same few words serialises the whole launch.  Every lane that
+// has not left the kernel calls it, from converged code.
+__device__ __forceinline__ int wave_add(int* counter, int key) {
+  const int lane = threadIdx.x & 63;
+  int slot = 0;
+  unsigned long long todo = __ballot(key >= 0);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int k = __shfl(key, leader, 64);
+    const unsigned long long same = __ballot(key == k) & todo;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&counter[k], __popcll(same));
+    base = __shfl(base, leader, 64);
+    if ((same >> lane) & 1ull) slot = base + __popcll(same & ((1ull << lane) - 1ull));
+    todo &= ~same;
+  }
+  return slot;
+}
+// entry e = 0 .. 3 of a small face: the bin (by0 + e / 2, bx0 + e % 2) if the face meets it, else -1
+__device__ __forceinline__ int bin_key(int e, int bx0, int bx1, int by0, int by1, int nbx) {
+  const int bx = bx0 + (e & 1), by = by0 + (e >> 1);
+  return (bx <= bx1 && by <= by1) ? by * nbx + bx : -1;
+}
+
+// One thread per face: camera space, the unit normal's z, the perspective division, the snapped screen position; a face that is drawn
+// (in front of the near plane, not culled, with an area and a pixel centre in its box) is counted into its bins or appended to `large`.
+__global__ __launch_bounds__(256) void view_project_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int F, dtp_view_cam cam,
+                                                           int H, int W, int cull, int flip, int binned, int nbx, ViewRec* __restrict__ rec,
+                                                           int* __restrict__ large, ViewState* st) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  float c[3][3];
+  bool draw = f < F;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float* v = verts + (size_t)3 * (draw ? faces[(size_t)3 * f + k] : 0);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      c[k][r] = ((cam.m[4 * r] * v[0] + cam.m[4 * r + 1] * v[1]) + cam.m[4 * r + 2] * v[2]) + cam.m[4 * r + 3];
+      draw = draw && isfinite(c[k][r]);
+    }
+    draw = draw && c[k][2] <= -cam.near;
+  }
+  ViewRec r;
+  memset(&r, 0, sizeof r);
+  if (draw) {
+    const float e1x = c[1][0] - c[0][0], e1y = c[1][1] - c[0][1], e1z = c[1][2] - c[0][2];
+    const float e2x = c[2][0] - c[0][0], e2y = c[2][1] - c[0][1], e2z = c[2][2] - c[0][2];
+    const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    r.nzu = nz / sqrtf((nx * nx + ny * ny) + nz * nz);  // correctly rounded (a zero area: 0 / 0)
+    const float wx = 128.0f * (float)W, wy = 128.0f * (float)H;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      r.iw[k] = 1.0f / (0.0f - c[k][2]);
+      r.X[k] = snap((((c[k][0] * cam.fx) * r.iw[k]) + 1.0f) * wx);
+      r.Y[k] = snap((1.0f - ((c[k][1] * cam.fy) * r.iw[k])) * wy);
+    }
+    const long long A = orient(r.X[0], r.Y[0], r.X[1], r.Y[1], r.X[2], r.Y[2]);
+    const bool front = (A < 0) != (flip != 0);
+    int x0, x1, y0, y1;
+    centre_range(min3(r.X[0], r.X[1], r.X[2]), max3(r.X[0], r.X[1], r.X[2]), W, x0, x1);
+    centre_range(min3(r.Y[0], r.Y[1], r.Y[2]), max3(r.Y[0], r.Y[1], r.Y[2]), H, y0, y1);
+    draw = A != 0 && (front || !cull) && x0 <= x1 && y0 <= y1;
+    if (draw) { r.px = x0 | (x1 << 16); r.py = y0 | (y1 << 16); }
+  }
+  int bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
+  if (draw) r.flags = (view_bins(r.px, r.py, bx0, bx1, by0, by1) && binned) ? VF_SMALL : VF_LARGE;
+  if (f < F) rec[f] = r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) wave_add(st->count, r.flags == VF_SMALL ? bin_key(e, bx0, bx1, by0, by1, nbx) : -1);
+  const int at = wave_add(&st->n_large, r.flags == VF_LARGE ? 0 : -1);
+  if (r.flags == VF_LARGE && at < F) large[at] = f;  // (always, unless two views of one mesh race)
+}
+
+// One workgroup: the exclusive prefix of the bins' counts -> where each bin's segment starts, and its cursor for the fill.
+__global__ __launch_bounds__(256) void view_scan_kernel(ViewState* st) {
+  constexpr int PER = VIEW_MAX_BINS / 256;
+  __shared__ int s_sum[256];
+  const int t = threadIdx.x;
+  int local[PER], sum = 0;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) { local[i] = st->count[PER * t + i]; sum += local[i]; }
+  s_sum[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int v = t >= d ? s_sum[t - d] : 0;
+    __syncthreads();
+    s_sum[t] += v;
+    __syncthreads();
+  }
+  int run = s_sum[t] - sum;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) { st->offset[PER * t + i] = run; st->cursor[PER * t + i] = run; run += local[i]; }
+  if (t == 255) st->offset[VIEW_MAX_BINS] = run;
+}
+
+// One thread per face: a small face writes its index into the segment of every bin it was counted in (in any order).
+__global__ __launch_bounds__(256) void view_fill_kernel(const ViewRec* __restrict__ rec, int F, int nbx, int* __restrict__ items, ViewState* st) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  const bool small = f < F && rec[f].flags == VF_SMALL;
+  if (__ballot(small) == 0ull) return;  // (uniform in the wave)
+  int bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
+  if (small) view_bins(rec[f].px, rec[f].py, bx0, bx1, by0, by1);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int key = small ? bin_key(e, bx0, bx1, by0, by1, nbx) : -1;
+    const int slot = wave_add(st->cursor, key);
+    if (key >= 0 && slot < 4 * F) items[slot] = f;  // (always, unless two views of one mesh race)
+  }
+}
+
+// One workgroup per 16 x 16 pixel tile, one thread per pixel.  The tile's bin segment, then the large list, stream through LDS CHUNK at a
+// time; a face whose pixel range misses the tile is dropped on the way in.  Winner: the largest (inverse depth d, -face index) among
+// the faces that cover the centre.  Then the perspective-correct UV, the bilinear sample, the shade and the stores.
+__global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restrict__ rec, const int* __restrict__ items, const int* __restrict__ large,
+                                                          const ViewState* st, int F, int nbx, const float* __restrict__ uvs,
+                                                          const unsigned int* __restrict__ tex, int TH, int TW, int H, int W, ViewShade sh,
+                                                          unsigned int* __restrict__ image, int* __restrict__ face_idx, float* __restrict__ depth) {
+  __shared__ int s_n, s_face[CHUNK], s_X[CHUNK][3], s_Y[CHUNK][3];
+  __shared__ float s_iw[CHUNK][3];
+  const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
+  const int col = col0 + (t & 15), row = row0 + (t >> 4);
+  const bool live = col < W && row < H;
+  const int px = 256 * col + 128, py = 256 * row + 128;
+  const int bin = (row0 >> VIEW_BIN_SHIFT) * nbx + (col0 >> VIEW_BIN_SHIFT);
+  const int cap = 4 * F;
+  const int seg0 = min(max(st->offset[bin], 0), cap), n_seg = min(max(st->offset[bin + 1], seg0), cap) - seg0;
+  const int total = n_seg + min(max(st->n_large, 0), F);
+  int best = -1;
+  float best_d = 0.f, bq[3] = {0.f, 0.f, 0.f};
+  for (int base = 0; base < total; base += CHUNK) {
+    if (t == 0) s_n = 0;
+    __syncthreads();
+    if (base + t < total) {
+      const int i = base + t, f = i < n_seg ? items[seg0 + i] : large[i - n_seg];
+      if ((unsigned int)f < (unsigned int)F) {
+        const ViewRec& r = rec[f];
+        if (ranges_meet(r.px, col0, col0 + 15) && ranges_meet(r.py, row0, row0 + 15)) {
+          const int slot = atomicAdd(&s_n, 1);
+          s_face[slot] = f;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { s_X[slot][k] = r.X[k]; s_Y[slot][k] = r.Y[k]; s_iw[slot][k] = r.iw[k]; }
+        }
+      }
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (live)
+      for (int i = 0; i < n; ++i) {
+        float w[3];
+        if (!cover(s_X[i], s_Y[i], px, py, w)) continue;
+        const float q0 = w[0] * s_iw[i][0], q1 = w[1] * s_iw[i][1], q2 = w[2] * s_iw[i][2];
+        const float d = (q0 + q1) + q2;
+        const int f = s_face[i];
+        if (best < 0 || d > best_d || (d == best_d && f < best)) { best = f; best_d = d; bq[0] = q0; bq[1] = q1; bq[2] = q2; }
+      }
+    __syncthreads();
+  }
+  if (!live) return;
+  const size_t pix = (size_t)row * W + col;
+  unsigned int out = sh.background;
+  float dist = 0.f;
+  if (best >= 0) {
+    const float* uv = uvs + (size_t)6 * best;
+    const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
+    const Taps tp = taps(u * (float)TW - 0.5f, (1.0f - v) * (float)TH - 0.5f, TH, TW);
+    const unsigned int t00 = tex[(size_t)tp.y0 * TW + tp.x0], t01 = tex[(size_t)tp.y0 * TW + tp.x1];
+    const unsigned int t10 = tex[(size_t)tp.y1 * TW + tp.x0], t11 = tex[(size_t)tp.y1 * TW + tp.x1];
+    float tc[4];
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+      const int s8 = 8 * ch;
+      tc[ch] = blend(tp, (float)((t00 >> s8) & 0xffu) / 255.0f, (float)((t01 >> s8) & 0xffu) / 255.0f,
+                     (float)((t10 >> s8) & 0xffu) / 255.0f, (float)((t11 >> s8) & 0xffu) / 255.0f);
+    }
+    const float s = sh.shade ? sh.ambient + (1.0f - sh.ambient) * fabsf(rec[best].nzu) : 1.0f;
+    const float rest = 1.0f - tc[3];
+    out = 0xff000000u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float cc = (tc[ch] * tc[3] + sh.unpainted[ch] * rest) * s;
+      out |= (unsigned int)(unsigned char)(fminf(cc, 1.0f) * 255.0f + 0.5f) << (8 * ch);
+    }
+    dist = 1.0f / best_d;
+  }
+  image[pix] = out;
+  if (face_idx) face_idx[pix] = best;
+  if (depth) depth[pix] = dist;
+}
+
+int view_reserve(const MeshGeom& g) {
+  if (*g.view) return DTP_OK;
+  ViewBufs* b = new ViewBufs();
+  const size_t nf = (size_t)g.F;
+  hipError_t e = hipMalloc((void**)&b->rec, nf * sizeof(ViewRec));
+  if (e == hipSuccess) e = hipMalloc((void**)&b->items, nf * 4 * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&b->large, nf * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&b->st, sizeof(ViewState));
+  if (e != hipSuccess) {
+    dtp_set_error("mesh view: %s (buffers for %d faces)", hipGetErrorString(e), g.F);
+    view_free(b);
+    return DTP_ERR_HIP;
+  }
+  *g.view = b;
+  return DTP_OK;
+}
+
+// every check, then zero the counters -> project -> scan -> fill -> raster on s; nothing waits
+int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* o,
+             uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s) {
+  if (!mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
+  if (const char* why = view_check(texture, TH, TW, cam, H, W, o, image, face_idx, depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
+  MeshGeom g;
+  if (!mesh_geom(mesh, &g)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
+  HIP_CHECK(hipSetDevice(g.ctx->device));
+  RC(view_reserve(g));
+  const ViewBufs* b = (const ViewBufs*)*g.view;
+  ViewShade sh;
+  sh.shade = o->shade; sh.ambient = o->ambient;
+  for (int ch = 0; ch < 3; ++ch) sh.unpainted[ch] = (float)o->unpainted[ch] / 255.0f;
+  sh.background = (unsigned int)o->background[0] | ((unsigned int)o->background[1] << 8) | ((unsigned int)o->background[2] << 16) |
+                  ((unsigned int)o->background[3] << 24);
+  const int nbx = view_bins_across(W), blocks = (g.F + 255) / 256;
+  HIP_CHECK(hipMemsetAsync(b->st, 0, offsetof(ViewState, offset), s));
+  hipLaunchKernelGGL(view_project_kernel, dim3(blocks), dim3(256), 0, s, g.verts, g.faces, g.F, *cam, H, W, o->cull, o->flip_normals, binned ? 1 : 0, nbx,
+                     b->rec, b->large, b->st);
+  hipLaunchKernelGGL(view_scan_kernel, dim3(1), dim3(256), 0, s, b->st);
+  hipLaunchKernelGGL(view_fill_kernel, dim3(blocks), dim3(256), 0, s, b->rec, g.F, nbx, b->items, b->st);
+  hipLaunchKernelGGL(view_raster_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs,
+                     (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth);
+  if (hipGetLastError() != hipSuccess) { dtp_set_error("%s: a kernel launch failed", who); return DTP_ERR_HIP; }
+  return DTP_OK;
+}
+
+}  // namespace
+
+void view_free(void* view) {
+  ViewBufs* b = (ViewBufs*)view;
+  if (!b) return;
+  (void)hipFree(b->rec); (void)hipFree(b->items); (void)hipFree(b->large); (void)hipFree(b->st);  // (waits for the work that still reads them)
+  delete b;
+}
+
+extern "C" {
+
+int dtp_view_camera(const float eye[3], const float at[3], const float up[3], float fov_y_degrees, int H, int W, float near, dtp_view_cam* out) {
+  if (!eye || !at || !up || !out) { dtp_set_error("dtp_view_camera: NULL argument"); return DTP_ERR_ARG; }
+  if (const char* why = view_camera(eye, at, up, fov_y_degrees, H, W, near, out)) { dtp_set_error("dtp_view_camera: %s", why); return DTP_ERR_ARG; }
+  return DTP_OK;
+}
+
+int dtp_view_rays(const dtp_view_cam* cam, int H, int W, const float* pixels_xy, int n, dtp_ray* out) {
+  if (!cam || !pixels_xy || !out) { dtp_set_error("dtp_view_rays: NULL argument"); return DTP_ERR_ARG; }
+  int bad = -1;
+  if (const char* why = view_rays(cam, H, W, pixels_xy, n, out, &bad)) {
+    if (bad >= 0) dtp_set_error("dtp_view_rays: pixel %d: %s", bad, why);
+    else dtp_set_error("dtp_view_rays: %s", why);
+    return DTP_ERR_ARG;
+  }
+  return DTP_OK;
+}
+
+int dtp_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
+                  uint8_t* image, int* face_idx, float* depth, dtp_stream s) {
+  return view_run("dtp_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, (hipStream_t)s);
+}
+
+int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
+                     uint8_t* image, int* face_idx, float* depth, int binned, dtp_stream s) {
+  return view_run("dtp_op_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s);
+}
+
+}  // extern "C"

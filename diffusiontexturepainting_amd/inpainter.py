@@ -174,6 +174,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.generator = torch.Generator(device=self._device).manual_seed(seed)
         self.stream = torch.cuda.Stream(device=self._device)
         self.pick_stream = torch.cuda.Stream(device=self._device)  # pick() alone runs here, beside whatever self.stream has queued
+        self._view_stream = None  # render_view() alone runs there: made at the first view (see view_stream)
         self.conditioning = None
         self.image = None
         self._slots = {}  # conditioning slot -> (image [1,3,R,R], (cond, uncond))
@@ -514,6 +515,67 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             return texture, state, 0
         self.paint_mesh_stroke(mesh, texture, positions, normals, prevs, float(radius if fov is None else fov), **stroke_kwargs)
         return texture, state, n
+
+    @property
+    def view_stream(self):
+        """The stream of render_view: not the pick's, not the stroke's.  Made at the first view, so that a model that never looks
+        creates the streams it always did, and with high priority: the runtime keeps the queues of a priority apart, so a short frame
+        never lands in the hardware queue in which a stroke -- or the caller's stream waiting for one -- is lined up."""
+        if self._view_stream is None:
+            self._view_stream = torch.cuda.Stream(device=self._device, priority=-1)
+        return self._view_stream
+
+    def render_view(self, mesh, texture, camera, size=None, cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128),
+                    background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False):
+        """A perspective view of the whole painted mesh (dtp_mesh_view; in the Kit app the viewport is Omniverse RTX):
+        `mesh` from load_mesh, `texture` uint8 [TH, TW, 4] on the model's device, `camera` from mesh.view_camera, size = (H, W) (default
+        the camera's; each side 1..4096).  -> the frame, uint8 [H, W, 4] on the device (RGB the texture under its alpha over `unpainted`,
+        shaded by ambient + (1 - ambient) |n_z| unless shade is off; alpha 255; `background` where no face is), and with want_face_idx /
+        want_depth also int32 [H, W] (-1: no face) and float32 [H, W] (the distance along the view direction; 0: no face), as a tuple in
+        that order.  cull: front faces only; flip_normals: a left-handed mesh.  A face with any vertex nearer than the camera's near
+        plane is dropped whole, not clipped; one sample per pixel, no mips: a preview that aliases under minification.  out: a frame to
+        write into.  The call only enqueues, on self.view_stream.  live=False: that stream first waits for everything queued on the
+        stroke's stream, so the frame shows all that was painted so far and is exact.  live=True: it waits for nothing and answers while
+        a queued stroke is still painting; each texel is then either old or new, and the frame may catch a stamp halfway.  The
+        caller's current stream waits for the frame (on the device; the host does not block).  One view of a mesh at a time."""
+        if not isinstance(mesh, _mesh.Mesh):
+            raise ValueError("mesh must come from load_mesh()")
+        if not isinstance(camera, _mesh.ViewCamera):
+            raise ValueError("camera must come from mesh.view_camera()")
+        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
+                and texture.device == self._device and texture.is_contiguous()):
+            raise ValueError(f"texture must be a contiguous uint8 [TH, TW, 4] tensor on {self._device}")
+        H, W = (int(v) for v in (camera.size if size is None else size))
+        if not (1 <= H <= _lib.VIEW_MAX and 1 <= W <= _lib.VIEW_MAX):
+            raise ValueError(f"size = ({H}, {W}): each side 1..{_lib.VIEW_MAX}")
+        if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == (H, W, 4) and out.device == self._device
+                  and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 [{H}, {W}, 4] tensor on {self._device}")
+        opts = _mesh.view_opts(cull, flip_normals, shade, ambient, unpainted, background)
+        cam = camera.struct()
+        cur = torch.cuda.current_stream(self._device)
+        given = out
+        with torch.cuda.stream(self.view_stream):  # the outputs belong to the view's stream: a live view waits for no other
+            if out is None:
+                out = torch.empty(H, W, 4, dtype=torch.uint8, device=self._device)
+            face_idx = torch.empty(H, W, dtype=torch.int32, device=self._device) if want_face_idx else None
+            depth = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_depth else None
+        if not live:
+            done = torch.cuda.Event()
+            done.record(self.stream)
+            self.view_stream.wait_event(done)
+            self.view_stream.wait_stream(cur)
+        check(self._lib.dtp_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(opts), ptr(out),
+                                      ptr(face_idx), ptr(depth), C.c_void_p(self.view_stream.cuda_stream)), "dtp_mesh_view")
+        cur.wait_stream(self.view_stream)
+        for t in (texture, given):
+            if t is not None:
+                t.record_stream(self.view_stream)
+        for t in (None if given is not None else out, face_idx, depth):
+            if t is not None:
+                t.record_stream(cur)
+        extra = tuple(t for t in (face_idx, depth) if t is not None)
+        return (out,) + extra if extra else out
 
     def bleed_texture(self, mesh, texture, bleed, rect=None):
         """The bleed pass of paint_mesh_stroke on its own (dtp_mesh_bleed), for a texture that was loaded from a file or painted without

@@ -3,7 +3,8 @@ the stamp array of a stroke.  The stroke itself is MI355ConditionalInpainter.pai
 are ops.mesh_render / ops.mesh_backproject.  The bleed pass that pads the UV charts is paint_mesh_stroke(bleed=k) and
 MI355ConditionalInpainter.bleed_texture; ops.mesh_coverage / ops.mesh_bleed_offsets show what it works from.  Picking:
 the host-only ray frame and the stamp spacing of a pointer path live here; the pick itself is MI355ConditionalInpainter.pick and the
-pointer-to-paint call paint_mesh_path."""
+pointer-to-paint call paint_mesh_path.  The view (DESIGN.md 3.24): the host-only perspective camera and the rays of its pixels live here;
+the frame itself is MI355ConditionalInpainter.render_view (ops.mesh_view at op level)."""
 import ctypes as C
 
 import torch
@@ -96,6 +97,53 @@ def plan_path(hits, stamp_distance, state=None):
     return out[0], out[1], out[2], dict(has_prev=bool(st.has_prev), prev=tuple(st.prev))
 
 
+class ViewCamera:
+    """A perspective camera of render_view (dtp_view_cam): m float32 [3, 4], rows (right, up, back) of the look-at, each followed by its
+    translation; fx, fy the focal lengths in NDC units; near the near plane's distance; size = (H, W) of the frame it was made for."""
+
+    def __init__(self, m, fx, fy, near, size):
+        self.m, self.fx, self.fy, self.near, self.size = m, float(fx), float(fy), float(near), (int(size[0]), int(size[1]))
+
+    def struct(self):
+        return _lib.ViewCam((C.c_float * 12)(*[float(v) for v in torch.as_tensor(self.m).reshape(-1).tolist()]), self.fx, self.fy, self.near)
+
+    def __repr__(self):
+        return f"ViewCamera(m={self.m.tolist()}, fx={self.fx}, fy={self.fy}, near={self.near}, size={self.size})"
+
+
+def view_camera(eye, at, up, fov_y=45.0, size=(720, 1280), near=0.01):
+    """The perspective camera of a view (dtp_view_camera: host only, needs no GPU): the look-at from `eye` at `at` with `up`, a vertical
+    field of view of fov_y degrees over a frame of size = (H, W) pixels; faces nearer than `near` along the view direction are not
+    drawn.  -> ViewCamera.  DtpError for anything non-finite, eye == at, an up that is zero or parallel to the view direction, fov_y
+    outside (0, 180), near <= 0, a side outside 1..4096."""
+    out = _lib.ViewCam()
+    check(_lib.load().dtp_view_camera(C.byref(_vec3(eye, "eye")), C.byref(_vec3(at, "at")), C.byref(_vec3(up, "up")), C.c_float(float(fov_y)),
+                                      int(size[0]), int(size[1]), C.c_float(float(near)), C.byref(out)), "dtp_view_camera")
+    return ViewCamera(torch.tensor(list(out.m), dtype=torch.float32).reshape(3, 4), out.fx, out.fy, out.near, size)
+
+
+def view_rays(camera, pixels, size=None):
+    """The rays of pixel positions of a view (dtp_view_rays: host only): pixels [n, 2] (or [2]) as (x, y), the centre of pixel (row i,
+    column j) being (j + 0.5, i + 0.5); size = (H, W), default the camera's.  -> (origins f32 [n, 3], directions f32 [n, 3]) on the
+    host, ready for model.pick and paint_mesh_path: the face a frame shows at a pixel is the face its ray hits."""
+    H, W = camera.size if size is None else size
+    xy = torch.as_tensor(pixels).detach().to("cpu", torch.float32).reshape(-1, 2).contiguous()
+    n = xy.shape[0]
+    out = torch.zeros(max(n, 1), 6, dtype=torch.float32)
+    cam = camera.struct()
+    src = xy if n else torch.zeros(1, 2, dtype=torch.float32)  # (an empty tensor has no address; n = 0 is the library's to refuse)
+    check(_lib.load().dtp_view_rays(C.byref(cam), int(H), int(W), _lib.ptr(src), n, _lib.ptr(out)), "dtp_view_rays")
+    return out[:n, :3].clone(), out[:n, 3:].clone()
+
+
+def view_opts(cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128), background=(0, 0, 0, 0)):
+    """The dtp_view_opts of a view."""
+    if len(unpainted) != 3 or len(background) != 4 or not all(0 <= int(v) <= 255 for v in tuple(unpainted) + tuple(background)):
+        raise ValueError(f"unpainted is 3 and background 4 bytes in 0..255, got {unpainted!r} and {background!r}")
+    return _lib.ViewOpts(int(bool(cull)), int(bool(flip_normals)), int(bool(shade)), float(ambient), (C.c_uint8 * 3)(*[int(v) for v in unpainted]),
+                         (C.c_uint8 * 4)(*[int(v) for v in background]))
+
+
 class Mesh:
     """A mesh on the device of a handle (dtp_mesh_create): vertices [V, 3] float, faces [F, 3] int, face_uvs [F, 3, 2] float (UVs in
     0..1, v up; kaolin's SurfaceMesh.face_uvs), copied from the host.  Freed by close(), by garbage collection, or with its handle."""
@@ -121,6 +169,8 @@ class Mesh:
 
     ray_frame = staticmethod(ray_frame)  # host only: see the functions of this module
     plan_path = staticmethod(plan_path)
+    view_camera = staticmethod(view_camera)
+    view_rays = staticmethod(view_rays)
 
     def close(self):
         if getattr(self, "_h", None):

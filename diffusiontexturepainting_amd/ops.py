@@ -625,6 +625,24 @@ def mesh_pick(mesh, origins, directions):
     return _mesh.hits_dict(rec)
 
 
+def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True, want_depth=True, **opts):
+    """dtp_op_mesh_view: the frame of MI355ConditionalInpainter.render_view on the current stream -> (image u8 [H,W,4], face_idx i32
+    [H,W] or None, depth f32 [H,W] or None).  binned=False puts every drawn face on the list that every tile streams (the arm a
+    measurement compares the bins with); the frame is the same bytes.  opts: cull, flip_normals, shade, ambient, unpainted, background."""
+    from . import mesh as _mesh
+    lib = _lib.load()
+    H, W = (int(v) for v in (camera.size if size is None else size))
+    if not (1 <= H <= _lib.VIEW_MAX and 1 <= W <= _lib.VIEW_MAX):
+        raise ValueError(f"size = ({H}, {W}): each side 1..{_lib.VIEW_MAX}")
+    o, cam = _mesh.view_opts(**opts), camera.struct()
+    image = torch.empty(H, W, 4, dtype=torch.uint8, device=texture.device)
+    face_idx = torch.empty(H, W, dtype=torch.int32, device=texture.device) if want_face_idx else None
+    depth = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_depth else None
+    check(lib.dtp_op_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(o), ptr(image),
+                               ptr(face_idx), ptr(depth), int(bool(binned)), _stream()), "mesh_view")
+    return image, face_idx, depth
+
+
 def mesh_bleed_offsets(k):
     """dtp_mesh_bleed_offsets (host only, needs no GPU): the candidate offsets (di, dj) of a gutter texel's source at radius k in 1..16,
     sorted by (di^2 + dj^2, di, dj) -> int8 [n, 2].  The table of a smaller radius is a prefix of it."""

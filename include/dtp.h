@@ -25,7 +25,7 @@ extern "C" {
  * dtp_op_stroke_gather, dtp_op_stroke_paste) and the mesh strokes (dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_camera, dtp_mesh_stroke,
  * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
  * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) and the undo / redo journal
- * (dtp_journal_*, dtp_op_journal_tiles) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
+ * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
  * caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -407,6 +407,63 @@ int dtp_mesh_pick(dtp_mesh* mesh, const dtp_ray* rays, int n, dtp_mesh_hit* out_
 int dtp_mesh_ray_frame(const float origin[3], const float dir[3], float out[12]);
 int dtp_mesh_path_plan(const dtp_mesh_hit* hits, int n, float stamp_distance, dtp_path_state* state, float* pos, float* normal, float* prev,
                        int cap, int* count);
+
+/* ---------------------------------------------------------------- a view of a textured mesh
+ * replaces: the viewport.  In the reference the painted mesh is seen through Omniverse RTX, which reads the texture through
+ * update_material_texture (kit_app/.../python/manager.py:349-354).  dtp_mesh_view draws the whole mesh with a perspective camera into an
+ * H x W RGBA frame on the device: a preview, so that a client without Omniverse sees what it painted, and the frame whose pixels
+ * dtp_view_rays turns into the rays of dtp_mesh_pick.  The stamp camera of dtp_mesh_stroke stays orthographic, as the reference's is.
+ * Every fp32 operation below is rounded once and in the order written (no contraction, correctly rounded division and square root);
+ * nothing is compared under a tolerance.  The frame does not depend on the order in which faces are visited or on how they are binned.
+ *
+ * The camera (dtp_view_camera; host only, in double from the fp32 inputs, rounded to fp32 once): b = normalize(eye - at),
+ * r = normalize(cross(up, b)), u = cross(b, r); m = the rows (r, u, b), each followed by t = -row . eye, laid out as dtp_mesh_camera's;
+ * fy = 1 / tan((fov_y pi) / 360) with fov_y in degrees, fx = (fy H) / W; near as given.  DTP_ERR_ARG for anything non-finite, eye == at,
+ * an up that is zero or parallel to the view direction, fov_y outside (0, 180), near <= 0, H or W outside 1..4096, a result that does
+ * not fit fp32 (a non-finite value, fx or fy that round to 0, a near whose reciprocal is not finite).  A camera filled in by hand is held
+ * to the same rule by the two calls that take one.
+ * The rays (dtp_view_rays; host only, in double from the fp32 camera, rounded once): for pixel position (x, y), the centre of pixel
+ * (i, j) being (j + 0.5, i + 0.5): ndc_x = (2 x) / W - 1, ndc_y = 1 - (2 y) / H; origin = the eye as the camera holds it,
+ * -((r t_r + u t_u) + b t_b) per component; dir = (r (ndc_x / fx) + u (ndc_y / fy)) - b: a dtp_ray for dtp_mesh_pick.  pixels_xy host
+ * float [n][2], n >= 1.
+ *
+ * Per face (fp32): the camera-space x_k, y_k, z_k of its three vertices exactly as a stamp's projection computes them,
+ * ((m0 vx + m1 vy) + m2 vz) + t per row.  A face is drawn iff all nine values are finite and all three z_k <= -near.  A face with ANY
+ * vertex nearer than the near plane (or behind the eye) is DROPPED WHOLE, NOT CLIPPED: that is the price of exact coverage, and a mesh
+ * the camera stands inside loses the faces that cross the plane.  iw_k = 1.0f / (0.0f - z_k);
+ * X_k = snap((((x_k fx) iw_k) + 1) (128 W)), Y_k = snap((1 - ((y_k fy) iw_k)) (128 H)) with snap(v) = rint(v) clamped to +-2^26 and
+ * 128 W, 128 H exact.  A face of zero snapped area is not drawn.  Facing is the sign of the snapped integer area
+ * A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0): A < 0 is FRONT (counter-clockwise on the screen with y up: the side a stamp's render
+ * calls front), flip_normals swaps the two; cull = 0 draws both sides, cull = 1 front faces only.  nzu, for the shade, is the z of the
+ * camera-space unit normal as a stamp's projection computes it: n = cross(c1 - c0, c2 - c0), each component a product minus a product,
+ * nzu = nz / sqrt((nx nx + ny ny) + nz nz).
+ * Per pixel (i, j), centre (256 j + 128, 256 i + 128): the coverage of the strokes unchanged (int64 edge functions, both windings, the
+ * top-left fill rule) gives w_k = (float)E_k / (float)|A|; q_k = w_k iw_k; d = (q0 + q1) + q2, the inverse depth, which is linear on the
+ * screen.  The winner is the covering face with the largest (d, -face index).  Perspective-correct UV: u = ((q0 u0 + q1 u1) + q2 u2) / d,
+ * v likewise.
+ * Colour: the texture (u8 [TH][TW][4]) is sampled as a stamp's render samples it: the four taps and weights of grid_sample
+ * (align_corners False, border padding) at (u TW - 0.5, (1 - v) TH - 0.5), the blend ((v00 w00 + v01 w01) + v10 w10) + v11 w11 of
+ * byte / 255 per channel: t_R, t_G, t_B, t_A.  s = 1 without shade; with it s = ambient + (1 - ambient) |nzu|.
+ * c_ch = (t_ch t_A + (unpainted_ch / 255) (1 - t_A)) s for R, G, B; the byte is (unsigned char)(fminf(c_ch, 1) 255 + 0.5f) and the
+ * alpha byte 255.  face_idx = the winner, depth = 1.0f / d (the distance from the eye along the view direction).  A pixel no face
+ * covers gets the four bytes of background, face_idx -1, depth 0.  No colour management, no mip or anisotropic filtering, one sample
+ * per pixel: the frame aliases under minification and along silhouettes.
+ *
+ * dtp_mesh_view: texture device u8 [TH][TW][4] (1..32768 a side), image device u8 [H][W][4], face_idx device i32 [H][W] or NULL,
+ * depth device f32 [H][W] or NULL; all 4-byte aligned; 1 <= H, W <= 4096; ambient in 0..1; cull, flip_normals, shade 0 or 1.  Every
+ * check comes before any device call, a mesh that is not alive is refused and not followed, and a refused call writes nothing.  The
+ * call only ENQUEUES on `s` (a memset and four kernels) and returns.  The kernels read the vertices, faces and UVs of the mesh, the
+ * texture, and the view's own buffers (a 64-byte record per face, 4 F + F list entries, the bin counters), allocated at the first view of
+ * a mesh and freed with it; they touch nothing a stroke or a pick in flight uses, so a view on a stream of its own runs beside them.  A
+ * view that runs WHILE a stroke writes the texture shows each texel either old or new (every writer stores whole 4-byte texels), and
+ * may catch a stamp halfway; for a frame of everything painted so far, make `s` wait for the stroke's stream first.  Two views of ONE
+ * mesh at the same time share the buffers: they are the caller's to serialise. */
+typedef struct { float m[12]; float fx, fy, near; } dtp_view_cam;
+typedef struct { int cull, flip_normals, shade; float ambient; uint8_t unpainted[3]; uint8_t background[4]; } dtp_view_opts;
+int dtp_view_camera(const float eye[3], const float at[3], const float up[3], float fov_y_degrees, int H, int W, float near, dtp_view_cam* out);
+int dtp_view_rays(const dtp_view_cam* cam, int H, int W, const float* pixels_xy, int n, dtp_ray* out);
+int dtp_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
+                  uint8_t* image, int* face_idx, float* depth, dtp_stream s);
 
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
@@ -795,6 +852,11 @@ int dtp_op_mesh_backproject(dtp_mesh* mesh, const float* dec, int dec_finished, 
  * dtp_mesh_hit[n] (52 bytes each).  The same checks; it enqueues on `s` and waits for `s`, because the frames travel through the mesh's
  * pinned buffer. */
 int dtp_op_mesh_pick(dtp_mesh* mesh, const dtp_ray* rays, int n, dtp_mesh_hit* out, dtp_stream s);
+/* dtp_mesh_view (the contract: see "a view of a textured mesh") with the binning switched: binned 1 is dtp_mesh_view exactly; binned 0
+ * puts every drawn face on the list that every 16 x 16 tile streams, the arm a measurement compares the bins with.  The frame is the
+ * same bytes either way. */
+int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
+                     uint8_t* image, int* face_idx, float* depth, int binned, dtp_stream s);
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@ int stamp_plan(Ctx*, StampPlan&) { return unreachable("stamp_plan"); }
 int stamp_enqueue(Ctx*, const StampPlan&, hipStream_t) { return unreachable("stamp_enqueue"); }
 int ctx_persistent(Ctx*, size_t, void**, bool) { return unreachable("ctx_persistent"); }
 int stroke_default_mask(Ctx*, int, hipStream_t, const unsigned char**) { return unreachable("stroke_default_mask"); }
+Journal* journal_armed(Ctx*, const void*, int, int) { unreachable("journal_armed"); return nullptr; }
+int journal_save_box(Journal*, const int*, int, hipStream_t) { return unreachable("journal_save_box"); }
+void view_free(void*) {}  // (a mesh that never had a view holds nothing)
 
 static int g_checks = 0;
 #define EXPECT(cond)                                                                      \
