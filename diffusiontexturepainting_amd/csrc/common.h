@@ -98,15 +98,16 @@ static __device__ __forceinline__ float gelu_erf(float x) {
 // A `for (q) s += p[q * stride]` loop chains one memory round trip per term (hipcc does not pipeline a runtime trip count): with
 // 5-20 partial sums per row that chain was microseconds of pure latency in front of every LayerNorm-folded GEMM and GroupNorm apply.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-static __device__ __forceinline__ void sum_pairs_strided(const float* __restrict__ p, size_t stride, int n, float& s1, float& s2) {
-  s1 = 0.f; s2 = 0.f;
+template <class T>  // T = the accumulator type
+static __device__ __forceinline__ void sum_pairs_strided_t(const float* __restrict__ p, size_t stride, int n, T& s1, T& s2) {
+  s1 = 0; s2 = 0;
   int q = 0;
   for (; q + 8 <= n; q += 8) {
     f32x2 t[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) t[e] = *(const f32x2*)(p + (size_t)(q + e) * stride);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { s1 += t[e][0]; s2 += t[e][1]; }
+    for (int e = 0; e < 8; ++e) { s1 += (T)t[e][0]; s2 += (T)t[e][1]; }
   }
   if (q < n) {
     f32x2 t[8];
@@ -114,32 +115,18 @@ static __device__ __forceinline__ void sum_pairs_strided(const float* __restrict
     for (int e = 0; e < 8; ++e) t[e] = *(const f32x2*)(p + (size_t)(q + (q + e < n ? e : 0)) * stride);  // clamped: always a valid address
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      if (q + e < n) { s1 += t[e][0]; s2 += t[e][1]; }
+      if (q + e < n) { s1 += (T)t[e][0]; s2 += (T)t[e][1]; }
   }
 }
-
+static __device__ __forceinline__ void sum_pairs_strided(const float* __restrict__ p, size_t stride, int n, float& s1, float& s2) {
+  sum_pairs_strided_t(p, stride, n, s1, s2);
+}
 // The same walk with the partial sums added in DOUBLE (round 6, GroupNorm statistics): every partial is an accurately rounded fp32
 // (sum, sum of squares) of one chunk; their total and the final E[x^2] - mean^2 are formed in fp64, so the variance of a group whose
 // mean is hundreds of standard deviations away from zero does not drown in the rounding of fp32 sums (tests/test_gpu_ops.py
 // test_groupnorm_large_group_means; fp64 adds run at the fp32 rate on this chip and there are <= 16 per lane).
 static __device__ __forceinline__ void sum_pairs_strided_d(const float* __restrict__ p, size_t stride, int n, double& s1, double& s2) {
-  s1 = 0.0; s2 = 0.0;
-  int q = 0;
-  for (; q + 8 <= n; q += 8) {
-    f32x2 t[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = *(const f32x2*)(p + (size_t)(q + e) * stride);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s1 += (double)t[e][0]; s2 += (double)t[e][1]; }
-  }
-  if (q < n) {
-    f32x2 t[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = *(const f32x2*)(p + (size_t)(q + (q + e < n ? e : 0)) * stride);  // clamped: always a valid address
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (q + e < n) { s1 += (double)t[e][0]; s2 += (double)t[e][1]; }
-  }
+  sum_pairs_strided_t(p, stride, n, s1, s2);
 }
 // LayerNorm fold, the mean term: out = rstd * (x W^T - mean * lns) + bias.  The kernels that stage their accumulators through an fp16
 // tile (gemm_kernel, gemm_wide, xattn) subtract mean * lns from the fp32 accumulator BEFORE that rounding and multiply by rstd behind it:
@@ -164,7 +151,9 @@ static __device__ __forceinline__ double shfl_xor_d(double v, int o) {
 // 4 and 8: row_half_mirror / row_mirror (every lane of a quad / half row holds the same partial by then, so "the mirrored lane" is a lane of the
 // other quad / half: the same pairs, in the same order, as the xor butterfly taken from the small offsets up); 16 and 32: v_permlane16_swap /
 // v_permlane32_swap of gfx950 (inline asm: this hipcc's builtins return their first result twice, attn_dma.hip).  All lanes of the group must be
-// active.  Bit-identical to `for (o = 1; o < W; o <<= 1) v = op(v, __shfl_xor(v, o))`.
+// active.  Bit-identical to the ASCENDING butterfly `for (o = 1; o < W; o <<= 1) v = op(v, __shfl_xor(v, o))` -- which is NOT the order of the
+// descending loops (o = W / 2 down to 1) it replaced in most kernels: a sum's last bits depend on the order, and every kernel's order is part
+// of its output bytes (gemm_fp8 / gemm_f8f8 still reduce their row statistics from W / 2 down: rowstats_emit, tile_epilogue.h).
 template <int CTRL>
 static __device__ __forceinline__ float dpp_get_f(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));

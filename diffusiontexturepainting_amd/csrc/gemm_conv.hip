@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "tile_epilogue.h"
 
 namespace {
 
@@ -446,6 +447,8 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
   }
 
   // ---------------------------------------------------------------- epilogue
+  // (the steps of tile_epilogue.h -- stage, transform, round, statistics -- as this kernel's OWN text but for the statistics emit: why is
+  // written at the head of that file; keep the order of operations in step with it)
   if constexpr (KH == 2) {  // sum the two k-halves: waves 4-7 hand their accumulators to waves 0-3 through the (now free) stages
     static_assert(BM * BN * 4 <= NS * STAGE, "the fp32 exchange tile must fit in the pipeline buffers");
     float* red = (float*)smem;
@@ -669,13 +672,7 @@ __global__ __launch_bounds__(256 * KH + 64 * LW) void gemm_kernel(const GemmPara
         }
       }
     }
-    if (fl & GF_ROWSTATS) {  // NC consecutive lanes hold one row of this N tile: fixed-order shuffle reduce
-      s1 = group_allsum<NC>(s1); s2 = group_allsum<NC>(s2);
-      if (nc == 0 && m < p.M) {
-        p.st_out[((size_t)tile_n * st_rows + st_m0 + m) * 2] = s1;
-        p.st_out[((size_t)tile_n * st_rows + st_m0 + m) * 2 + 1] = s2;
-      }
-    }
+    if (fl & GF_ROWSTATS) rowstats_emit<NC>(s1, s2, nc == 0 && m < p.M, p.st_out + ((size_t)tile_n * st_rows + st_m0 + m) * 2);
   }
 }
 

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "tile_epilogue.h"
 
 namespace {
 
@@ -184,39 +185,23 @@ __global__ __launch_bounds__(256) void gemm_f8f8_kernel(const GemmParams p) {
   const float sc = p.a_scale * p.w_scale;
   f16* stg = (f16*)smem;
   const int fl = p.flags;
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) {
-      const int ml = wm0 + j * 32 + frow;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
-        f16x4 v = {(f16)(acc[i][j][4 * q] * sc), (f16)(acc[i][j][4 * q + 1] * sc), (f16)(acc[i][j][4 * q + 2] * sc), (f16)(acc[i][j][4 * q + 3] * sc)};
-        *(f16x4*)(stg + ml * SLD + nl) = v;
-      }
-    }
+  stage_tile<TN, TM, SLD>(stg, acc, wm0 + frow, wn0 + 4 * fhalf, StageScaled{sc});
   __syncthreads();
   if (fl & GF_GEGLU) {  // W rows packed [a (64) | gate (64)] per 128-column tile -> 64 output columns
     const int nc = tid & 7;
     const int ca = nc * 8, cg = ca + 64, col = (n0 / 128) * 64 + nc * 8;
     float ba[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (fl & GF_BIAS) {
-#pragma unroll
-      for (int x = 0; x < 8; ++x) { ba[x] = p.bias[n0 + ca + x]; bg[x] = p.bias[n0 + cg + x]; }
+      cols8<false>(p.bias, n0 + ca, ba);
+      cols8<false>(p.bias, n0 + cg, bg);
     }
     const bool col_ok = (n0 + cg + 8 <= p.N);
     for (int idx = tid; idx < BM * 8; idx += NT) {
       const int ml = idx >> 3, m = m0 + ml;
       if (m >= p.M || !col_ok) continue;
       const f16x8 a = *(const f16x8*)(stg + ml * SLD + ca), gt = *(const f16x8*)(stg + ml * SLD + cg);
-      f16x8 o;
       float x[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        o[e] = (f16)(((float)a[e] + ba[e]) * gelu_erf((float)gt[e] + bg[e]));
-        x[e] = (float)o[e];
-      }
+      const f16x8 o = geglu_chunk(a, gt, 1.f, ba, bg, x);
       if (p.C) *(f16x8*)((f16*)p.C + (size_t)m * p.ldc + col) = o;
       if (p.C8) *(u32x2*)(p.C8 + (size_t)m * p.ldc8 + col) = q8x8(x, p.c_scale);
     }
@@ -226,42 +211,21 @@ __global__ __launch_bounds__(256) void gemm_f8f8_kernel(const GemmParams p) {
     const int nc = tid % NC, n = n0 + nc * 8;
     const bool col_ok = (n + 8 <= p.N);
     float bv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (col_ok && (fl & GF_BIAS)) {
-#pragma unroll
-      for (int x = 0; x < 8; ++x) bv[x] = p.bias[n + x];
-    }
+    if (col_ok && (fl & GF_BIAS)) cols8<false>(p.bias, n, bv);
     for (int idx = tid; idx < BM * NC; idx += NT) {  // BM * NC is a multiple of NT: every lane runs every iteration
       const int ml = idx / NC, m = m0 + ml;
       const bool active = col_ok && m < p.M;
       float s1 = 0.f, s2 = 0.f;
       if (active) {
-        const f16x8 v = *(const f16x8*)(stg + ml * SLD + nc * 8);
         float x[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = (float)v[k] + bv[k];
-        if (fl & GF_RESID) {
-          const f16x8 r = *(const f16x8*)(p.R + (size_t)m * p.ldr + n);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) x[k] += (float)r[k];
-        }
-        f16x8 o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          o[k] = (f16)x[k];
-          x[k] = (float)o[k];
-          s1 += x[k]; s2 += x[k] * x[k];
-        }
+        chunk_bias(x, *(const f16x8*)(stg + ml * SLD + nc * 8), bv);
+        f16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (fl & GF_RESID) r = *(const f16x8*)(p.R + (size_t)m * p.ldr + n);
+        const f16x8 o = chunk_round(x, fl & GF_RESID, r, s1, s2);
         if (p.C) *(f16x8*)((f16*)p.C + (size_t)m * p.ldc + n) = o;
         if (p.C8) *(u32x2*)(p.C8 + (size_t)m * p.ldc8 + n) = q8x8(x, p.c_scale);
       }
-      if (fl & GF_ROWSTATS) {
-#pragma unroll
-        for (int o = NC / 2; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-        if (nc == 0 && m < p.M) {
-          p.st_out[((size_t)tile_n * st_rows + m) * 2] = s1;
-          p.st_out[((size_t)tile_n * st_rows + m) * 2 + 1] = s2;
-        }
-      }
+      if (fl & GF_ROWSTATS) rowstats_emit<NC, true>(s1, s2, nc == 0 && m < p.M, p.st_out + ((size_t)tile_n * st_rows + m) * 2);
     }
   }
 }

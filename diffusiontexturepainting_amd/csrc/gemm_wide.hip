@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "tile_epilogue.h"
 
 namespace {
 
@@ -298,42 +299,16 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
   for (int e = 0; e < EP; ++e) {
     __syncthreads();  // pass 0: every wave finished reading the last stage; pass 1: the staging tile was consumed
     if (wm0 / ROWS_EP == e) {
+      const int row0 = wm0 - e * ROWS_EP + frow, col0 = wn0 + 4 * fhalf;
       if (fl & GF_LNFOLD) {
         // the mean term of the LayerNorm fold, mean * lns, leaves the accumulator in fp32, before the rounding (the row sums wait in LDS;
         // common.h, col4)
         float mean[TM];
 #pragma unroll
         for (int j = 0; j < TM; ++j) mean[j] = rowst[2 * (wm0 + j * 32 + frow)];
-#pragma unroll
-        for (int i = 0; i < TN; ++i) {
-          f32x4 l[4];  // this lane's 16 columns of n-block i: read once, before the staging stores (which the compiler must assume alias them)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) l[q] = *(const f32x4*)(lnst + wn0 + i * 32 + 8 * q + 4 * fhalf);
-#pragma unroll
-          for (int j = 0; j < TM; ++j) {
-            const int ml = wm0 - e * ROWS_EP + j * 32 + frow;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
-              f16x4 v = {(f16)(acc[i][j][4 * q] - mean[j] * l[q][0]), (f16)(acc[i][j][4 * q + 1] - mean[j] * l[q][1]),
-                         (f16)(acc[i][j][4 * q + 2] - mean[j] * l[q][2]), (f16)(acc[i][j][4 * q + 3] - mean[j] * l[q][3])};
-              *(f16x4*)(stg + ml * SLD + nl) = v;
-            }
-          }
-        }
+        stage_tile<TN, TM, SLD>(stg, acc, row0, col0, StageLnFold{mean, lnst + col0});
       } else {
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-          for (int j = 0; j < TM; ++j) {
-            const int ml = wm0 - e * ROWS_EP + j * 32 + frow;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
-              f16x4 v = {(f16)acc[i][j][4 * q], (f16)acc[i][j][4 * q + 1], (f16)acc[i][j][4 * q + 2], (f16)acc[i][j][4 * q + 3]};
-              *(f16x4*)(stg + ml * SLD + nl) = v;
-            }
-          }
+        stage_tile<TN, TM, SLD>(stg, acc, row0, col0, StageAsIs{});
       }
     }
     __syncthreads();
@@ -347,10 +322,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
         const int ca = g * 128 + nc * 8, cg = ca + 64;
         float ba[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fl & GF_BIAS) {
-          const f32x4 t0 = *(const f32x4*)(p.bias + n0 + ca), t1 = *(const f32x4*)(p.bias + n0 + ca + 4);
-          const f32x4 u0 = *(const f32x4*)(p.bias + n0 + cg), u1 = *(const f32x4*)(p.bias + n0 + cg + 4);
-#pragma unroll
-          for (int x = 0; x < 4; ++x) { ba[x] = t0[x]; ba[4 + x] = t1[x]; bg[x] = u0[x]; bg[4 + x] = u1[x]; }
+          cols8(p.bias, n0 + ca, ba);
+          cols8(p.bias, n0 + cg, bg);
         }
         const bool col_ok = (n0 + cg + 8 <= p.N);  // N % 128 == 0 for GEGLU: whole groups are in or out
         for (int idx = tid; idx < ROWS_EP * IT; idx += NT) {
@@ -359,19 +332,14 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
           const f16x8 a = *(const f16x8*)(stg + ml * SLD + ca);
           const f16x8 gt = *(const f16x8*)(stg + ml * SLD + cg);
           const float rstd = (fl & GF_LNFOLD) ? rowst[2 * (e * ROWS_EP + ml) + 1] : 1.f;  // (the mean term left the accumulators before they were staged)
-          f16x8 o;
-#pragma unroll
-          for (int x = 0; x < 8; ++x) {
-            const float av = rstd * (float)a[x] + ba[x];
-            const float gv = rstd * (float)gt[x] + bg[x];
-            o[x] = (f16)(av * gelu_erf(gv));
-          }
-          *(f16x8*)((f16*)p.C + (size_t)m * p.ldc + (size_t)(tile_n * G + g) * 64 + nc * 8) = o;
+          float x[8];
+          *(f16x8*)((f16*)p.C + (size_t)m * p.ldc + (size_t)(tile_n * G + g) * 64 + nc * 8) = geglu_chunk(a, gt, rstd, ba, bg, x);
         }
       }
       continue;
     }
-    // plain epilogue: a thread owns the same 8-column chunk in every iteration (NTE % NC == 0)
+    // plain epilogue: a thread owns the same 8-column chunk in every iteration (NTE % NC == 0).  Steps (2) and (3) of tile_epilogue.h
+    // as this kernel's OWN text: through helpers the bias + residual + statistics launches were slower
     constexpr int NTE = (NT / NC) * NC;
     const int nc = tid % NC, n = n0 + nc * 8;
     const bool col_ok = (tid < NTE) && (n + 8 <= p.N);  // N % 8 == 0 is required by the launcher
@@ -437,13 +405,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_wide_kernel(const GemmParams
         *(f16x8*)((f16*)p.C + (size_t)m * p.ldc + n) = o;
       }
       if constexpr (NTE == NT && (NC & (NC - 1)) == 0 && NC <= 64) {
-        if (fl & GF_ROWSTATS) {  // NC consecutive lanes hold one row of this N tile: fixed-order shuffle reduce
-          s1 = group_allsum<NC>(s1); s2 = group_allsum<NC>(s2);
-          if (nc == 0 && ml < ROWS_EP && m < p.M) {
-            p.st_out[((size_t)tile_n * st_rows + m) * 2] = s1;
-            p.st_out[((size_t)tile_n * st_rows + m) * 2 + 1] = s2;
-          }
-        }
+        if (fl & GF_ROWSTATS) rowstats_emit<NC>(s1, s2, nc == 0 && ml < ROWS_EP && m < p.M, p.st_out + ((size_t)tile_n * st_rows + m) * 2);
       }
     }
   }

@@ -17,6 +17,7 @@
 // Reference: diffusers CrossAttention (attn2 of BasicTransformerBlock) as called from trt_inference/models.py:1097-1139 (the UNet
 // engine); the algebraic fusion itself is described in unet.hip transformer().
 #include "common.h"
+#include "tile_epilogue.h"
 
 namespace {
 
@@ -210,15 +211,7 @@ __global__ __launch_bounds__(256) void xattn_kernel(const XattnParams p) {
   f16* const stg = (f16*)ring;
   auto stage_acc = [&]() {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ml = wm0 + frow;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int nl = wn0 + i * 32 + 8 * q + 4 * fhalf;
-        f16x4 v = {(f16)acc[i][4 * q], (f16)acc[i][4 * q + 1], (f16)acc[i][4 * q + 2], (f16)acc[i][4 * q + 3]};
-        *(f16x4*)(stg + ml * XSLD + nl) = v;
-      }
-    }
+    for (int i = 0; i < 2; ++i) stage_block(stg + (wm0 + frow) * XSLD + wn0 + i * 32 + 4 * fhalf, acc[i], [](int, int, float a) { return a; });
   };
   {  // the mean term of the LayerNorm fold, in fp32 before the scores are rounded to fp16 (common.h, col4)
     const float mean = rowst[2 * (wm0 + frow)];

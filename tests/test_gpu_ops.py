@@ -463,7 +463,7 @@ def test_gemm_two_activation_matrices(ops, m, k1, k2, n, tile, splits):
 
 @pytest.mark.parametrize("tile", [-1, 20, 21])
 def test_gemm_epilogues(ops, tile):
-    from diffusiontexturepainting_amd._lib import GF_BIAS_M, GF_GELU, GF_QUICKGELU, GF_SILU
+    from diffusiontexturepainting_amd._lib import GF_BIAS_M, GF_GELU, GF_OUT_F32, GF_QUICKGELU, GF_SILU
     m, n, k = 130, 256, 192
     a, w = rnd(m, k, seed=11), rnd(n, k, seed=12, scale=k ** -0.5)
     bias = torch.randn(n, generator=torch.Generator().manual_seed(13))
@@ -481,6 +481,13 @@ def test_gemm_epilogues(ops, tile):
     bm = torch.randn(m, generator=torch.Generator().manual_seed(14))
     got = ops.gemm(a.cuda(), wp, n, k, bias=bm.cuda(), flags=GF_BIAS_M)
     close(got, F.linear(a.float(), w.float()) + bm[:, None])
+    # the same activations behind a split contraction: the slabs are summed, biased and activated by the reduce kernel (four columns per
+    # thread with an fp16 output, one per thread with an fp32 one); reached once, by the tile = -1 case (the wide tiles returned above)
+    for f32 in (0, GF_OUT_F32):
+        close(ops.gemm(a.cuda(), wp, n, k, bias=bias.cuda(), flags=GF_GELU | f32, tile=2, splits=3), F.gelu(lin))
+        close(ops.gemm(a.cuda(), wp, n, k, bias=bias.cuda(), flags=GF_QUICKGELU | f32, tile=2, splits=3), lin * torch.sigmoid(1.702 * lin))
+        close(ops.gemm(a.cuda(), wp, n, k, bias=bias.cuda(), flags=GF_SILU | f32, tile=2, splits=3), F.silu(lin))
+    close(ops.gemm(a.cuda(), wp, n, k, bias=bm.cuda(), flags=GF_BIAS_M | GF_SILU, tile=2, splits=3), F.silu(F.linear(a.float(), w.float()) + bm[:, None]))
 
 
 CONV_CASES = [
