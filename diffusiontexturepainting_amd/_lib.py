@@ -80,6 +80,10 @@ class ViewOpts(C.Structure):  # dtp_view_opts
 VIEW_MAX = 4096  # the largest side of a view's frame
 
 
+class MipLevels(C.Structure):  # dtp_mip_levels
+    _fields_ = [("levels", C.c_int), ("h", C.c_int * 16), ("w", C.c_int * 16), ("offset", C.c_uint64 * 16), ("bytes", C.c_uint64)]
+
+
 class ProfRow(C.Structure):
     _fields_ = [("kind", C.c_int), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -215,6 +219,9 @@ SYMBOLS = {
     "dtp_view_rays": (_i, [C.POINTER(ViewCam), _i, _i, _vp, _i, _vp]),
     "dtp_mesh_view": (_i, [_vp, _vp, _i, _i, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _vp]),
     "dtp_op_mesh_view": (_i, [_vp, _vp, _i, _i, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _i, _vp]),
+    "dtp_mip_layout": (_i, [_i, _i, C.POINTER(MipLevels)]),
+    "dtp_texture_mips": (_i, [_vp, _i, _i, _vp, C.c_uint64, _vp]),
+    "dtp_mesh_view_mips": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _vp, _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

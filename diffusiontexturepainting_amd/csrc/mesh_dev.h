@@ -37,6 +37,20 @@ __device__ __forceinline__ bool cover(const int X[3], const int Y[3], int px, in
   for (int k = 0; k < 3; ++k) w[k] = (float)E[k] / fa;
   return true;
 }
+// The barycentric weights of cover() at (px, py) with NO inside test: the same sign-normalised edge functions over the same |A|, for a
+// point that may lie outside the triangle (a weight is then negative).  false: a triangle of zero area (w untouched).
+__device__ __forceinline__ bool weights_at(const int X[3], const int Y[3], int px, int py, float w[3]) {
+  const long long A = orient(X[0], Y[0], X[1], Y[1], X[2], Y[2]);
+  if (A == 0) return false;
+  const long long s = A > 0 ? 1 : -1;
+  const float fa = (float)(s * A);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int a = (k + 1) % 3, b = (k + 2) % 3;
+    w[k] = (float)(s * orient(X[a], Y[a], X[b], Y[b], px, py)) / fa;
+  }
+  return true;
+}
 __device__ __forceinline__ float interp(const float w[3], float a0, float a1, float a2) { return (w[0] * a0 + w[1] * a1) + w[2] * a2; }
 
 // grid_sample(align_corners=False, padding_mode="border") at pixel position (x, y) of an Hs x Ws image: the four taps and their weights

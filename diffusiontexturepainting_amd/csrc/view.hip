@@ -7,7 +7,8 @@
 // 64 x 64 pixels, the counts are scanned, the faces written into their bins' segments, and a tile of 16 x 16 pixels streams its bin's
 // segment alone -- plus the short list of faces too large to bin.  No capacity to choose, no overflow, no read-back.  The kernels read
 // the mesh's vertices, faces and UVs and write buffers of their own: nothing a stroke or a pick in flight uses.  Plain HIP: vector loads,
-// stores and atomics only.
+// stores and atomics only.  dtp_mesh_view_mips is the same frame with a trilinear sample from the texture's mip pyramid
+// (mips.hip): the raster kernel is a template on the filter, and its unfiltered instantiation is dtp_mesh_view's code.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stddef.h>
@@ -15,6 +16,7 @@
 
 #include "engine.h"
 #include "mesh_dev.h"
+#include "mips_host.h"
 #include "view_host.h"
 
 namespace {
@@ -34,6 +36,11 @@ struct ViewBufs {
   ViewState* st = nullptr;
 };
 struct ViewShade { int shade; float ambient, unpainted[3]; unsigned int background; };  // travels as a kernel argument
+// what the raster kernel needs of the filter it is instantiated for; travels as a kernel argument.  0: one bilinear sample of level 0
+// (dtp_mesh_view); 1: trilinear between two levels of the pyramid (dtp_mesh_view_mips): levels 1 .. levels - 1 as dtp_texture_mips lays
+// them out, and the map of lod (or null)
+template <int FILTER> struct ViewFilter {};
+template <> struct ViewFilter<1> { const unsigned int* mips; float* lod; int levels; };
 
 // counter[key] += 1 for every lane of the wave whose key is >= 0, with ONE atomic per distinct key: the lanes that share a key elect a
 // leader, which adds their number; -> the lane's slot, the counter's value before its own add.  Neighbouring faces of a mesh mostly share
@@ -147,13 +154,30 @@ __global__ __launch_bounds__(256) void view_fill_kernel(const ViewRec* __restric
   }
 }
 
+// the bilinear sample of an h x w level at (u, v): the four taps of grid_sample, byte / 255 per channel
+__device__ __forceinline__ void view_sample(const unsigned int* __restrict__ tex, int h, int w, float u, float v, float tc[4]) {
+  const Taps tp = taps(u * (float)w - 0.5f, (1.0f - v) * (float)h - 0.5f, h, w);
+  const unsigned int t00 = tex[(size_t)tp.y0 * w + tp.x0], t01 = tex[(size_t)tp.y0 * w + tp.x1];
+  const unsigned int t10 = tex[(size_t)tp.y1 * w + tp.x0], t11 = tex[(size_t)tp.y1 * w + tp.x1];
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) {
+    const int s8 = 8 * ch;
+    tc[ch] = blend(tp, (float)((t00 >> s8) & 0xffu) / 255.0f, (float)((t01 >> s8) & 0xffu) / 255.0f,
+                   (float)((t10 >> s8) & 0xffu) / 255.0f, (float)((t11 >> s8) & 0xffu) / 255.0f);
+  }
+}
+
 // One workgroup per 16 x 16 pixel tile, one thread per pixel.  The tile's bin segment, then the large list, stream through LDS CHUNK at a
 // time; a face whose pixel range misses the tile is dropped on the way in.  Winner: the largest (inverse depth d, -face index) among
-// the faces that cover the centre.  Then the perspective-correct UV, the bilinear sample, the shade and the stores.
+// the faces that cover the centre.  Then the perspective-correct UV, the sample, the shade and the stores.  FILTER 1: the winner face
+// alone is evaluated again at the two neighbouring centres, the footprint of the pixel in the texture picks a level of the pyramid by
+// compares against powers of four (walking the layout on the way), and the sample is blended from that level and the next.
+template <int FILTER>
 __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restrict__ rec, const int* __restrict__ items, const int* __restrict__ large,
                                                           const ViewState* st, int F, int nbx, const float* __restrict__ uvs,
                                                           const unsigned int* __restrict__ tex, int TH, int TW, int H, int W, ViewShade sh,
-                                                          unsigned int* __restrict__ image, int* __restrict__ face_idx, float* __restrict__ depth) {
+                                                          unsigned int* __restrict__ image, int* __restrict__ face_idx, float* __restrict__ depth,
+                                                          ViewFilter<FILTER> fl) {
   __shared__ int s_n, s_face[CHUNK], s_X[CHUNK][3], s_Y[CHUNK][3];
   __shared__ float s_iw[CHUNK][3];
   const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
@@ -197,19 +221,45 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   if (!live) return;
   const size_t pix = (size_t)row * W + col;
   unsigned int out = sh.background;
-  float dist = 0.f;
+  float dist = 0.f, lod = 0.f;
   if (best >= 0) {
     const float* uv = uvs + (size_t)6 * best;
     const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
-    const Taps tp = taps(u * (float)TW - 0.5f, (1.0f - v) * (float)TH - 0.5f, TH, TW);
-    const unsigned int t00 = tex[(size_t)tp.y0 * TW + tp.x0], t01 = tex[(size_t)tp.y0 * TW + tp.x1];
-    const unsigned int t10 = tex[(size_t)tp.y1 * TW + tp.x0], t11 = tex[(size_t)tp.y1 * TW + tp.x1];
     float tc[4];
+    if constexpr (FILTER == 0) {
+      view_sample(tex, TH, TW, u, v, tc);
+    } else {
+      const ViewRec& r = rec[best];
+      float wx[3], wy[3];
+      weights_at(r.X, r.Y, px + 256, py, wx);
+      weights_at(r.X, r.Y, px, py + 256, wy);
+      const float qx[3] = {wx[0] * r.iw[0], wx[1] * r.iw[1], wx[2] * r.iw[2]}, qy[3] = {wy[0] * r.iw[0], wy[1] * r.iw[1], wy[2] * r.iw[2]};
+      const float dx = (qx[0] + qx[1]) + qx[2], dy = (qy[0] + qy[1]) + qy[2];
+      float rho2 = INFINITY;  // beyond the horizon, or a footprint that is not finite: the last level
+      if (isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f) {
+        const float fw = (float)TW, fh = (float)TH;
+        const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
+        const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
+        rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
+        if (!isfinite(rho2)) rho2 = INFINITY;
+      }
+      // level l of hl x wl texels at `at` of the pyramid (l >= 1), level l + 1 at `next`; p4 = 4^l
+      int l = 0, hl = TH, wl = TW;
+      size_t at = 0, next = 0;
+      float p4 = 1.0f;
+      while (l + 1 < fl.levels && p4 * 4.0f <= rho2) {
+        at = next; hl = mip_half(hl); wl = mip_half(wl); next = at + (size_t)hl * wl;
+        p4 *= 4.0f; ++l;
+      }
+      const float f = (l + 1 == fl.levels || rho2 <= p4) ? 0.f : ((rho2 / p4) - 1.0f) / 3.0f;
+      lod = (float)l + f;
+      view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
+      if (f > 0.f) {
+        float tn[4];
+        view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
 #pragma unroll
-    for (int ch = 0; ch < 4; ++ch) {
-      const int s8 = 8 * ch;
-      tc[ch] = blend(tp, (float)((t00 >> s8) & 0xffu) / 255.0f, (float)((t01 >> s8) & 0xffu) / 255.0f,
-                     (float)((t10 >> s8) & 0xffu) / 255.0f, (float)((t11 >> s8) & 0xffu) / 255.0f);
+        for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+      }
     }
     const float s = sh.shade ? sh.ambient + (1.0f - sh.ambient) * fabsf(rec[best].nzu) : 1.0f;
     const float rest = 1.0f - tc[3];
@@ -224,6 +274,9 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   image[pix] = out;
   if (face_idx) face_idx[pix] = best;
   if (depth) depth[pix] = dist;
+  if constexpr (FILTER != 0) {
+    if (fl.lod) fl.lod[pix] = lod;
+  }
 }
 
 int view_reserve(const MeshGeom& g) {
@@ -244,10 +297,17 @@ int view_reserve(const MeshGeom& g) {
 }
 
 // every check, then zero the counters -> project -> scan -> fill -> raster on s; nothing waits
+// filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null)
 int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* o,
-             uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s) {
+             uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s, int filter = 0, const uint8_t* mips = nullptr, float* lod = nullptr) {
   if (!mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
   if (const char* why = view_check(texture, TH, TW, cam, H, W, o, image, face_idx, depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
+  dtp_mip_levels lay;
+  if (filter) {
+    (void)mip_layout(TH, TW, &lay);  // (the sides were checked above)
+    if (lay.levels > 1 && !mips) { dtp_set_error("%s: NULL argument (mips is required for a texture larger than 1 x 1)", who); return DTP_ERR_ARG; }
+    if (((uintptr_t)mips & 3) != 0 || ((uintptr_t)lod & 3) != 0) { dtp_set_error("%s: mips and lod must be 4-byte aligned", who); return DTP_ERR_ARG; }
+  }
   MeshGeom g;
   if (!mesh_geom(mesh, &g)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
   HIP_CHECK(hipSetDevice(g.ctx->device));
@@ -264,8 +324,16 @@ int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, in
                      b->rec, b->large, b->st);
   hipLaunchKernelGGL(view_scan_kernel, dim3(1), dim3(256), 0, s, b->st);
   hipLaunchKernelGGL(view_fill_kernel, dim3(blocks), dim3(256), 0, s, b->rec, g.F, nbx, b->items, b->st);
-  hipLaunchKernelGGL(view_raster_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs,
-                     (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth);
+  const dim3 tiles((W + 15) / 16, (H + 15) / 16);
+  if (filter) {
+    ViewFilter<1> fl;
+    fl.mips = (const unsigned int*)mips; fl.lod = lod; fl.levels = lay.levels;
+    hipLaunchKernelGGL(view_raster_kernel<1>, tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs,
+                       (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, fl);
+  } else {
+    hipLaunchKernelGGL(view_raster_kernel<0>, tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs,
+                       (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, ViewFilter<0>());
+  }
   if (hipGetLastError() != hipSuccess) { dtp_set_error("%s: a kernel launch failed", who); return DTP_ERR_HIP; }
   return DTP_OK;
 }
@@ -301,6 +369,11 @@ int dtp_view_rays(const dtp_view_cam* cam, int H, int W, const float* pixels_xy,
 int dtp_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
                   uint8_t* image, int* face_idx, float* depth, dtp_stream s) {
   return view_run("dtp_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, (hipStream_t)s);
+}
+
+int dtp_mesh_view_mips(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                       const dtp_view_opts* opts, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s) {
+  return view_run("dtp_mesh_view_mips", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, (hipStream_t)s, 1, mips, lod);
 }
 
 int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,

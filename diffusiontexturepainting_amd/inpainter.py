@@ -175,6 +175,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         self.stream = torch.cuda.Stream(device=self._device)
         self.pick_stream = torch.cuda.Stream(device=self._device)  # pick() alone runs here, beside whatever self.stream has queued
         self._view_stream = None  # render_view() alone runs there: made at the first view (see view_stream)
+        self._view_mips = {}      # (TH, TW) -> the pyramid render_view(filter="trilinear") builds when it is given none
         self.conditioning = None
         self.image = None
         self._slots = {}  # conditioning slot -> (image [1,3,R,R], (cond, uncond))
@@ -526,7 +527,8 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         return self._view_stream
 
     def render_view(self, mesh, texture, camera, size=None, cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128),
-                    background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False):
+                    background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False, filter="bilinear", mips=None,
+                    want_lod=False):
         """A perspective view of the whole painted mesh (dtp_mesh_view; in the Kit app the viewport is Omniverse RTX):
         `mesh` from load_mesh, `texture` uint8 [TH, TW, 4] on the model's device, `camera` from mesh.view_camera, size = (H, W) (default
         the camera's; each side 1..4096).  -> the frame, uint8 [H, W, 4] on the device (RGB the texture under its alpha over `unpainted`,
@@ -537,7 +539,18 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         write into.  The call only enqueues, on self.view_stream.  live=False: that stream first waits for everything queued on the
         stroke's stream, so the frame shows all that was painted so far and is exact.  live=True: it waits for nothing and answers while
         a queued stroke is still painting; each texel is then either old or new, and the frame may catch a stamp halfway.  The
-        caller's current stream waits for the frame (on the device; the host does not block).  One view of a mesh at a time."""
+        caller's current stream waits for the frame (on the device; the host does not block).  One view of a mesh at a time.
+        filter="trilinear" (dtp_mesh_view_mips): the sample is blended from two levels of the texture's mip pyramid,
+        picked per pixel from the pixel's footprint in the texture, so a minified mesh shows its colour instead of single texels; a
+        magnified frame is the bilinear one byte for byte.  mips: the pyramid from build_mips(texture) (complete before a live=True
+        call, which waits for nothing); None: built here on the view's stream, after the same waits the frame makes, into a buffer the
+        model keeps per texture shape -- so a live pyramid may catch a stamp halfway, as the frame may.  want_lod: also the level
+        each pixel took, float32 [H, W] (0 where no face is), last in the tuple."""
+        if filter not in ("bilinear", "trilinear"):
+            raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
+        trilinear = filter == "trilinear"
+        if not trilinear and (mips is not None or want_lod):
+            raise ValueError("mips and want_lod need filter='trilinear'")
         if not isinstance(mesh, _mesh.Mesh):
             raise ValueError("mesh must come from load_mesh()")
         if not isinstance(camera, _mesh.ViewCamera):
@@ -555,27 +568,70 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         cam = camera.struct()
         cur = torch.cuda.current_stream(self._device)
         given = out
+        build = trilinear and mips is None
+        if trilinear:
+            need = self._mip_bytes(texture)
+            if mips is not None and not (isinstance(mips, torch.Tensor) and mips.dtype == torch.uint8 and mips.dim() == 1 and mips.numel() >= need
+                                         and mips.device == self._device and mips.is_contiguous()):
+                raise ValueError(f"mips must be a contiguous uint8 tensor of at least {need} bytes on {self._device} (build_mips)")
         with torch.cuda.stream(self.view_stream):  # the outputs belong to the view's stream: a live view waits for no other
             if out is None:
                 out = torch.empty(H, W, 4, dtype=torch.uint8, device=self._device)
             face_idx = torch.empty(H, W, dtype=torch.int32, device=self._device) if want_face_idx else None
             depth = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_depth else None
+            lod = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_lod else None
+            if build:
+                key = (texture.shape[0], texture.shape[1])
+                if key not in self._view_mips:
+                    self._view_mips[key] = torch.empty(need, dtype=torch.uint8, device=self._device)
+                mips = self._view_mips[key]
         if not live:
             done = torch.cuda.Event()
             done.record(self.stream)
             self.view_stream.wait_event(done)
             self.view_stream.wait_stream(cur)
-        check(self._lib.dtp_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(opts), ptr(out),
-                                      ptr(face_idx), ptr(depth), C.c_void_p(self.view_stream.cuda_stream)), "dtp_mesh_view")
+        vs = C.c_void_p(self.view_stream.cuda_stream)
+        if trilinear:
+            if build:
+                check(self._lib.dtp_texture_mips(ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), need, vs), "dtp_texture_mips")
+            check(self._lib.dtp_mesh_view_mips(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), C.byref(cam), H, W,
+                                               C.byref(opts), ptr(out), ptr(face_idx), ptr(depth), ptr(lod), vs), "dtp_mesh_view_mips")
+        else:
+            check(self._lib.dtp_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(opts), ptr(out),
+                                          ptr(face_idx), ptr(depth), vs), "dtp_mesh_view")
         cur.wait_stream(self.view_stream)
-        for t in (texture, given):
+        for t in (texture, given, None if build else mips):
             if t is not None:
                 t.record_stream(self.view_stream)
-        for t in (None if given is not None else out, face_idx, depth):
+        for t in (None if given is not None else out, face_idx, depth, lod):
             if t is not None:
                 t.record_stream(cur)
-        extra = tuple(t for t in (face_idx, depth) if t is not None)
+        extra = tuple(t for t in (face_idx, depth, lod) if t is not None)
         return (out,) + extra if extra else out
+
+    def _mip_bytes(self, texture):
+        lay = _lib.MipLevels()
+        check(self._lib.dtp_mip_layout(texture.shape[0], texture.shape[1], C.byref(lay)), "dtp_mip_layout")
+        return int(lay.bytes)
+
+    def build_mips(self, texture, out=None):
+        """The mip pyramid of a painted texture (dtp_texture_mips): texture uint8 [TH, TW, 4] on the model's device ->
+        uint8 [bytes], levels 1 .. levels - 1 one after the other as ops.mip_layout(TH, TW) says (level 0 is the texture itself; a
+        1 x 1 texture has 0 bytes).  Alpha-weighted in exact integers: an unpainted texel (0, 0, 0, 0) adds no colour, so chart borders
+        do not darken.  out: a buffer of at least that many bytes to write into.  For render_view(filter="trilinear", mips=...) and for
+        an exporter that hands the levels to a renderer's sampler.  The call only enqueues, on the current stream."""
+        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
+                and texture.device == self._device and texture.is_contiguous()):
+            raise ValueError(f"texture must be a contiguous uint8 [TH, TW, 4] tensor on {self._device}")
+        need = self._mip_bytes(texture)
+        if out is None:
+            out = torch.empty(need, dtype=torch.uint8, device=self._device)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.dim() == 1 and out.numel() >= need and out.device == self._device
+                  and out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor of at least {need} bytes on {self._device}")
+        check(self._lib.dtp_texture_mips(ptr(texture), texture.shape[0], texture.shape[1], ptr(out), out.numel(),
+                                         C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)), "dtp_texture_mips")
+        return out
 
     def bleed_texture(self, mesh, texture, bleed, rect=None):
         """The bleed pass of paint_mesh_stroke on its own (dtp_mesh_bleed), for a texture that was loaded from a file or painted without

@@ -643,6 +643,16 @@ def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True,
     return image, face_idx, depth
 
 
+def mip_layout(TH, TW):
+    """dtp_mip_layout (host only, needs no GPU): where the levels of the mip pyramid of a TH x TW texture lie -> dict(levels, h, w,
+    offset, bytes): h, w, offset lists of `levels` entries (level 0 is the texture itself, offset[0] = 0 and unused; offset[1] = 0),
+    bytes the size of the buffer of levels 1 .. levels - 1 (MI355ConditionalInpainter.build_mips)."""
+    lay = _lib.MipLevels()
+    check(_lib.load().dtp_mip_layout(int(TH), int(TW), C.byref(lay)), "dtp_mip_layout")
+    n = lay.levels
+    return dict(levels=n, h=list(lay.h)[:n], w=list(lay.w)[:n], offset=list(lay.offset)[:n], bytes=int(lay.bytes))
+
+
 def mesh_bleed_offsets(k):
     """dtp_mesh_bleed_offsets (host only, needs no GPU): the candidate offsets (di, dj) of a gutter texel's source at radius k in 1..16,
     sorted by (di^2 + dj^2, di, dj) -> int8 [n, 2].  The table of a smaller radius is a prefix of it."""

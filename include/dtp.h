@@ -25,8 +25,9 @@ extern "C" {
  * dtp_op_stroke_gather, dtp_op_stroke_paste) and the mesh strokes (dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_camera, dtp_mesh_stroke,
  * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
  * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) and the undo / redo journal
- * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) are additions; nothing that existed at version 3 changed its signature or behaviour, so a
- * caller built against the earlier header keeps working. */
+ * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) and the
+ * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) are additions; nothing that existed at
+ * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
 /* error codes (every entry point returns one; dtp_last_error() has the text) */
@@ -464,6 +465,55 @@ int dtp_view_camera(const float eye[3], const float at[3], const float up[3], fl
 int dtp_view_rays(const dtp_view_cam* cam, int H, int W, const float* pixels_xy, int n, dtp_ray* out);
 int dtp_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
                   uint8_t* image, int* face_idx, float* depth, dtp_stream s);
+
+/* ---------------------------------------------------------------- the mip pyramid of a texture and a trilinear-filtered view
+ * A mesh seen whole is minified: many texels per pixel, and one bilinear sample of level 0 shows a nearly random one.
+ * dtp_texture_mips builds the pyramid of a painted texture on the device in exact integers, alpha-weighted, because unpainted texels are
+ * 0,0,0,0 and a plain box filter would drag black into every chart border; dtp_mesh_view_mips is dtp_mesh_view with a level chosen per
+ * pixel from the footprint of the pixel in the texture.  An exporter feeds the same pyramid to a renderer's sampler.  Nothing is
+ * compared under a tolerance.
+ *
+ * Layout (dtp_mip_layout; host only).  Level 0 is the texture itself and is never copied.  Level l + 1 has h' = (h + 1) / 2 rows and
+ * w' = (w + 1) / 2 columns (integer division), down to 1 x 1; levels = the number of levels including level 0 (<= 16 for sides up to
+ * 32768; a 1 x 1 texture has 1 level and 0 pyramid bytes).  Levels 1 .. levels - 1 lie one after the other in ONE buffer of 4-byte
+ * texels, row-major: offset[l] is the byte offset of level l in it, offset[1] = 0, offset[l + 1] = offset[l] + 4 h[l] w[l]; bytes = their
+ * sum.  h[0], w[0] = TH, TW; offset[0] and every entry from `levels` on are 0.  DTP_ERR_ARG for NULL and for sides outside 1..32768
+ * (nothing written).  (The struct is dtp_mip_levels: C does not let a typedef and a function share a name.)
+ *
+ * Texel rule (integers only).  Texel (i, j) of level l + 1 reads four texels of level l (h x w): rows 2 i and min(2 i + 1, h - 1),
+ * columns 2 j and min(2 j + 1, w - 1); a clamped index counts twice.  With the bytes c_k of a colour channel and a_k of alpha:
+ * A = sum a_k; alpha = (A + 2) >> 2; colour = A ? (sum c_k a_k + (A >> 1)) / A : 0 (an unsigned 32-bit division; the largest numerator
+ * is 4 x 255 x 255 + 510).  So a 2 x 2 block of one opaque red texel and three unpainted ones is 255,0,0,64, not a dark red.
+ *
+ * dtp_texture_mips: texture device u8 [TH][TW][4], mips device u8 [mips_bytes]; both 4-byte aligned; mips_bytes >= the layout's bytes.
+ * With 1 level, mips may be NULL and nothing is launched.  Every check comes before any device call and a refused call writes nothing.
+ * The call only ENQUEUES on `s`: one kernel per pass, a pass takes 64 x 64-texel tiles of its source level and writes that tile's part
+ * of up to six levels; the passes start from levels 0, 6 and 12 (at most three launches; two for 2048 x 2048).  It reads the texture
+ * and writes the pyramid alone; built while a stroke writes the texture it may catch a stamp halfway, as a view may.
+ *
+ * dtp_mesh_view_mips: dtp_mesh_view's arguments, checks, buffers and launches, plus mips (the pyramid of `texture` as dtp_texture_mips
+ * lays it out; device, 4-byte aligned; may be NULL when the layout has 1 level) and lod (device f32 [H][W], 4-byte aligned, or NULL).
+ * Visibility, face_idx and depth are dtp_mesh_view's.  Only the sample differs.  Per covered pixel, fp32, one rounded operation at a
+ * time in the order written, with L = levels:
+ *  1. (u, v) is the pixel's UV as dtp_mesh_view computes it.
+ *  2. The WINNER FACE ALONE is evaluated at the neighbouring centres (px + 256, py) and (px, py + 256) with no inside test: E_k' the same
+ *     sign-normalised int64 edge functions, w_k' = (float)E_k' / (float)|A|, q_k' = w_k' iw_k, d' = (q0' + q1') + q2',
+ *     u' = ((q0' u0 + q1' u1) + q2' u2) / d', v' likewise.
+ *  3. If either d' is not finite or not > 0 (the face's plane ends within a pixel: beyond the horizon), the level is L - 1 and f = 0.
+ *  4. a = ((u'_x - u) TW)^2 + ((v'_x - v) TH)^2 with (float)TW, (float)TH of level 0 and each square a product; b the same from the y
+ *     neighbour; rho2 = fmaxf(a, b).  A non-finite rho2 also takes level L - 1 with f = 0.
+ *  5. l = the largest level in 0 .. L - 1 with 4^l <= rho2 (compared against exact powers of four; no logarithm), or 0 when rho2 < 1.
+ *     f = 0 if l = L - 1 or rho2 <= 4^l, otherwise f = ((rho2 / 4^l) - 1) / 3: continuous and monotone, 0 at rho = 2^l and tending to 1
+ *     at 2^(l + 1).  lod = (float)l + f; a pixel no face covers gets lod 0.
+ *  6. t_l = the taps and blend of byte / 255 of dtp_mesh_view at level l with that level's h[l], w[l] in place of TH, TW.  If f > 0,
+ *     t = t_l + (t_(l + 1) - t_l) f per channel (a difference, a product, a sum); otherwise t = t_l and level l + 1 is not read.
+ *     The shade, the unpainted mix, the byte conversion and the background are dtp_mesh_view's.
+ * A frame with rho2 <= 1 everywhere is dtp_mesh_view's frame byte for byte.  No anisotropic filtering, no anti-aliasing of silhouettes. */
+typedef struct { int levels; int h[16], w[16]; uint64_t offset[16]; uint64_t bytes; } dtp_mip_levels;
+int dtp_mip_layout(int TH, int TW, dtp_mip_levels* out);
+int dtp_texture_mips(const uint8_t* texture, int TH, int TW, uint8_t* mips, uint64_t mips_bytes, dtp_stream s);
+int dtp_mesh_view_mips(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                       const dtp_view_opts* opts, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s);
 
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
