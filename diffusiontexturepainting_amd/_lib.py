@@ -84,6 +84,12 @@ class MipLevels(C.Structure):  # dtp_mip_levels
     _fields_ = [("levels", C.c_int), ("h", C.c_int * 16), ("w", C.c_int * 16), ("offset", C.c_uint64 * 16), ("bytes", C.c_uint64)]
 
 
+class DeltaSizes(C.Structure):  # dtp_delta_sizes
+    _fields_ = [(n, C.c_int) for n in ("tiles_x", "tiles_y", "n_tiles", "n_groups", "capacity")] + \
+        [(n, C.c_uint64) for n in ("shadow_bytes", "stale_bytes", "flag_bytes", "group_bytes", "ids_bytes", "tiles_bytes", "counts_bytes",
+                                   "host_ids_offset", "host_tiles_offset", "host_bytes")]
+
+
 class ProfRow(C.Structure):
     _fields_ = [("kind", C.c_int), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -233,6 +239,15 @@ SYMBOLS = {
     "dtp_journal_record_info": (_i, [_vp, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_i)]),
     "dtp_op_journal_tiles": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
     "dtp_journal_window_tiles": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i), _i, C.POINTER(_i)]),
+    "dtp_delta_layout": (_i, [_i, _i, _i, C.POINTER(DeltaSizes)]),
+    "dtp_delta_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "dtp_delta_destroy": (_i, [_vp]),
+    "dtp_delta_reset": (_i, [_vp, _vp]),
+    "dtp_delta_scan": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "dtp_delta_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "dtp_delta_host": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "dtp_delta_pull": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "dtp_op_delta_state": (_i, [_vp, _vp, _vp, _vp]),
 }
 
 

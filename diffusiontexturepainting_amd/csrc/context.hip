@@ -64,6 +64,7 @@ void dtp_destroy(dtp_ctx* ctx) {
   (void)hipDeviceSynchronize();
   graphs_drop_all(c);
   journal_drop_ctx(c);
+  delta_drop_ctx(c);
   mesh_drop_ctx(c);
   for (auto& s : c->staged) (void)hipFree(s.second.d);
   for (auto& s : c->refit_staged) (void)hipFree(s.second.d);

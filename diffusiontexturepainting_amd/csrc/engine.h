@@ -404,6 +404,8 @@ struct Journal* journal_armed(Ctx* c, const void* texture, int H, int W);
 int journal_save_windows(struct Journal* j, int R, const int* xs, const int* ys, int k, int wrap, hipStream_t s);
 // the tiles that meet the device-side texel box bb = {x0, y0, x1, y1} grown by `grow` and clipped (an empty box: none)
 int journal_save_box(struct Journal* j, const int* bb, int grow, hipStream_t s);
+// ---- delta.hip: the changed-tile trackers of images
+void delta_drop_ctx(Ctx* c);  // frees the trackers created on this handle (dtp_destroy)
 const Staged* ctx_find(Ctx* c, const std::string& name);
 int ctx_fetch_host(Ctx* c, const std::string& name, std::vector<float>& out);
 int ctx_upload_f32(Ctx* c, const std::vector<float>& v, float** out);

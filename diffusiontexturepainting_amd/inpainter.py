@@ -671,6 +671,26 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             capacity_tiles = 4 * _journal.tile_count(texture.shape[0], texture.shape[1])
         return _journal.Journal(self, texture, capacity_tiles, depth)
 
+    def delta_tracker(self, shape_or_image, capacity_tiles=None):
+        """A changed-tile tracker (dtp_delta_create) for images of one shape -- (H, W), or an image uint8 [H,W,4] to take
+        the shape from: -> delta.DeltaTracker.  Its pull(image) finds, on the device, the 16 x 16-texel tiles of a painted texture or of a
+        render_view frame whose bytes differ from what the tracker emitted last, and reads back those alone; frame(image) packs them for a
+        client that keeps a mirror with delta.apply_frame.  What the Kit app does by pushing the whole texture to the viewport after
+        every stamp (manager.py:349-354), for a client in another process.  capacity_tiles: the most tiles one pull emits (the rest follow
+        with the next pulls); default the image's tile count, which never caps.  Memory, all allocated here: a shadow image of H W 4
+        bytes, capacity_tiles KiB of payload on the device and the same pinned on the host, 2 bytes per tile; for a 2048^2 texture at
+        the default 16 + 16 + 16 MiB."""
+        from . import delta as _delta
+        if isinstance(shape_or_image, torch.Tensor):
+            if shape_or_image.dim() != 3 or shape_or_image.shape[2] != 4:
+                raise ValueError("an image to take the shape from must be [H, W, 4]")
+            H, W = int(shape_or_image.shape[0]), int(shape_or_image.shape[1])
+        else:
+            H, W = (int(v) for v in shape_or_image)
+        if capacity_tiles is None:
+            capacity_tiles = _journal.tile_count(H, W)
+        return _delta.DeltaTracker(self, H, W, capacity_tiles)
+
     def stroke_info(self):
         """Of the last paint_stroke: its stamps, its groups and the UNet evaluations of all groups (dtp_last_stroke_info)."""
         a, b, e = C.c_int(), C.c_int(), C.c_int()

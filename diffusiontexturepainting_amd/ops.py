@@ -670,3 +670,32 @@ def journal_window_tiles(H, W, R, x, y, wrap=False):
     wrap a wrapped piece of it.  -> list of int, tile t = (row / 16) * ceil(W / 16) + col / 16."""
     from . import journal
     return journal.window_tiles(H, W, R, x, y, wrap=wrap)
+
+
+def delta_layout(H, W, capacity_tiles=None):
+    """dtp_delta_layout (host only, needs no GPU): what a changed-tile tracker of an H x W image with `capacity_tiles` (default: its tile
+    count) owns -> dict(tiles_x, tiles_y, n_tiles, n_groups, capacity, and the byte sizes shadow_bytes, stale_bytes, flag_bytes,
+    group_bytes, ids_bytes, tiles_bytes, counts_bytes, host_ids_offset, host_tiles_offset, host_bytes)."""
+    from . import journal
+    if capacity_tiles is None:
+        capacity_tiles = journal.tile_count(H, W)
+    lay = _lib.DeltaSizes()
+    check(_lib.load().dtp_delta_layout(int(H), int(W), int(capacity_tiles), C.byref(lay)), "dtp_delta_layout")
+    return {name: int(getattr(lay, name)) for name, _ in _lib.DeltaSizes._fields_}
+
+
+def delta_scan(tracker, image):
+    """dtp_delta_scan of `image` (u8 [H,W,4]) with a delta.DeltaTracker on the current stream, and the tracker's state afterwards, for the
+    kernel tests -> (ids i32 [emitted], tiles u8 [emitted,16,16,4], counts [emitted, remaining], shadow u8 [H,W,4], stale u8 [n_tiles]),
+    CPU tensors; ids and tiles are copies of the first `emitted` device slots."""
+    from . import journal
+    lib = _lib.load()
+    m = tracker._model
+    check(lib.dtp_delta_scan(m._h, tracker.handle, ptr(image), image.shape[0], image.shape[1], _stream()), "dtp_delta_scan")
+    ids, tiles, counts = tracker._device_views()
+    counts = counts.cpu().tolist()
+    shadow = torch.empty(tracker.H, tracker.W, 4, dtype=torch.uint8)
+    stale = torch.empty(journal.tile_count(tracker.H, tracker.W), dtype=torch.uint8)
+    check(lib.dtp_op_delta_state(tracker.handle, ptr(shadow), ptr(stale), _stream()), "dtp_op_delta_state")
+    return ids[:counts[0]].cpu(), tiles[:counts[0]].cpu(), counts, shadow, stale
+

@@ -26,7 +26,7 @@ extern "C" {
  * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
  * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) and the undo / redo journal
  * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) and the
- * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) are additions; nothing that existed at
+ * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state) are additions; nothing that existed at
  * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -582,6 +582,71 @@ int dtp_journal_info(dtp_journal* j, int* records, int* cursor, int* open, uint6
 int dtp_journal_record_info(dtp_journal* j, int record, uint64_t* start, uint64_t* end, int* restorable);
 int dtp_op_journal_tiles(dtp_journal* j, int record, int* tiles_host, int max, int* n);
 int dtp_journal_window_tiles(int H, int W, int R, int wrap, int x, int y, int* tiles, int max, int* n);
+
+/* ---------------------------------------------------------------- changed tiles of an image
+ * What a client in another process needs to keep a mirror of a painted texture or of a rendered frame current.  The
+ * reference pushes the whole texture to the viewport after every stamp (kit_app/.../python/manager.py:349-354); here the device finds the
+ * 16 x 16-texel tiles whose bytes changed since the client last got them, by comparison against a shadow copy the tracker owns, and
+ * only those tiles cross to the host.  Comparison catches every writer -- strokes, the bleed pass, undo and redo, a torch write, a
+ * re-rendered frame -- without any of them knowing, and a change that was changed back costs nothing.  Exact bytes; no tolerance.
+ *
+ * Image.  Any contiguous u8 [H][W][4] image on the handle's device, 1 <= H, W <= 16384, 4-byte aligned (no more is assumed).  The tracker
+ * is made for a shape, not for a pointer: every scan names its image.
+ *
+ * Tiles.  The journal's tiles and numbers: tile t = (i / 16) * ceil(W / 16) + (j / 16); a payload is 1 KiB = 256 RGBA texels, row-major,
+ * 64 bytes per row.
+ *
+ * dtp_delta_create makes a tracker for (ctx, H, W, capacity_tiles >= 1) and allocates all it will ever need, as dtp_delta_layout lists
+ * it: a shadow image (H W 4 bytes), one stale mark per tile, one flag per tile and a count and a base per group of 64 tiles, the device
+ * outputs ids i32 [capacity], tiles u8 [capacity][1024] and counts i32 [2], and one pinned host block (16 bytes that receive counts,
+ * then ids, then tiles, at host_ids_offset and host_tiles_offset; dtp_delta_host gives the two addresses).  A tracker belongs to its
+ * handle: dtp_destroy frees the trackers still alive; dtp_delta_destroy(NULL) is a no-op.  A pointer that is not a live tracker is
+ * DTP_ERR_ARG in every call here: refused, not followed.
+ *
+ * State.  A new tracker has every tile stale.  dtp_delta_reset marks every tile stale again with one memset in stream order: for a
+ * client that reconnected with an empty mirror.
+ *
+ * dtp_delta_scan(ctx, tracker, image, H, W, s).  A tile is CHANGED iff it is stale or any byte of it inside the image differs from the
+ * shadow.  With total = the number of changed tiles and emitted = min(total, capacity), the scan writes the first `emitted` changed tiles
+ * in ascending tile order: ids[k] = the tile, tiles[k] = its 1 KiB with the texels outside the image zero, counts = {emitted, total -
+ * emitted}.  Slots from `emitted` on keep what they held.  For the emitted tiles, and only for those, the shadow takes the image's
+ * bytes and the stale mark is cleared: a capped scan loses nothing and the next one goes on with the next tiles in order; a key frame is
+ * the same call on a fresh (or reset) tracker.  The output does not depend on scheduling: a slot is the tile's rank in ascending order,
+ * never claimed with an atomic counter.  It only ENQUEUES on `s`, three launches (flag the tiles and count per group of 64; one
+ * workgroup scans the group counts and writes counts; gather), none of which waits for another workgroup.  Texels of an edge tile that
+ * lie outside the image are neither read nor compared.  Scans of one tracker must be ordered with each other (one stream, or events).
+ *
+ * dtp_delta_device gives the device addresses of ids, tiles and counts, valid for the tracker's life, holding what the last scan wrote
+ * once that scan has run.  dtp_delta_host gives the addresses of ids and tiles inside the pinned block.
+ *
+ * dtp_delta_pull is the scan and the read-back: it enqueues the scan, copies the 8 bytes of counts into the pinned block and waits for
+ * `s`, then copies ids[:count] into host_ids and tiles[:count] into host_tiles (host memory with room for max_tiles tiles; the pinned
+ * block's addresses are the fast choice) and waits again; *count = emitted, *remaining = total - emitted.  Nothing is copied when count
+ * is 0.  max_tiles below the tracker's capacity is refused before any device work.
+ *
+ * Refusals, every one before the first device call and with every output left alone, DTP_ERR_ARG: a NULL pointer; H or W outside
+ * 1..16384; capacity_tiles < 1; a tracker that is not alive, or that belongs to another handle; an image whose H, W are not the
+ * tracker's, or that is not 4-byte aligned; max_tiles below the capacity.
+ *
+ * dtp_delta_layout (host only): the tiles in x and y, their number, the groups of 64, and the byte size of every buffer above. */
+typedef struct dtp_delta dtp_delta;
+typedef struct {
+  int tiles_x, tiles_y, n_tiles, n_groups, capacity;
+  uint64_t shadow_bytes, stale_bytes, flag_bytes, group_bytes, ids_bytes, tiles_bytes, counts_bytes;
+  uint64_t host_ids_offset, host_tiles_offset, host_bytes;
+} dtp_delta_sizes;
+int dtp_delta_layout(int H, int W, int capacity_tiles, dtp_delta_sizes* out);
+int dtp_delta_create(dtp_ctx* ctx, int H, int W, int capacity_tiles, dtp_delta** out);
+int dtp_delta_destroy(dtp_delta* d);
+int dtp_delta_reset(dtp_delta* d, dtp_stream s);
+int dtp_delta_scan(dtp_ctx* ctx, dtp_delta* d, const uint8_t* image, int H, int W, dtp_stream s);
+int dtp_delta_device(dtp_delta* d, int** ids, uint8_t** tiles, int** counts);
+int dtp_delta_host(dtp_delta* d, int** ids, uint8_t** tiles);
+int dtp_delta_pull(dtp_ctx* ctx, dtp_delta* d, const uint8_t* image, int H, int W, dtp_stream s, int* host_ids, uint8_t* host_tiles,
+                   int max_tiles, int* count, int* remaining);
+/* the tracker's shadow and stale marks copied to host memory (u8 [H][W][4] and u8 [n_tiles]; either may be NULL), for the kernel
+ * tests: waits for `s` */
+int dtp_op_delta_state(dtp_delta* d, uint8_t* shadow_host, uint8_t* stale_host, dtp_stream s);
 
 /* Host-only: the DDIM tables dtp_stamp uses for `steps` inference steps -- timesteps[steps] (descending,
  * +1 offset), alphas_cumprod gathered at those timesteps, and final_alpha_cumprod
