@@ -228,6 +228,8 @@ SYMBOLS = {
     "dtp_mip_layout": (_i, [_i, _i, C.POINTER(MipLevels)]),
     "dtp_texture_mips": (_i, [_vp, _i, _i, _vp, C.c_uint64, _vp]),
     "dtp_mesh_view_mips": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _vp, _vp]),
+    "dtp_mesh_view_clip": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _vp, _vp, _vp, _vp, _vp]),
+    "dtp_op_mesh_view_clip": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

@@ -8,7 +8,10 @@
 // segment alone -- plus the short list of faces too large to bin.  No capacity to choose, no overflow, no read-back.  The kernels read
 // the mesh's vertices, faces and UVs and write buffers of their own: nothing a stroke or a pick in flight uses.  Plain HIP: vector loads,
 // stores and atomics only.  dtp_mesh_view_mips is the same frame with a trilinear sample from the texture's mip pyramid
-// (mips.hip): the raster kernel is a template on the filter, and its unfiltered instantiation is dtp_mesh_view's code.
+// (mips.hip): the raster kernel is a template on the filter, and its unfiltered instantiation is dtp_mesh_view's code.  dtp_mesh_view_clip
+//  also draws the faces that CROSS the near plane, in homogeneous form: per face the cross products of its camera-space
+// vertices, per pixel their edge functions against the pixel's ray, which give the same q_k and d the rest of the raster kernel consumes.
+// It is a second template parameter; the instantiations without it are the code they were.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stddef.h>
@@ -22,9 +25,12 @@
 namespace {
 
 enum { VF_SMALL = 1, VF_LARGE = 2 };  // drawn, and binned / on the list every tile streams; 0: not drawn
+enum { VF_CROSS = 4 };                // with VF_LARGE: a face across the near plane, whose record holds the homogeneous form
+constexpr int CROSS_SLOT = 1 << 30;   // a staged slot of such a face: this bit of s_face (a face index is below 2^20)
 
 // what a view's projection leaves per face, 64 bytes: screen position snapped to 1/256 pixel, 1 / depth per vertex, the unit normal's z,
-// the pixel ranges x0 | x1 << 16, y0 | y1 << 16
+// the pixel ranges x0 | x1 << 16, y0 | y1 << 16.  A face across the near plane (VF_CROSS): X, Y, iw hold the bits of sign(D) n_0,
+// sign(D) n_1, sign(D) n_2 (three floats each) and pad[0] those of 1 / |D|
 struct ViewRec { int X[3], Y[3]; float iw[3], nzu; int flags, px, py, pad[3]; };
 static_assert(sizeof(ViewRec) == 64, "one record per 64-byte line");
 // the counters of a frame: count and n_large are zeroed on the stream before every projection
@@ -41,6 +47,12 @@ struct ViewShade { int shade; float ambient, unpainted[3]; unsigned int backgrou
 // them out, and the map of lod (or null)
 template <int FILTER> struct ViewFilter {};
 template <> struct ViewFilter<1> { const unsigned int* mips; float* lod; int levels; };
+// and of the near-plane clip: what the ray of a pixel and the clip itself need of the camera
+template <int CLIP> struct ViewClip {};
+template <> struct ViewClip<1> { float fx, fy, near; };
+// the ray of the centre of pixel column j (row i) of a W (H) pixel frame, without its z = -1: ndc / f
+__device__ __forceinline__ float ray_x(int j, int W, float fx) { return ((float)(2 * j + 1) / (float)W - 1.0f) / fx; }
+__device__ __forceinline__ float ray_y(int i, int H, float fy) { return (1.0f - (float)(2 * i + 1) / (float)H) / fy; }
 
 // counter[key] += 1 for every lane of the wave whose key is >= 0, with ONE atomic per distinct key: the lanes that share a key elect a
 // leader, which adds their number; -> the lane's slot, the counter's value before its own add.  Neighbouring faces of a mesh mostly share
@@ -70,24 +82,57 @@ __device__ __forceinline__ int bin_key(int e, int bx0, int bx1, int by0, int by1
 
 // One thread per face: camera space, the unit normal's z, the perspective division, the snapped screen position; a face that is drawn
 // (in front of the near plane, not culled, with an area and a pixel centre in its box) is counted into its bins or appended to `large`.
+// clip: a face with vertices on both sides of the near plane is drawn too: its record is the homogeneous form, its pixel range the box
+// of view_clip_box (the whole frame when not binned), and it goes on `large`.  clip 0 writes what the kernel always wrote.
 __global__ __launch_bounds__(256) void view_project_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int F, dtp_view_cam cam,
                                                            int H, int W, int cull, int flip, int binned, int nbx, ViewRec* __restrict__ rec,
-                                                           int* __restrict__ large, ViewState* st) {
+                                                           int* __restrict__ large, ViewState* st, int clip) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   float c[3][3];
-  bool draw = f < F;
+  bool draw = f < F, finite = f < F;
+  int ahead = 0;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float* v = verts + (size_t)3 * (draw ? faces[(size_t)3 * f + k] : 0);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       c[k][r] = ((cam.m[4 * r] * v[0] + cam.m[4 * r + 1] * v[1]) + cam.m[4 * r + 2] * v[2]) + cam.m[4 * r + 3];
-      draw = draw && isfinite(c[k][r]);
+      finite = finite && isfinite(c[k][r]);
     }
-    draw = draw && c[k][2] <= -cam.near;
+    ahead += c[k][2] <= -cam.near ? 1 : 0;
   }
+  draw = finite && ahead == 3;
+  const bool cross = clip && finite && ahead > 0 && ahead < 3;
   ViewRec r;
   memset(&r, 0, sizeof r);
+  if (cross) {
+    float n[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float* a = c[(k + 1) % 3];
+      const float* b = c[(k + 2) % 3];
+      n[k][0] = a[1] * b[2] - a[2] * b[1]; n[k][1] = a[2] * b[0] - a[0] * b[2]; n[k][2] = a[0] * b[1] - a[1] * b[0];
+    }
+    const float D = (c[0][0] * n[0][0] + c[0][1] * n[0][1]) + c[0][2] * n[0][2];
+    const bool front = (D < 0.f) != (flip != 0);
+    int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
+    if (isfinite(D) && D != 0.f && (front || !cull) && (view_clip_box(c, cam.fx, cam.fy, cam.near, H, W, x0, x1, y0, y1) || !binned)) {
+      if (!binned) { x0 = 0; x1 = W - 1; y0 = 0; y1 = H - 1; }
+      const float e1x = c[1][0] - c[0][0], e1y = c[1][1] - c[0][1], e1z = c[1][2] - c[0][2];
+      const float e2x = c[2][0] - c[0][0], e2y = c[2][1] - c[0][1], e2z = c[2][2] - c[0][2];
+      const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+      r.nzu = nz / sqrtf((nx * nx + ny * ny) + nz * nz);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        r.X[k] = __float_as_int(D < 0.f ? -n[0][k] : n[0][k]);
+        r.Y[k] = __float_as_int(D < 0.f ? -n[1][k] : n[1][k]);
+        r.iw[k] = D < 0.f ? -n[2][k] : n[2][k];
+      }
+      r.pad[0] = __float_as_int(1.0f / fabsf(D));
+      r.px = x0 | (x1 << 16); r.py = y0 | (y1 << 16);
+      r.flags = VF_LARGE | VF_CROSS;
+    }
+  }
   if (draw) {
     const float e1x = c[1][0] - c[0][0], e1y = c[1][1] - c[0][1], e1z = c[1][2] - c[0][2];
     const float e2x = c[2][0] - c[0][0], e2y = c[2][1] - c[0][1], e2z = c[2][2] - c[0][2];
@@ -113,8 +158,8 @@ __global__ __launch_bounds__(256) void view_project_kernel(const float* __restri
   if (f < F) rec[f] = r;
 #pragma unroll
   for (int e = 0; e < 4; ++e) wave_add(st->count, r.flags == VF_SMALL ? bin_key(e, bx0, bx1, by0, by1, nbx) : -1);
-  const int at = wave_add(&st->n_large, r.flags == VF_LARGE ? 0 : -1);
-  if (r.flags == VF_LARGE && at < F) large[at] = f;  // (always, unless two views of one mesh race)
+  const int at = wave_add(&st->n_large, (r.flags & VF_LARGE) ? 0 : -1);
+  if ((r.flags & VF_LARGE) && at < F) large[at] = f;  // (always, unless two views of one mesh race)
 }
 
 // One workgroup: the exclusive prefix of the bins' counts -> where each bin's segment starts, and its cursor for the fill.
@@ -171,15 +216,18 @@ __device__ __forceinline__ void view_sample(const unsigned int* __restrict__ tex
 // time; a face whose pixel range misses the tile is dropped on the way in.  Winner: the largest (inverse depth d, -face index) among
 // the faces that cover the centre.  Then the perspective-correct UV, the sample, the shade and the stores.  FILTER 1: the winner face
 // alone is evaluated again at the two neighbouring centres, the footprint of the pixel in the texture picks a level of the pyramid by
-// compares against powers of four (walking the layout on the way), and the sample is blended from that level and the next.
-template <int FILTER>
+// compares against powers of four (walking the layout on the way), and the sample is blended from that level and the next.  CLIP 1: a
+// staged slot may hold a face across the near plane (CROSS_SLOT in s_face): its nine record words travel through s_X, s_Y, s_iw as they
+// are, 1 / |D| beside them, and the pixel tests the edge functions of its ray instead of cover(); the winner update is the same.
+template <int FILTER, int CLIP>
 __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restrict__ rec, const int* __restrict__ items, const int* __restrict__ large,
                                                           const ViewState* st, int F, int nbx, const float* __restrict__ uvs,
                                                           const unsigned int* __restrict__ tex, int TH, int TW, int H, int W, ViewShade sh,
                                                           unsigned int* __restrict__ image, int* __restrict__ face_idx, float* __restrict__ depth,
-                                                          ViewFilter<FILTER> fl) {
+                                                          ViewFilter<FILTER> fl, ViewClip<CLIP> cl) {
   __shared__ int s_n, s_face[CHUNK], s_X[CHUNK][3], s_Y[CHUNK][3];
   __shared__ float s_iw[CHUNK][3];
+  __shared__ float s_inv[CLIP ? CHUNK : 1];  // (CLIP 0 never names it: no LDS)
   const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
   const int col = col0 + (t & 15), row = row0 + (t >> 4);
   const bool live = col < W && row < H;
@@ -190,6 +238,8 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   const int total = n_seg + min(max(st->n_large, 0), F);
   int best = -1;
   float best_d = 0.f, bq[3] = {0.f, 0.f, 0.f};
+  float gx = 0.f, gy = 0.f;
+  if constexpr (CLIP != 0) { gx = ray_x(col, W, cl.fx); gy = ray_y(row, H, cl.fy); }
   for (int base = 0; base < total; base += CHUNK) {
     if (t == 0) s_n = 0;
     __syncthreads();
@@ -199,7 +249,12 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
         const ViewRec& r = rec[f];
         if (ranges_meet(r.px, col0, col0 + 15) && ranges_meet(r.py, row0, row0 + 15)) {
           const int slot = atomicAdd(&s_n, 1);
-          s_face[slot] = f;
+          if constexpr (CLIP != 0) {
+            s_face[slot] = (r.flags & VF_CROSS) ? f | CROSS_SLOT : f;
+            s_inv[slot] = __int_as_float(r.pad[0]);
+          } else {
+            s_face[slot] = f;
+          }
 #pragma unroll
           for (int k = 0; k < 3; ++k) { s_X[slot][k] = r.X[k]; s_Y[slot][k] = r.Y[k]; s_iw[slot][k] = r.iw[k]; }
         }
@@ -209,12 +264,34 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
     const int n = s_n;
     if (live)
       for (int i = 0; i < n; ++i) {
-        float w[3];
-        if (!cover(s_X[i], s_Y[i], px, py, w)) continue;
-        const float q0 = w[0] * s_iw[i][0], q1 = w[1] * s_iw[i][1], q2 = w[2] * s_iw[i][2];
-        const float d = (q0 + q1) + q2;
-        const int f = s_face[i];
-        if (best < 0 || d > best_d || (d == best_d && f < best)) { best = f; best_d = d; bq[0] = q0; bq[1] = q1; bq[2] = q2; }
+        if constexpr (CLIP == 0) {
+          float w[3];
+          if (!cover(s_X[i], s_Y[i], px, py, w)) continue;
+          const float q0 = w[0] * s_iw[i][0], q1 = w[1] * s_iw[i][1], q2 = w[2] * s_iw[i][2];
+          const float d = (q0 + q1) + q2;
+          const int f = s_face[i];
+          if (best < 0 || d > best_d || (d == best_d && f < best)) { best = f; best_d = d; bq[0] = q0; bq[1] = q1; bq[2] = q2; }
+        } else {
+          float q0, q1, q2, d;
+          int f = s_face[i];
+          if (f & CROSS_SLOT) {
+            f ^= CROSS_SLOT;
+            const float E0 = (__int_as_float(s_X[i][0]) * gx + __int_as_float(s_X[i][1]) * gy) - __int_as_float(s_X[i][2]);
+            const float E1 = (__int_as_float(s_Y[i][0]) * gx + __int_as_float(s_Y[i][1]) * gy) - __int_as_float(s_Y[i][2]);
+            const float E2 = (s_iw[i][0] * gx + s_iw[i][1] * gy) - s_iw[i][2];
+            if (!(E0 >= 0.f && E1 >= 0.f && E2 >= 0.f)) continue;
+            const float inv = s_inv[i];
+            q0 = E0 * inv; q1 = E1 * inv; q2 = E2 * inv;
+            d = (q0 + q1) + q2;
+            if (!(isfinite(d) && d > 0.f && 1.0f / d >= cl.near)) continue;  // the plane's horizon, and the clip itself
+          } else {
+            float w[3];
+            if (!cover(s_X[i], s_Y[i], px, py, w)) continue;
+            q0 = w[0] * s_iw[i][0]; q1 = w[1] * s_iw[i][1]; q2 = w[2] * s_iw[i][2];
+            d = (q0 + q1) + q2;
+          }
+          if (best < 0 || d > best_d || (d == best_d && f < best)) { best = f; best_d = d; bq[0] = q0; bq[1] = q1; bq[2] = q2; }
+        }
       }
     __syncthreads();
   }
@@ -230,10 +307,28 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
       view_sample(tex, TH, TW, u, v, tc);
     } else {
       const ViewRec& r = rec[best];
-      float wx[3], wy[3];
-      weights_at(r.X, r.Y, px + 256, py, wx);
-      weights_at(r.X, r.Y, px, py + 256, wy);
-      const float qx[3] = {wx[0] * r.iw[0], wx[1] * r.iw[1], wx[2] * r.iw[2]}, qy[3] = {wy[0] * r.iw[0], wy[1] * r.iw[1], wy[2] * r.iw[2]};
+      float qx[3], qy[3];
+      bool crossing = false;
+      if constexpr (CLIP != 0) crossing = (r.flags & VF_CROSS) != 0;
+      if (crossing) {
+        if constexpr (CLIP != 0) {  // the same E_k, q_k at the two neighbouring centres, no inside test
+          const float gx1 = ray_x(col + 1, W, cl.fx), gy1 = ray_y(row + 1, H, cl.fy), inv = __int_as_float(r.pad[0]);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const float nx = k == 0 ? __int_as_float(r.X[0]) : k == 1 ? __int_as_float(r.Y[0]) : r.iw[0];
+            const float ny = k == 0 ? __int_as_float(r.X[1]) : k == 1 ? __int_as_float(r.Y[1]) : r.iw[1];
+            const float nz = k == 0 ? __int_as_float(r.X[2]) : k == 1 ? __int_as_float(r.Y[2]) : r.iw[2];
+            qx[k] = ((nx * gx1 + ny * gy) - nz) * inv;
+            qy[k] = ((nx * gx + ny * gy1) - nz) * inv;
+          }
+        }
+      } else {
+        float wx[3], wy[3];
+        weights_at(r.X, r.Y, px + 256, py, wx);
+        weights_at(r.X, r.Y, px, py + 256, wy);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { qx[k] = wx[k] * r.iw[k]; qy[k] = wy[k] * r.iw[k]; }
+      }
       const float dx = (qx[0] + qx[1]) + qx[2], dy = (qy[0] + qy[1]) + qy[2];
       float rho2 = INFINITY;  // beyond the horizon, or a footprint that is not finite: the last level
       if (isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f) {
@@ -297,9 +392,11 @@ int view_reserve(const MeshGeom& g) {
 }
 
 // every check, then zero the counters -> project -> scan -> fill -> raster on s; nothing waits
-// filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null)
+// filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null); clip: the faces across the near
+// plane are drawn too
 int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* o,
-             uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s, int filter = 0, const uint8_t* mips = nullptr, float* lod = nullptr) {
+             uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s, int filter = 0, const uint8_t* mips = nullptr, float* lod = nullptr,
+             int clip = 0) {
   if (!mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
   if (const char* why = view_check(texture, TH, TW, cam, H, W, o, image, face_idx, depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
   dtp_mip_levels lay;
@@ -321,19 +418,22 @@ int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, in
   const int nbx = view_bins_across(W), blocks = (g.F + 255) / 256;
   HIP_CHECK(hipMemsetAsync(b->st, 0, offsetof(ViewState, offset), s));
   hipLaunchKernelGGL(view_project_kernel, dim3(blocks), dim3(256), 0, s, g.verts, g.faces, g.F, *cam, H, W, o->cull, o->flip_normals, binned ? 1 : 0, nbx,
-                     b->rec, b->large, b->st);
+                     b->rec, b->large, b->st, clip ? 1 : 0);
   hipLaunchKernelGGL(view_scan_kernel, dim3(1), dim3(256), 0, s, b->st);
   hipLaunchKernelGGL(view_fill_kernel, dim3(blocks), dim3(256), 0, s, b->rec, g.F, nbx, b->items, b->st);
   const dim3 tiles((W + 15) / 16, (H + 15) / 16);
-  if (filter) {
-    ViewFilter<1> fl;
-    fl.mips = (const unsigned int*)mips; fl.lod = lod; fl.levels = lay.levels;
-    hipLaunchKernelGGL(view_raster_kernel<1>, tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs,
-                       (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, fl);
-  } else {
-    hipLaunchKernelGGL(view_raster_kernel<0>, tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs,
-                       (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, ViewFilter<0>());
-  }
+  ViewFilter<1> fl;
+  fl.mips = (const unsigned int*)mips; fl.lod = lod; fl.levels = filter ? lay.levels : 1;
+  ViewClip<1> cl;
+  cl.fx = cam->fx; cl.fy = cam->fy; cl.near = cam->near;
+#define RASTER(FILTER, CLIP, fl, cl)                                                                                                   \
+  hipLaunchKernelGGL((view_raster_kernel<FILTER, CLIP>), tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs, \
+                     (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, fl, cl)
+  if (filter && clip) RASTER(1, 1, fl, cl);
+  else if (filter) RASTER(1, 0, fl, ViewClip<0>());
+  else if (clip) RASTER(0, 1, ViewFilter<0>(), cl);
+  else RASTER(0, 0, ViewFilter<0>(), ViewClip<0>());
+#undef RASTER
   if (hipGetLastError() != hipSuccess) { dtp_set_error("%s: a kernel launch failed", who); return DTP_ERR_HIP; }
   return DTP_OK;
 }
@@ -379,6 +479,19 @@ int dtp_mesh_view_mips(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, c
 int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
                      uint8_t* image, int* face_idx, float* depth, int binned, dtp_stream s) {
   return view_run("dtp_op_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s);
+}
+
+int dtp_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                       const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s) {
+  return dtp_op_mesh_view_clip(mesh, texture, TH, TW, mips, cam, H, W, opts, filter, image, face_idx, depth, lod, 1, s);
+}
+
+int dtp_op_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                          const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, int binned, dtp_stream s) {
+  const char* who = binned == 1 ? "dtp_mesh_view_clip" : "dtp_op_mesh_view_clip";
+  if (filter != 0 && filter != 1) { dtp_set_error("%s: filter is 0 (bilinear) or 1 (trilinear)", who); return DTP_ERR_ARG; }
+  if (!filter && (mips || lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
+  return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, filter, mips, lod, 1);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // The host-only arithmetic of the view of a textured mesh (include/dtp.h "a view of a textured mesh": dtp_view_camera, dtp_view_rays,
 // dtp_mesh_view): the perspective camera and the rays of its pixels in double, rounded to fp32 once; every argument check
-// of a view but the look-up of the mesh; the bins a face's pixel range meets.  No device call, so the stand-alone sanitizer program
-// (tools/view_host_check.cpp) drives it directly, built by a plain C++ compiler.
+// of a view but the look-up of the mesh; the bins a face's pixel range meets; the pixel range of a face that crosses the near plane.  No
+// device call, so the stand-alone sanitizer programs (tools/view_host_check.cpp, tools/view_clip_host_check.cpp) drive it directly, built by
+// a plain C++ compiler.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -29,6 +30,50 @@ VIEW_HD inline bool view_bins(int px, int py, int& bx0, int& bx1, int& by0, int&
   return bx1 - bx0 <= 1 && by1 - by0 <= 1;
 }
 inline int view_bins_across(int n) { return (n + VIEW_BIN - 1) >> VIEW_BIN_SHIFT; }
+
+// The pixel ranges of a face that CROSSES the near plane (include/dtp.h "a view clipped at the near plane"; c: its camera-space vertices,
+// finite, at least one with z <= -near and one nearer).  The face is rasterised in homogeneous form and never cut, so the ranges are used
+// for the reject and the bins alone and only have to be conservative: the box of the projections of the polygon cut at z = -near (its
+// vertices in front, and where its edges meet the plane: up to four points, in fp32), grown by a pixel and a half and by a bound on the
+// rounding of the cut points, which are differences of coordinates divided by near.  true: [x0, x1] x [y0, y1], inclusive pixel indices
+// clamped to the frame; the whole frame where an intermediate is not finite.  false: the box misses the frame (nothing written).
+VIEW_HD inline bool view_clip_box(const float c[3][3], float fx, float fy, float near, int H, int W, int& x0, int& x1, int& y0, int& y1) {
+#pragma clang fp contract(off)
+  const float hw = 0.5f * (float)W, hh = 0.5f * (float)H, inear = 1.0f / near, big = 3.4028235e38f;
+  float lox = big, hix = -big, loy = big, hiy = -big, slack = 0.f;
+  bool finite = true;
+  for (int k = 0; k < 3; ++k) {
+    const float* a = c[k];
+    const float* b = c[(k + 1) % 3];
+    const bool a_in = a[2] <= -near, b_in = b[2] <= -near;
+    for (int cut = 0; cut < 2; ++cut) {
+      if (cut == 0 ? !a_in : a_in == b_in) continue;
+      float nx, ny, err = 0.f;
+      if (cut == 0) {
+        const float iw = 1.0f / (0.0f - a[2]);
+        nx = (a[0] * fx) * iw; ny = (a[1] * fy) * iw;
+      } else {
+        const float t = ((0.0f - near) - a[2]) / (b[2] - a[2]);
+        nx = ((a[0] + t * (b[0] - a[0])) * fx) * inear; ny = ((a[1] + t * (b[1] - a[1])) * fy) * inear;
+        err = fmaxf((((fabsf(a[0]) + fabsf(b[0])) * fx) * inear) * hw, (((fabsf(a[1]) + fabsf(b[1])) * fy) * inear) * hh) * 1e-6f;
+      }
+      const float sx = (nx + 1.0f) * hw, sy = (1.0f - ny) * hh;
+      finite = finite && fabsf(sx) <= big && fabsf(sy) <= big && fabsf(err) <= big;  // (false for a NaN)
+      lox = fminf(lox, sx); hix = fmaxf(hix, sx); loy = fminf(loy, sy); hiy = fmaxf(hiy, sy);
+      slack = fmaxf(slack, err);
+    }
+  }
+  const float grow = 1.5f + slack;
+  const float ax = floorf(lox - grow), bx = ceilf(hix + grow), ay = floorf(loy - grow), by = ceilf(hiy + grow);
+  if (!finite || !(fabsf(ax) <= big && fabsf(bx) <= big && fabsf(ay) <= big && fabsf(by) <= big)) {
+    x0 = 0; x1 = W - 1; y0 = 0; y1 = H - 1;
+    return true;
+  }
+  if (bx < 0.f || ax > (float)(W - 1) || by < 0.f || ay > (float)(H - 1)) return false;
+  x0 = (int)fmaxf(ax, 0.f); x1 = (int)fminf(bx, (float)(W - 1));
+  y0 = (int)fmaxf(ay, 0.f); y1 = (int)fminf(by, (float)(H - 1));
+  return true;
+}
 
 // nullptr, or what is wrong with a camera that was not made by dtp_view_camera
 inline const char* view_cam_check(const dtp_view_cam* c) {

@@ -528,14 +528,14 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def render_view(self, mesh, texture, camera, size=None, cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128),
                     background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False, filter="bilinear", mips=None,
-                    want_lod=False):
+                    want_lod=False, clip_near=False):
         """A perspective view of the whole painted mesh (dtp_mesh_view; in the Kit app the viewport is Omniverse RTX):
         `mesh` from load_mesh, `texture` uint8 [TH, TW, 4] on the model's device, `camera` from mesh.view_camera, size = (H, W) (default
         the camera's; each side 1..4096).  -> the frame, uint8 [H, W, 4] on the device (RGB the texture under its alpha over `unpainted`,
         shaded by ambient + (1 - ambient) |n_z| unless shade is off; alpha 255; `background` where no face is), and with want_face_idx /
         want_depth also int32 [H, W] (-1: no face) and float32 [H, W] (the distance along the view direction; 0: no face), as a tuple in
         that order.  cull: front faces only; flip_normals: a left-handed mesh.  A face with any vertex nearer than the camera's near
-        plane is dropped whole, not clipped; one sample per pixel, no mips: a preview that aliases under minification.  out: a frame to
+        plane is dropped whole, not clipped (unless clip_near, below); one sample per pixel, no mips: a preview that aliases under minification.  out: a frame to
         write into.  The call only enqueues, on self.view_stream.  live=False: that stream first waits for everything queued on the
         stroke's stream, so the frame shows all that was painted so far and is exact.  live=True: it waits for nothing and answers while
         a queued stroke is still painting; each texel is then either old or new, and the frame may catch a stamp halfway.  The
@@ -545,7 +545,11 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         magnified frame is the bilinear one byte for byte.  mips: the pyramid from build_mips(texture) (complete before a live=True
         call, which waits for nothing); None: built here on the view's stream, after the same waits the frame makes, into a buffer the
         model keeps per texture shape -- so a live pyramid may catch a stamp halfway, as the frame may.  want_lod: also the level
-        each pixel took, float32 [H, W] (0 where no face is), last in the tuple."""
+        each pixel took, float32 [H, W] (0 where no face is), last in the tuple.
+        clip_near=True (dtp_mesh_view_clip): a face ACROSS the near plane is drawn down to the plane instead of dropped
+        -- the floor under the camera, the walls of a room painted from inside -- with either filter; no pixel then has a depth below
+        the camera's near, and the face a frame shows at a pixel is the face mesh.view_rays' ray of that pixel hits.  Faces wholly in
+        front keep their exact coverage, and a frame without a crossing face is the same bytes as without the keyword."""
         if filter not in ("bilinear", "trilinear"):
             raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
         trilinear = filter == "trilinear"
@@ -591,9 +595,13 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             self.view_stream.wait_event(done)
             self.view_stream.wait_stream(cur)
         vs = C.c_void_p(self.view_stream.cuda_stream)
-        if trilinear:
-            if build:
-                check(self._lib.dtp_texture_mips(ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), need, vs), "dtp_texture_mips")
+        if trilinear and build:
+            check(self._lib.dtp_texture_mips(ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), need, vs), "dtp_texture_mips")
+        if clip_near:
+            check(self._lib.dtp_mesh_view_clip(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips) if trilinear else None,
+                                               C.byref(cam), H, W, C.byref(opts), int(trilinear), ptr(out), ptr(face_idx), ptr(depth), ptr(lod), vs),
+                  "dtp_mesh_view_clip")
+        elif trilinear:
             check(self._lib.dtp_mesh_view_mips(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), C.byref(cam), H, W,
                                                C.byref(opts), ptr(out), ptr(face_idx), ptr(depth), ptr(lod), vs), "dtp_mesh_view_mips")
         else:

@@ -125,7 +125,9 @@ def view_camera(eye, at, up, fov_y=45.0, size=(720, 1280), near=0.01):
 def view_rays(camera, pixels, size=None):
     """The rays of pixel positions of a view (dtp_view_rays: host only): pixels [n, 2] (or [2]) as (x, y), the centre of pixel (row i,
     column j) being (j + 0.5, i + 0.5); size = (H, W), default the camera's.  -> (origins f32 [n, 3], directions f32 [n, 3]) on the
-    host, ready for model.pick and paint_mesh_path: the face a frame shows at a pixel is the face its ray hits."""
+    host, ready for model.pick and paint_mesh_path: the face a frame shows at a pixel is the face its ray hits.  That holds for the
+    faces wholly in front of the camera's near plane; a face across it is shown only by render_view(clip_near=True), and with that
+    keyword it holds for those too (a ray also hits what no frame shows: faces nearer than the plane)."""
     H, W = camera.size if size is None else size
     xy = torch.as_tensor(pixels).detach().to("cpu", torch.float32).reshape(-1, 2).contiguous()
     n = xy.shape[0]

@@ -625,22 +625,36 @@ def mesh_pick(mesh, origins, directions):
     return _mesh.hits_dict(rec)
 
 
-def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True, want_depth=True, **opts):
+def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True, want_depth=True, clip_near=False, filter="bilinear", mips=None,
+              want_lod=False, **opts):
     """dtp_op_mesh_view: the frame of MI355ConditionalInpainter.render_view on the current stream -> (image u8 [H,W,4], face_idx i32
     [H,W] or None, depth f32 [H,W] or None).  binned=False puts every drawn face on the list that every tile streams (the arm a
-    measurement compares the bins with); the frame is the same bytes.  opts: cull, flip_normals, shade, ambient, unpainted, background."""
+    measurement compares the bins with); the frame is the same bytes.  opts: cull, flip_normals, shade, ambient, unpainted, background.
+    clip_near=True (dtp_op_mesh_view_clip): the faces across the camera's near plane are drawn too, down to the plane; binned=False
+    then also gives each of them the whole frame as its pixel range.  With it, filter="trilinear" takes mips (the pyramid of
+    build_mips / ops.texture_mips) and want_lod appends lod f32 [H,W] to the tuple."""
     from . import mesh as _mesh
     lib = _lib.load()
     H, W = (int(v) for v in (camera.size if size is None else size))
     if not (1 <= H <= _lib.VIEW_MAX and 1 <= W <= _lib.VIEW_MAX):
         raise ValueError(f"size = ({H}, {W}): each side 1..{_lib.VIEW_MAX}")
+    if filter not in ("bilinear", "trilinear"):
+        raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
+    if not clip_near and (filter != "bilinear" or mips is not None or want_lod):
+        raise ValueError("filter, mips and want_lod need clip_near=True here (render_view(filter='trilinear') is the unclipped filtered frame)")
     o, cam = _mesh.view_opts(**opts), camera.struct()
     image = torch.empty(H, W, 4, dtype=torch.uint8, device=texture.device)
     face_idx = torch.empty(H, W, dtype=torch.int32, device=texture.device) if want_face_idx else None
     depth = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_depth else None
-    check(lib.dtp_op_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(o), ptr(image),
-                               ptr(face_idx), ptr(depth), int(bool(binned)), _stream()), "mesh_view")
-    return image, face_idx, depth
+    if not clip_near:
+        check(lib.dtp_op_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(o), ptr(image),
+                                   ptr(face_idx), ptr(depth), int(bool(binned)), _stream()), "mesh_view")
+        return image, face_idx, depth
+    lod = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_lod else None
+    check(lib.dtp_op_mesh_view_clip(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), C.byref(cam), H, W, C.byref(o),
+                                    int(filter == "trilinear"), ptr(image), ptr(face_idx), ptr(depth), ptr(lod), int(bool(binned)), _stream()),
+          "mesh_view_clip")
+    return (image, face_idx, depth, lod) if want_lod else (image, face_idx, depth)
 
 
 def mip_layout(TH, TW):

@@ -26,7 +26,8 @@ extern "C" {
  * dtp_op_mesh_render, dtp_op_mesh_backproject) and their bleed pass (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_mesh_bleed_offsets,
  * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) and the undo / redo journal
  * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) and the
- * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state) are additions; nothing that existed at
+ * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state)
+ * and the view clipped at the near plane (dtp_mesh_view_clip, dtp_op_mesh_view_clip) are additions; nothing that existed at
  * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -515,6 +516,50 @@ int dtp_texture_mips(const uint8_t* texture, int TH, int TW, uint8_t* mips, uint
 int dtp_mesh_view_mips(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                        const dtp_view_opts* opts, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s);
 
+/* ---------------------------------------------------------------- a view clipped at the near plane
+ * dtp_mesh_view drops a face whole as soon as one vertex is nearer than the near plane.  On a scan of sub-pixel faces that costs a rim;
+ * on a floor under the camera, the walls of a room painted from inside, the long side of a box seen along its length it removes the
+ * surface, and the frame shows background where dtp_mesh_pick of the pixel's ray hits.  dtp_mesh_view_clip is
+ * dtp_mesh_view (filter 0) or dtp_mesh_view_mips (filter 1) that also draws the faces ACROSS the plane, down to the plane.  No geometry
+ * is cut: a cut makes new vertices, whose snapped positions are no function of the mesh alone.  A crossing face is rasterised in
+ * homogeneous form instead (Olano and Greer, "Triangle scan conversion using 2D homogeneous coordinates", 1997): per pixel the edge
+ * functions of the camera-space triangle against the pixel's ray, which give the same q_k and d that the rest of the frame consumes.
+ * fp32, one rounded operation at a time in the order written; nothing is compared under a tolerance.
+ *
+ * Classes of face, from the camera-space c_k = (x_k, y_k, z_k) exactly as dtp_mesh_view computes them:
+ *   IN FRONT  all nine values finite and every z_k <= -near: dtp_mesh_view's face, bit for bit (snapped integers, int64 coverage).
+ *   BEHIND    every z_k > -near, or any value not finite: not drawn.
+ *   CROSSING  finite, at least one vertex on each side (a vertex with z_k == -near is in front): drawn as follows.
+ * Per crossing face: n_0 = c_1 x c_2, n_1 = c_2 x c_0, n_2 = c_0 x c_1 with cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z,
+ * a.x b.y - a.y b.x), each component a product minus a product; D = (c_0.x n_0.x + c_0.y n_0.y) + c_0.z n_0.z.  D == 0 or a D that is
+ * not finite (the face's plane contains the eye): not drawn.  The face keeps m_k = n_k for D > 0, -n_k for D < 0 (a sign flip, exact)
+ * and r = 1.0f / |D|, SEPARATELY: two faces that share an edge have n that are exact negations of each other, so the signs of their
+ * edge functions at a pixel agree exactly and a centre on the shared edge is never refused by both.  Facing comes from the side of the
+ * face's plane the eye is on: D < 0 is FRONT (the side dtp_mesh_view calls front: a face pushed back until it no longer crosses keeps
+ * its facing), flip_normals swaps the two, cull = 1 draws front faces only.  nzu is computed as dtp_mesh_view computes it.
+ * Per pixel (i, j): g_x = ((float)(2 j + 1) / (float)W - 1.0f) / fx, g_y = (1.0f - (float)(2 i + 1) / (float)H) / fy: the ray of the
+ * centre as dtp_view_rays defines it, (g_x, g_y, -1) in camera space.  E_k = (m_k.x g_x + m_k.y g_y) - m_k.z.  The face covers the
+ * centre iff every E_k >= 0 (edges are inclusive; the winner rule settles a double cover), and with q_k = E_k r, d = (q0 + q1) + q2:
+ * d is finite and > 0 (the face's plane ends at its horizon), and 1.0f / d >= near.  That last test IS the clip: it generalises "every
+ * z_k <= -near", and no pixel of a clipped frame has a depth below near.  From there on nothing is new: the winner is the covering face
+ * with the largest (d, -face index) among faces of both kinds, u = ((q0 u0 + q1 u1) + q2 u2) / d, v likewise, the sample, the shade,
+ * the byte, face_idx and depth = 1.0f / d are dtp_mesh_view's.  In real arithmetic q_k and d are the quantities the integer path computes.
+ * filter 1: steps 2-3 of dtp_mesh_view_mips apply to a crossing winner with the same E_k, q_k', d' at the rays of the centres (i, j + 1)
+ * and (i + 1, j), no inside test; a d' that is not finite or not > 0 gives level L - 1 with f = 0.
+ * What is known and not hidden: crossing faces are watertight among themselves (the sign argument above), faces in front among
+ * themselves (the integer rule).  Along an edge between a crossing face and a neighbour in front two rules meet, snapped integers and
+ * fp32 homogeneous edge functions: a centre within the snap (1/256 pixel) of that edge may be claimed by both, and depth decides, or by
+ * neither, and one pixel shows what lies behind.  It is a preview.  A scene without a crossing face gives dtp_mesh_view's (or
+ * dtp_mesh_view_mips') frame byte for byte.
+ *
+ * dtp_mesh_view_clip: the arguments, checks, buffers and launches (a memset and four kernels) of dtp_mesh_view_mips, plus filter: 0 =
+ * one bilinear sample of level 0 (mips and lod must be NULL), 1 = trilinear (mips may be NULL when the layout has 1 level; lod or NULL).
+ * A filter that is neither is DTP_ERR_ARG.  Every check comes before any device call and a refused call writes nothing.  A crossing
+ * face is streamed by every tile its pixel range meets; the range is the box of the projected polygon cut at z = -near, grown, and
+ * holds every centre the face covers. */
+int dtp_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                       const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s);
+
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
  * the last 10 copies and uploads one on Ctrl+Z (kit_app/.../python/ui/brush.py:52-77,131-137; redo is a TODO there).  A journal keeps, on
@@ -972,6 +1017,11 @@ int dtp_op_mesh_pick(dtp_mesh* mesh, const dtp_ray* rays, int n, dtp_mesh_hit* o
  * same bytes either way. */
 int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
                      uint8_t* image, int* face_idx, float* depth, int binned, dtp_stream s);
+/* dtp_mesh_view_clip (the contract: see "a view clipped at the near plane") with the binning switched: binned 1 is dtp_mesh_view_clip
+ * exactly; binned 0 puts every drawn face on the list that every tile streams AND gives every crossing face the whole frame as its pixel
+ * range: the arm against which the ranges are tested.  The frame is the same bytes either way. */
+int dtp_op_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                          const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, int binned, dtp_stream s);
 #ifdef __cplusplus
 }
 #endif
