@@ -78,6 +78,16 @@ class ViewOpts(C.Structure):  # dtp_view_opts
 
 
 VIEW_MAX = 4096  # the largest side of a view's frame
+VIEW_SAMPLES = (1, 2, 4)  # the sides of the sample grid of a pixel (dtp_mesh_view_aa); samples * side <= VIEW_MAX
+
+
+def view_samples_check(samples, H, W):
+    """ValueError for a `samples` that dtp_mesh_view_aa refuses at H x W; -> samples as an int."""
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples not in VIEW_SAMPLES:
+        raise ValueError(f"samples = {samples!r}: choose 1, 2 or 4 (the side of the sample grid of a pixel)")
+    if samples * H > VIEW_MAX or samples * W > VIEW_MAX:
+        raise ValueError(f"samples = {samples} at size ({H}, {W}): samples * side must not exceed {VIEW_MAX}")
+    return samples
 
 
 class MipLevels(C.Structure):  # dtp_mip_levels
@@ -230,6 +240,9 @@ SYMBOLS = {
     "dtp_mesh_view_mips": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _vp, _vp, _vp, _vp, _vp]),
     "dtp_mesh_view_clip": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _vp, _vp, _vp, _vp, _vp]),
     "dtp_op_mesh_view_clip": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "dtp_mesh_view_aa": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dtp_op_mesh_view_aa": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i,
+                                 _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

@@ -11,7 +11,9 @@
 // (mips.hip): the raster kernel is a template on the filter, and its unfiltered instantiation is dtp_mesh_view's code.  dtp_mesh_view_clip
 //  also draws the faces that CROSS the near plane, in homogeneous form: per face the cross products of its camera-space
 // vertices, per pixel their edge functions against the pixel's ray, which give the same q_k and d the rest of the raster kernel consumes.
-// It is a second template parameter; the instantiations without it are the code they were.
+// It is a second template parameter; the instantiations without it are the code they were.  dtp_mesh_view_aa draws the
+// same frames with s x s samples per pixel: project, scan and fill run for the frame of s H x s W, and a raster kernel of its own
+// (view_raster_aa_kernel) keeps a winner per sample in registers and sums the samples' bytes in LDS: the larger frame is never stored.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stddef.h>
@@ -212,6 +214,84 @@ __device__ __forceinline__ void view_sample(const unsigned int* __restrict__ tex
   }
 }
 
+// The texel of a covered centre: `best` won pixel (row, col) of an H x W frame, centre (px, py), ray (gx, gy) (CLIP alone), with q_k = bq
+// and their sum best_d.  The perspective-correct UV, the sample (FILTER 1: the footprint from the face at the two neighbouring centres,
+// the level walk, two levels blended; lod is written), the shade, the bytes with alpha 255.  This is the text of view_raster_kernel's
+// own shading below, for the anti-aliased kernel alone: calling it from view_raster_kernel too changes that kernel's register
+// allocation and argument loads, and the instantiations of 3.24 - 3.27 are to stay the code they are.  A change to one is a change to
+// both; the anti-aliased tests compare the two byte for byte.
+template <int FILTER, int CLIP>
+__device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ rec, const float* __restrict__ uvs, const unsigned int* __restrict__ tex,
+                                                   int TH, int TW, int H, int W, ViewShade sh, ViewFilter<FILTER> fl,
+                                                   ViewClip<CLIP> cl, int best, const float bq[3], float best_d, int col, int row, int px,
+                                                   int py, float gx, float gy, float& lod) {
+  const float* uv = uvs + (size_t)6 * best;
+  const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
+  float tc[4];
+  if constexpr (FILTER == 0) {
+    view_sample(tex, TH, TW, u, v, tc);
+  } else {
+    const ViewRec& r = rec[best];
+    float qx[3], qy[3];
+    bool crossing = false;
+    if constexpr (CLIP != 0) crossing = (r.flags & VF_CROSS) != 0;
+    if (crossing) {
+      if constexpr (CLIP != 0) {  // the same E_k, q_k at the two neighbouring centres, no inside test
+        const float gx1 = ray_x(col + 1, W, cl.fx), gy1 = ray_y(row + 1, H, cl.fy), inv = __int_as_float(r.pad[0]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float nx = k == 0 ? __int_as_float(r.X[0]) : k == 1 ? __int_as_float(r.Y[0]) : r.iw[0];
+          const float ny = k == 0 ? __int_as_float(r.X[1]) : k == 1 ? __int_as_float(r.Y[1]) : r.iw[1];
+          const float nz = k == 0 ? __int_as_float(r.X[2]) : k == 1 ? __int_as_float(r.Y[2]) : r.iw[2];
+          qx[k] = ((nx * gx1 + ny * gy) - nz) * inv;
+          qy[k] = ((nx * gx + ny * gy1) - nz) * inv;
+        }
+      }
+    } else {
+      float wx[3], wy[3];
+      weights_at(r.X, r.Y, px + 256, py, wx);
+      weights_at(r.X, r.Y, px, py + 256, wy);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { qx[k] = wx[k] * r.iw[k]; qy[k] = wy[k] * r.iw[k]; }
+    }
+    const float dx = (qx[0] + qx[1]) + qx[2], dy = (qy[0] + qy[1]) + qy[2];
+    float rho2 = INFINITY;  // beyond the horizon, or a footprint that is not finite: the last level
+    if (isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f) {
+      const float fw = (float)TW, fh = (float)TH;
+      const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
+      const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
+      rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
+      if (!isfinite(rho2)) rho2 = INFINITY;
+    }
+    // level l of hl x wl texels at `at` of the pyramid (l >= 1), level l + 1 at `next`; p4 = 4^l
+    int l = 0, hl = TH, wl = TW;
+    size_t at = 0, next = 0;
+    float p4 = 1.0f;
+    while (l + 1 < fl.levels && p4 * 4.0f <= rho2) {
+      at = next; hl = mip_half(hl); wl = mip_half(wl); next = at + (size_t)hl * wl;
+      p4 *= 4.0f; ++l;
+    }
+    const float f = (l + 1 == fl.levels || rho2 <= p4) ? 0.f : ((rho2 / p4) - 1.0f) / 3.0f;
+    lod = (float)l + f;
+    view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
+    if (f > 0.f) {
+      float tn[4];
+      view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+    }
+  }
+  const float s = sh.shade ? sh.ambient + (1.0f - sh.ambient) * fabsf(rec[best].nzu) : 1.0f;
+  const float rest = 1.0f - tc[3];
+  unsigned int out = 0xff000000u;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float cc = (tc[ch] * tc[3] + sh.unpainted[ch] * rest) * s;
+    out |= (unsigned int)(unsigned char)(fminf(cc, 1.0f) * 255.0f + 0.5f) << (8 * ch);
+  }
+  return out;
+}
+
 // One workgroup per 16 x 16 pixel tile, one thread per pixel.  The tile's bin segment, then the large list, stream through LDS CHUNK at a
 // time; a face whose pixel range misses the tile is dropped on the way in.  Winner: the largest (inverse depth d, -face index) among
 // the faces that cover the centre.  Then the perspective-correct UV, the sample, the shade and the stores.  FILTER 1: the winner face
@@ -374,6 +454,182 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   }
 }
 
+// The anti-aliased frame (dtp_mesh_view_aa): the raster kernel above for the FINE frame of S H x S W pixels that project,
+// scan and fill have binned, resolved on the chip.  One workgroup per 16 x 16 OUTPUT pixels = 16 S x 16 S fine ones, which lie in one
+// bin (view_aa_tile_bin).  The fine tile is S x S SUB-TILES of 16 x 16 fine pixels.  A round stages a chunk of the bin's segment (then
+// of the large list) ONCE for all of them -- the plain kernel at S x the size stages it once per 16 x 16 tile -- and while staging, a
+// face is entered into the list of every sub-tile its pixel range meets.  S > 1 runs 1024 threads, four groups of 256, and stages 1024
+// (S = 2) or 512 (S = 4) faces a round; group g draws the sub-tiles g, g + 4, ... in turns (one turn at S = 2, four at S = 4), thread
+// (ty, tx) of the group owning fine pixel (ty, tx) of each of them and keeping that sample's winner (d, face) in registers.  In a turn
+// the group walks that sub-tile's list with cover() (or the rays of a crossing face): the plain kernel's loop on the faces the plain
+// kernel's tile would have staged, so the lanes of a wave look at neighbouring samples of the same few faces, and a frame that covers
+// few tiles keeps some of the plain kernel's parallelism.  (A first version gave each thread the S x S samples of ONE output pixel and
+// stepped the edge functions between them: with faces of a fine pixel or two, nearly every face was then evaluated at all S^2 samples
+// for the sake of one or two lanes, and the frame took 3 to 18 times as long as the plain kernel at S x the size; 3.28 has the
+// figures.)  After the last round each sample is weighted again at its centre (the same operations: the same q_k, d), shaded by
+// view_shade as a pixel of the fine frame, and its bytes, the background's where no face is, are added to the sums of its output
+// pixel in LDS (integer adds: the order does not matter); the sample (S / 2, S / 2) of a pixel stores face_idx, depth and lod.  Last,
+// thread (ty, tx) of the first group stores the rounded average and the count of output pixel (ty, tx).  The turns are rolled loops
+// (copies of the body would crowd the instruction cache): a turn's winner is picked out of the registers and put back by compares with
+// the turn, never by an index.  S = 1 is the kernel above with a count.
+constexpr int view_aa_threads(int S) { return S == 1 ? 256 : 1024; }
+constexpr int view_aa_chunk(int S) { return S == 1 ? CHUNK : S == 2 ? 1024 : 512; }  // faces staged per round (56 and 42 KB of LDS)
+template <int FILTER, int CLIP, int S>
+__global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(const ViewRec* __restrict__ rec, const int* __restrict__ items,
+                                                             const int* __restrict__ large, const ViewState* st, int F, int nbx, const float* __restrict__ uvs,
+                                                             const unsigned int* __restrict__ tex, int TH, int TW, int H, int W, ViewShade sh,
+                                                             unsigned int* __restrict__ image, int* __restrict__ face_idx, float* __restrict__ depth,
+                                                             unsigned char* __restrict__ coverage, ViewFilter<FILTER> fl, ViewClip<CLIP> cl) {
+  constexpr int N = S * S, LOG2N = S == 1 ? 0 : S == 2 ? 2 : 4;
+  constexpr int GROUPS = view_aa_threads(S) / 256, P = N / GROUPS;  // 256 threads a group; group g takes the sub-tiles g, g + GROUPS, ...: P turns
+  constexpr int CH = view_aa_chunk(S);
+  __shared__ int s_n, s_cnt[N], s_face[CH], s_X[CH][3], s_Y[CH][3];
+  __shared__ float s_iw[CH][3];
+  __shared__ float s_inv[CLIP ? CH : 1];
+  __shared__ unsigned short s_list[N][CH];    // per sub-tile: the staged slots whose pixel range meets it
+  __shared__ unsigned int s_sum[256][2];      // per output pixel: the sums of R | G << 16 and of B | A << 16 (at most 16 x 255 each)
+  __shared__ int s_cov[256];                  // and the number of samples that a face covers
+  const int t = threadIdx.x & 255, tx = t & 15, ty = t >> 4, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
+  const int group = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);  // (the same in every lane of a wave)
+  const bool first = group == 0;                                            // the group that stores the pixels
+  const int FH = S * H, FW = S * W;              // the fine frame
+  const int fcol0 = S * col0, frow0 = S * row0;  // the tile's first fine pixel
+  const int bin = view_aa_tile_bin(S, row0, col0, nbx);
+  const int cap = 4 * F;
+  const int seg0 = min(max(st->offset[bin], 0), cap), n_seg = min(max(st->offset[bin + 1], seg0), cap) - seg0;
+  const int total = n_seg + min(max(st->n_large, 0), F);
+  int best[P];
+  float best_d[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) { best[p] = -1; best_d[p] = 0.f; }
+  if (first) { s_sum[t][0] = 0u; s_sum[t][1] = 0u; s_cov[t] = 0; }
+  for (int base = 0; base < total; base += CH) {
+    if (first && t == 0) s_n = 0;
+    if (first && t < N) s_cnt[t] = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < CH && base + (int)threadIdx.x < total) {
+      const int i = base + (int)threadIdx.x, f = i < n_seg ? items[seg0 + i] : large[i - n_seg];
+      if ((unsigned int)f < (unsigned int)F) {
+        const ViewRec& r = rec[f];
+        if (ranges_meet(r.px, fcol0, fcol0 + 16 * S - 1) && ranges_meet(r.py, frow0, frow0 + 16 * S - 1)) {
+          const int slot = atomicAdd(&s_n, 1);  // (below CH: at most one per staging thread)
+          if constexpr (CLIP != 0) {
+            s_face[slot] = (r.flags & VF_CROSS) ? f | CROSS_SLOT : f;
+            s_inv[slot] = __int_as_float(r.pad[0]);
+          } else {
+            s_face[slot] = f;
+          }
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { s_X[slot][k] = r.X[k]; s_Y[slot][k] = r.Y[k]; s_iw[slot][k] = r.iw[k]; }
+#pragma unroll
+          for (int k = 0; k < N; ++k) {
+            const int x = fcol0 + 16 * (k % S), y = frow0 + 16 * (k / S);
+            if (ranges_meet(r.px, x, x + 15) && ranges_meet(r.py, y, y + 15)) s_list[k][atomicAdd(&s_cnt[k], 1)] = (unsigned short)slot;
+          }
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int p = 0; p < P; ++p) {
+      const int k = group + GROUPS * p, n = s_cnt[k];
+      const int col = fcol0 + 16 * (k % S) + tx, row = frow0 + 16 * (k / S) + ty;  // this thread's sample of sub-tile k
+      if (n == 0 || !(col < FW && row < FH)) continue;
+      const int px = 256 * col + 128, py = 256 * row + 128;
+      float gx = 0.f, gy = 0.f;
+      if constexpr (CLIP != 0) { gx = ray_x(col, FW, cl.fx); gy = ray_y(row, FH, cl.fy); }
+      int cur = -1;
+      float cur_d = 0.f;
+#pragma unroll
+      for (int j = 0; j < P; ++j) { cur = j == p ? best[j] : cur; cur_d = j == p ? best_d[j] : cur_d; }
+      for (int at = 0; at < n; ++at) {
+        const int i = s_list[k][at];
+        int f = s_face[i];
+        float d;
+        bool crossing = false;
+        if constexpr (CLIP != 0) { crossing = (f & CROSS_SLOT) != 0; f &= ~CROSS_SLOT; }
+        if (crossing) {
+          if constexpr (CLIP != 0) {
+            const float E0 = (__int_as_float(s_X[i][0]) * gx + __int_as_float(s_X[i][1]) * gy) - __int_as_float(s_X[i][2]);
+            const float E1 = (__int_as_float(s_Y[i][0]) * gx + __int_as_float(s_Y[i][1]) * gy) - __int_as_float(s_Y[i][2]);
+            const float E2 = (s_iw[i][0] * gx + s_iw[i][1] * gy) - s_iw[i][2];
+            if (!(E0 >= 0.f && E1 >= 0.f && E2 >= 0.f)) continue;
+            const float inv = s_inv[i];
+            d = (E0 * inv + E1 * inv) + E2 * inv;
+            if (!(isfinite(d) && d > 0.f && 1.0f / d >= cl.near)) continue;  // the plane's horizon, and the clip itself
+          }
+        } else {
+          float w[3];
+          if (!cover(s_X[i], s_Y[i], px, py, w)) continue;
+          d = (w[0] * s_iw[i][0] + w[1] * s_iw[i][1]) + w[2] * s_iw[i][2];
+        }
+        if (cur < 0 || d > cur_d || (d == cur_d && f < cur)) { cur = f; cur_d = d; }
+      }
+#pragma unroll
+      for (int j = 0; j < P; ++j) { best[j] = j == p ? cur : best[j]; best_d[j] = j == p ? cur_d : best_d[j]; }
+    }
+    __syncthreads();
+  }
+  __syncthreads();  // (the sums were zeroed above; without a chunk nothing has waited yet)
+#pragma unroll 1
+  for (int p = 0; p < P; ++p) {
+    const int k = group + GROUPS * p;
+    const int sy = 16 * (k / S) + ty, sx = 16 * (k % S) + tx;  // the sample's place in the fine tile
+    const int col = fcol0 + sx, row = frow0 + sy;
+    if (!(col < FW && row < FH)) continue;
+    int f = -1;
+#pragma unroll
+    for (int j = 0; j < P; ++j) f = j == p ? best[j] : f;
+    unsigned int out = sh.background;
+    float dist = 0.f, lod = 0.f;
+    if (f >= 0) {
+      const ViewRec& r = rec[f];
+      const int px = 256 * col + 128, py = 256 * row + 128;
+      float q[3] = {0.f, 0.f, 0.f}, gx = 0.f, gy = 0.f;
+      bool crossing = false;
+      if constexpr (CLIP != 0) {
+        crossing = (r.flags & VF_CROSS) != 0;
+        gx = ray_x(col, FW, cl.fx); gy = ray_y(row, FH, cl.fy);
+      }
+      if (crossing) {
+        if constexpr (CLIP != 0) {
+          const float inv = __int_as_float(r.pad[0]);
+          q[0] = ((__int_as_float(r.X[0]) * gx + __int_as_float(r.X[1]) * gy) - __int_as_float(r.X[2])) * inv;
+          q[1] = ((__int_as_float(r.Y[0]) * gx + __int_as_float(r.Y[1]) * gy) - __int_as_float(r.Y[2])) * inv;
+          q[2] = ((r.iw[0] * gx + r.iw[1] * gy) - r.iw[2]) * inv;
+        }
+      } else {
+        float w[3] = {0.f, 0.f, 0.f};
+        weights_at(r.X, r.Y, px, py, w);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q[c] = w[c] * r.iw[c];
+      }
+      const float d = (q[0] + q[1]) + q[2];
+      out = view_shade<FILTER, CLIP>(rec, uvs, tex, TH, TW, FH, FW, sh, fl, cl, f, q, d, col, row, px, py, gx, gy, lod);
+      dist = 1.0f / d;
+    }
+    const int at = (sy / S) * 16 + sx / S;  // the output pixel of the tile that this sample belongs to
+    atomicAdd(&s_sum[at][0], (out & 0xffu) | ((out & 0xff00u) << 8));
+    atomicAdd(&s_sum[at][1], ((out >> 16) & 0xffu) | ((out >> 24) << 16));
+    if (f >= 0) atomicAdd(&s_cov[at], 1);
+    if (sy % S == S / 2 && sx % S == S / 2) {  // (inside the frame, as its sample is)
+      const size_t pix = (size_t)(row0 + sy / S) * W + (col0 + sx / S);
+      if (face_idx) face_idx[pix] = f;
+      if (depth) depth[pix] = dist;
+      if constexpr (FILTER != 0) {
+        if (fl.lod) fl.lod[pix] = lod;
+      }
+    }
+  }
+  __syncthreads();
+  if (!(first && col0 + tx < W && row0 + ty < H)) return;
+  const size_t pix = (size_t)(row0 + ty) * W + (col0 + tx);
+  const unsigned int rg = s_sum[t][0], ba = s_sum[t][1];
+  image[pix] = (((rg & 0xffffu) + N / 2) >> LOG2N) | ((((rg >> 16) + N / 2) >> LOG2N) << 8) | ((((ba & 0xffffu) + N / 2) >> LOG2N) << 16) |
+               ((((ba >> 16) + N / 2) >> LOG2N) << 24);
+  if (coverage) coverage[pix] = (unsigned char)s_cov[t];
+}
+
 int view_reserve(const MeshGeom& g) {
   if (*g.view) return DTP_OK;
   ViewBufs* b = new ViewBufs();
@@ -396,9 +652,11 @@ int view_reserve(const MeshGeom& g) {
 // plane are drawn too
 int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* o,
              uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s, int filter = 0, const uint8_t* mips = nullptr, float* lod = nullptr,
-             int clip = 0) {
+             int clip = 0, int samples = 0, uint8_t* coverage = nullptr) {
   if (!mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
   if (const char* why = view_check(texture, TH, TW, cam, H, W, o, image, face_idx, depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
+  if (samples)
+    if (const char* why = view_aa_check(samples, H, W)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
   dtp_mip_levels lay;
   if (filter) {
     (void)mip_layout(TH, TW, &lay);  // (the sides were checked above)
@@ -415,10 +673,11 @@ int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, in
   for (int ch = 0; ch < 3; ++ch) sh.unpainted[ch] = (float)o->unpainted[ch] / 255.0f;
   sh.background = (unsigned int)o->background[0] | ((unsigned int)o->background[1] << 8) | ((unsigned int)o->background[2] << 16) |
                   ((unsigned int)o->background[3] << 24);
-  const int nbx = view_bins_across(W), blocks = (g.F + 255) / 256;
+  const int fine = samples ? samples : 1;  // project, scan and fill see the frame the samples are the pixels of
+  const int nbx = view_bins_across(fine * W), blocks = (g.F + 255) / 256;
   HIP_CHECK(hipMemsetAsync(b->st, 0, offsetof(ViewState, offset), s));
-  hipLaunchKernelGGL(view_project_kernel, dim3(blocks), dim3(256), 0, s, g.verts, g.faces, g.F, *cam, H, W, o->cull, o->flip_normals, binned ? 1 : 0, nbx,
-                     b->rec, b->large, b->st, clip ? 1 : 0);
+  hipLaunchKernelGGL(view_project_kernel, dim3(blocks), dim3(256), 0, s, g.verts, g.faces, g.F, *cam, fine * H, fine * W, o->cull, o->flip_normals,
+                     binned ? 1 : 0, nbx, b->rec, b->large, b->st, clip ? 1 : 0);
   hipLaunchKernelGGL(view_scan_kernel, dim3(1), dim3(256), 0, s, b->st);
   hipLaunchKernelGGL(view_fill_kernel, dim3(blocks), dim3(256), 0, s, b->rec, g.F, nbx, b->items, b->st);
   const dim3 tiles((W + 15) / 16, (H + 15) / 16);
@@ -429,10 +688,22 @@ int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, in
 #define RASTER(FILTER, CLIP, fl, cl)                                                                                                   \
   hipLaunchKernelGGL((view_raster_kernel<FILTER, CLIP>), tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs, \
                      (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, fl, cl)
-  if (filter && clip) RASTER(1, 1, fl, cl);
-  else if (filter) RASTER(1, 0, fl, ViewClip<0>());
-  else if (clip) RASTER(0, 1, ViewFilter<0>(), cl);
-  else RASTER(0, 0, ViewFilter<0>(), ViewClip<0>());
+#define RASTER_AA(FILTER, CLIP, S, fl, cl)                                                                                                    \
+  hipLaunchKernelGGL((view_raster_aa_kernel<FILTER, CLIP, S>), tiles, dim3(view_aa_threads(S)), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs, \
+                     (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, coverage, fl, cl)
+#define RASTER_S(FILTER, CLIP, fl, cl)                 \
+  do {                                                 \
+    if (samples == 0) RASTER(FILTER, CLIP, fl, cl);    \
+    else if (samples == 1) RASTER_AA(FILTER, CLIP, 1, fl, cl); \
+    else if (samples == 2) RASTER_AA(FILTER, CLIP, 2, fl, cl); \
+    else RASTER_AA(FILTER, CLIP, 4, fl, cl);           \
+  } while (0)
+  if (filter && clip) RASTER_S(1, 1, fl, cl);
+  else if (filter) RASTER_S(1, 0, fl, ViewClip<0>());
+  else if (clip) RASTER_S(0, 1, ViewFilter<0>(), cl);
+  else RASTER_S(0, 0, ViewFilter<0>(), ViewClip<0>());
+#undef RASTER_S
+#undef RASTER_AA
 #undef RASTER
   if (hipGetLastError() != hipSuccess) { dtp_set_error("%s: a kernel launch failed", who); return DTP_ERR_HIP; }
   return DTP_OK;
@@ -492,6 +763,23 @@ int dtp_op_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW
   if (filter != 0 && filter != 1) { dtp_set_error("%s: filter is 0 (bilinear) or 1 (trilinear)", who); return DTP_ERR_ARG; }
   if (!filter && (mips || lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
   return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, filter, mips, lod, 1);
+}
+
+int dtp_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                     const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
+                     uint8_t* coverage, dtp_stream s) {
+  return dtp_op_mesh_view_aa(mesh, texture, TH, TW, mips, cam, H, W, opts, filter, clip, samples, image, face_idx, depth, lod, coverage, 1, s);
+}
+
+int dtp_op_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                        const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
+                        uint8_t* coverage, int binned, dtp_stream s) {
+  const char* who = binned == 1 ? "dtp_mesh_view_aa" : "dtp_op_mesh_view_aa";
+  if (filter != 0 && filter != 1) { dtp_set_error("%s: filter is 0 (bilinear) or 1 (trilinear)", who); return DTP_ERR_ARG; }
+  if (clip != 0 && clip != 1) { dtp_set_error("%s: clip is 0 or 1", who); return DTP_ERR_ARG; }
+  if (!filter && (mips || lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
+  if (samples != 1 && samples != 2 && samples != 4) { dtp_set_error("%s: %s", who, view_aa_check(samples, 1, 1)); return DTP_ERR_ARG; }
+  return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, filter, mips, lod, clip, samples, coverage);
 }
 
 }  // extern "C"

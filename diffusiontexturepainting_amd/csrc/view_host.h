@@ -1,8 +1,9 @@
 // The host-only arithmetic of the view of a textured mesh (include/dtp.h "a view of a textured mesh": dtp_view_camera, dtp_view_rays,
 // dtp_mesh_view): the perspective camera and the rays of its pixels in double, rounded to fp32 once; every argument check
-// of a view but the look-up of the mesh; the bins a face's pixel range meets; the pixel range of a face that crosses the near plane.  No
-// device call, so the stand-alone sanitizer programs (tools/view_host_check.cpp, tools/view_clip_host_check.cpp) drive it directly, built by
-// a plain C++ compiler.
+// of a view but the look-up of the mesh; the bins a face's pixel range meets; the pixel range of a face that crosses the near plane; the
+// checks of the anti-aliased view and the bin of one of its tiles.  No device call, so the stand-alone sanitizer programs
+// (tools/view_host_check.cpp, tools/view_clip_host_check.cpp, tools/view_aa_host_check.cpp) drive it directly, built by a plain C++
+// compiler.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -85,6 +86,20 @@ inline const char* view_cam_check(const dtp_view_cam* c) {
 }
 inline const char* view_size_check(int H, int W) {
   return (H < 1 || W < 1 || H > VIEW_MAX || W > VIEW_MAX) ? "the frame's H and W must lie in 1..4096" : nullptr;
+}
+
+// The anti-aliased view (include/dtp.h "an anti-aliased view"): samples = the side s of the sample grid of a pixel.  The frame that is
+// binned is the FINE one, s H x s W, so that is what has to fit the packed ranges and the bin counters.  nullptr, or what is wrong.
+inline const char* view_aa_check(int samples, int H, int W) {
+  if (samples != 1 && samples != 2 && samples != 4) return "samples is 1, 2 or 4 (the side of the sample grid of a pixel)";
+  if (const char* why = view_size_check(H, W)) return why;
+  if (samples * H > VIEW_MAX || samples * W > VIEW_MAX) return "samples * H and samples * W must not exceed 4096";
+  return nullptr;
+}
+// The bin of the fine frame that holds ALL fine pixels of the output tile whose first pixel is (row0, col0) (multiples of 16): the tile
+// is 16 s <= 64 fine pixels a side and starts at a multiple of 16 s, so it never straddles a bin.  nbx: view_bins_across(s W).
+VIEW_HD inline int view_aa_tile_bin(int s, int row0, int col0, int nbx) {
+  return ((s * row0) >> VIEW_BIN_SHIFT) * nbx + ((s * col0) >> VIEW_BIN_SHIFT);
 }
 
 // dtp_view_camera: in double from the fp32 inputs, rounded to fp32 once.  b = normalize(eye - at), r = normalize(cross(up, b)),

@@ -528,7 +528,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def render_view(self, mesh, texture, camera, size=None, cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128),
                     background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False, filter="bilinear", mips=None,
-                    want_lod=False, clip_near=False):
+                    want_lod=False, clip_near=False, samples=1, want_coverage=False):
         """A perspective view of the whole painted mesh (dtp_mesh_view; in the Kit app the viewport is Omniverse RTX):
         `mesh` from load_mesh, `texture` uint8 [TH, TW, 4] on the model's device, `camera` from mesh.view_camera, size = (H, W) (default
         the camera's; each side 1..4096).  -> the frame, uint8 [H, W, 4] on the device (RGB the texture under its alpha over `unpainted`,
@@ -549,7 +549,15 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         clip_near=True (dtp_mesh_view_clip): a face ACROSS the near plane is drawn down to the plane instead of dropped
         -- the floor under the camera, the walls of a room painted from inside -- with either filter; no pixel then has a depth below
         the camera's near, and the face a frame shows at a pixel is the face mesh.view_rays' ray of that pixel hits.  Faces wholly in
-        front keep their exact coverage, and a frame without a crossing face is the same bytes as without the keyword."""
+        front keep their exact coverage, and a frame without a crossing face is the same bytes as without the keyword.
+        samples=2 or 4 (dtp_mesh_view_aa): anti-aliasing, samples x samples centres per pixel on an ordered grid, in one
+        pass.  The samples of pixel (i, j) are the pixels (samples i + a, samples j + b) of the frame the same call would draw at
+        samples x the size (which is never stored), and the pixel is the rounded average of their bytes, per channel, the background's
+        bytes included: with the default transparent background a silhouette pixel carries its colour premultiplied by its coverage,
+        and the coverage in alpha.  face_idx, depth and lod are those of the sample just below and right of the pixel's centre; lod
+        comes out about log2(samples) lower, because a sample covers that much less of the texture.  samples x each side <= 4096, so
+        1080p takes samples=2.  want_coverage: also uint8 [H, W], how many of the pixel's samples a face covers (0 .. samples^2), last
+        in the tuple.  samples=1 without want_coverage is the call it always was, launch for launch."""
         if filter not in ("bilinear", "trilinear"):
             raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
         trilinear = filter == "trilinear"
@@ -559,12 +567,14 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             raise ValueError("mesh must come from load_mesh()")
         if not isinstance(camera, _mesh.ViewCamera):
             raise ValueError("camera must come from mesh.view_camera()")
-        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
-                and texture.device == self._device and texture.is_contiguous()):
-            raise ValueError(f"texture must be a contiguous uint8 [TH, TW, 4] tensor on {self._device}")
         H, W = (int(v) for v in (camera.size if size is None else size))
         if not (1 <= H <= _lib.VIEW_MAX and 1 <= W <= _lib.VIEW_MAX):
             raise ValueError(f"size = ({H}, {W}): each side 1..{_lib.VIEW_MAX}")
+        samples = _lib.view_samples_check(samples, H, W)
+        aa = samples > 1 or bool(want_coverage)
+        if not (isinstance(texture, torch.Tensor) and texture.dtype == torch.uint8 and texture.dim() == 3 and texture.shape[2] == 4
+                and texture.device == self._device and texture.is_contiguous()):
+            raise ValueError(f"texture must be a contiguous uint8 [TH, TW, 4] tensor on {self._device}")
         if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == (H, W, 4) and out.device == self._device
                   and out.is_contiguous()):
             raise ValueError(f"out must be a contiguous uint8 [{H}, {W}, 4] tensor on {self._device}")
@@ -584,6 +594,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             face_idx = torch.empty(H, W, dtype=torch.int32, device=self._device) if want_face_idx else None
             depth = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_depth else None
             lod = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_lod else None
+            coverage = torch.empty(H, W, dtype=torch.uint8, device=self._device) if want_coverage else None
             if build:
                 key = (texture.shape[0], texture.shape[1])
                 if key not in self._view_mips:
@@ -597,7 +608,11 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         vs = C.c_void_p(self.view_stream.cuda_stream)
         if trilinear and build:
             check(self._lib.dtp_texture_mips(ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), need, vs), "dtp_texture_mips")
-        if clip_near:
+        if aa:
+            check(self._lib.dtp_mesh_view_aa(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips) if trilinear else None,
+                                             C.byref(cam), H, W, C.byref(opts), int(trilinear), int(bool(clip_near)), samples, ptr(out),
+                                             ptr(face_idx), ptr(depth), ptr(lod), ptr(coverage), vs), "dtp_mesh_view_aa")
+        elif clip_near:
             check(self._lib.dtp_mesh_view_clip(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips) if trilinear else None,
                                                C.byref(cam), H, W, C.byref(opts), int(trilinear), ptr(out), ptr(face_idx), ptr(depth), ptr(lod), vs),
                   "dtp_mesh_view_clip")
@@ -611,10 +626,10 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         for t in (texture, given, None if build else mips):
             if t is not None:
                 t.record_stream(self.view_stream)
-        for t in (None if given is not None else out, face_idx, depth, lod):
+        for t in (None if given is not None else out, face_idx, depth, lod, coverage):
             if t is not None:
                 t.record_stream(cur)
-        extra = tuple(t for t in (face_idx, depth, lod) if t is not None)
+        extra = tuple(t for t in (face_idx, depth, lod, coverage) if t is not None)
         return (out,) + extra if extra else out
 
     def _mip_bytes(self, texture):

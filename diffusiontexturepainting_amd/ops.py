@@ -626,13 +626,16 @@ def mesh_pick(mesh, origins, directions):
 
 
 def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True, want_depth=True, clip_near=False, filter="bilinear", mips=None,
-              want_lod=False, **opts):
+              want_lod=False, samples=1, want_coverage=False, **opts):
     """dtp_op_mesh_view: the frame of MI355ConditionalInpainter.render_view on the current stream -> (image u8 [H,W,4], face_idx i32
     [H,W] or None, depth f32 [H,W] or None).  binned=False puts every drawn face on the list that every tile streams (the arm a
     measurement compares the bins with); the frame is the same bytes.  opts: cull, flip_normals, shade, ambient, unpainted, background.
     clip_near=True (dtp_op_mesh_view_clip): the faces across the camera's near plane are drawn too, down to the plane; binned=False
     then also gives each of them the whole frame as its pixel range.  With it, filter="trilinear" takes mips (the pyramid of
-    build_mips / ops.texture_mips) and want_lod appends lod f32 [H,W] to the tuple."""
+    build_mips / ops.texture_mips) and want_lod appends lod f32 [H,W] to the tuple.
+    samples in (2, 4) (dtp_op_mesh_view_aa): samples x samples centres per pixel, averaged (render_view has the rule); filter="trilinear"
+    then needs no clip_near.  want_coverage (any samples) appends coverage u8 [H,W], the number of the pixel's samples a face covers, last.
+    samples=1 without want_coverage is the call it always was."""
     from . import mesh as _mesh
     lib = _lib.load()
     H, W = (int(v) for v in (camera.size if size is None else size))
@@ -640,12 +643,24 @@ def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True,
         raise ValueError(f"size = ({H}, {W}): each side 1..{_lib.VIEW_MAX}")
     if filter not in ("bilinear", "trilinear"):
         raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
-    if not clip_near and (filter != "bilinear" or mips is not None or want_lod):
-        raise ValueError("filter, mips and want_lod need clip_near=True here (render_view(filter='trilinear') is the unclipped filtered frame)")
+    samples = _lib.view_samples_check(samples, H, W)
+    aa = samples > 1 or bool(want_coverage)
+    if not clip_near and not aa and (filter != "bilinear" or mips is not None or want_lod):
+        raise ValueError("filter, mips and want_lod need clip_near=True or samples > 1 here (render_view(filter='trilinear') is the unclipped "
+                         "filtered frame)")
+    if aa and filter == "bilinear" and (mips is not None or want_lod):
+        raise ValueError("mips and want_lod need filter='trilinear'")
     o, cam = _mesh.view_opts(**opts), camera.struct()
     image = torch.empty(H, W, 4, dtype=torch.uint8, device=texture.device)
     face_idx = torch.empty(H, W, dtype=torch.int32, device=texture.device) if want_face_idx else None
     depth = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_depth else None
+    if aa:
+        lod = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_lod else None
+        coverage = torch.empty(H, W, dtype=torch.uint8, device=texture.device) if want_coverage else None
+        check(lib.dtp_op_mesh_view_aa(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), C.byref(cam), H, W, C.byref(o),
+                                      int(filter == "trilinear"), int(bool(clip_near)), samples, ptr(image), ptr(face_idx), ptr(depth), ptr(lod),
+                                      ptr(coverage), int(bool(binned)), _stream()), "mesh_view_aa")
+        return (image, face_idx, depth) + ((lod,) if want_lod else ()) + ((coverage,) if want_coverage else ())
     if not clip_near:
         check(lib.dtp_op_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(o), ptr(image),
                                    ptr(face_idx), ptr(depth), int(bool(binned)), _stream()), "mesh_view")

@@ -27,7 +27,8 @@ extern "C" {
  * dtp_op_mesh_coverage) and picking (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan, dtp_op_mesh_pick) and the undo / redo journal
  * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) and the
  * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state)
- * and the view clipped at the near plane (dtp_mesh_view_clip, dtp_op_mesh_view_clip) are additions; nothing that existed at
+ * and the view clipped at the near plane (dtp_mesh_view_clip, dtp_op_mesh_view_clip) and the anti-aliased view (dtp_mesh_view_aa,
+ * dtp_op_mesh_view_aa) are additions; nothing that existed at
  * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -560,6 +561,34 @@ int dtp_mesh_view_mips(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, c
 int dtp_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                        const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s);
 
+/* ---------------------------------------------------------------- an anti-aliased view
+ * The views above take one sample per pixel, at its centre: silhouettes, UV-chart borders and creases are staircases that crawl from
+ * frame to frame, and a face about a pixel wide is there or not by chance.  The trilinear filter decides what is sampled INSIDE a face;
+ * nothing above decides which face is sampled.  dtp_mesh_view_aa takes samples x samples centres per pixel on an ordered grid and stores
+ * their average, in one pass.  No new arithmetic: the camera holds nothing that depends on the frame's size, so "the
+ * same camera at s H x s W" is a frame the sections above define, and the samples of pixel (i, j) are its pixels.
+ *
+ * samples = s in {1, 2, 4}: 1, 4 or 16 samples per pixel.  filter and clip: 0 or 1 each.  The FINE frame is what dtp_mesh_view (filter 0,
+ * clip 0), dtp_mesh_view_mips (filter 1, clip 0) or dtp_mesh_view_clip (clip 1, with that filter) writes for the same mesh, texture,
+ * pyramid, camera and options at size (s H) x (s W): every rule of those sections with s H, s W in place of H, W -- the snap by 128 s W
+ * and 128 s H, the centres 256 b + 128 of fine pixel b, the rays of clip, the footprint of filter 1 measured between the centres of
+ * neighbouring FINE pixels.  So lod comes out about log2(s) lower than at samples 1: each sample covers that much less of the texture.
+ *   image[i][j][ch]  = (sum of fine[s i + a][s j + b][ch] over a, b in 0 .. s - 1  +  s s / 2) >> log2(s s), per channel R, G, B, A: the
+ *                      rounded box average of the BYTES of the fine frame, each sample rounded to its byte before it is summed, the
+ *                      background's bytes where no face is.  With the default background 0,0,0,0 a silhouette pixel therefore
+ *                      carries its colour premultiplied by its coverage, and the coverage in alpha.
+ *   face_idx, depth, lod [i][j] (each or NULL; lod needs filter 1) = those of fine pixel (s i + s / 2, s j + s / 2): the sample just below
+ *                      and right of the pixel's centre; for s = 1 the pixel itself.
+ *   coverage[i][j]   device u8 [H][W] or NULL: how many of the pixel's samples a face covers, 0 .. s s.
+ * samples 1 writes the bytes of the call it stands for.  The fine frame exists nowhere: the samples are resolved on the chip (registers and LDS), and the
+ * view's per-mesh buffers are those of dtp_mesh_view whatever s is.  The checks are dtp_mesh_view_clip's (mips and lod must be NULL
+ * with filter 0), plus clip in {0, 1}, samples in {1, 2, 4} and s H, s W <= 4096 (the pixel ranges of a face are packed in 16 bits and
+ * there are 4096 bin counters, of the fine frame); every check comes before any device call and a refused call writes nothing.  The call
+ * only enqueues on `s`: a memset and four kernels.  Not here: a rotated or jittered pattern, anisotropic filtering. */
+int dtp_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                     const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
+                     uint8_t* coverage, dtp_stream s);
+
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
  * the last 10 copies and uploads one on Ctrl+Z (kit_app/.../python/ui/brush.py:52-77,131-137; redo is a TODO there).  A journal keeps, on
@@ -1022,6 +1051,11 @@ int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, con
  * range: the arm against which the ranges are tested.  The frame is the same bytes either way. */
 int dtp_op_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                           const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, int binned, dtp_stream s);
+/* dtp_mesh_view_aa (the contract: see "an anti-aliased view") with the binning switched, as dtp_op_mesh_view_clip switches it: binned 1
+ * is dtp_mesh_view_aa exactly.  The frame is the same bytes either way. */
+int dtp_op_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                        const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
+                        uint8_t* coverage, int binned, dtp_stream s);
 #ifdef __cplusplus
 }
 #endif
