@@ -90,6 +90,21 @@ def view_samples_check(samples, H, W):
     return samples
 
 
+VIEW_MAX_ANISO = 16  # the most taps of an anisotropic sample (dtp_mesh_view_aniso)
+
+
+def view_anisotropy_check(anisotropy, filter, want_taps, least=1):
+    """ValueError for what render_view / ops.mesh_view refuse of `anisotropy` and `want_taps`; -> anisotropy as an int.  least: the
+    smallest anisotropy that goes to dtp_mesh_view_aniso (below it, want_taps has no map to return)."""
+    if isinstance(anisotropy, bool) or not isinstance(anisotropy, int) or not 1 <= anisotropy <= VIEW_MAX_ANISO:
+        raise ValueError(f"anisotropy = {anisotropy!r}: an integer in 1..{VIEW_MAX_ANISO} (the most taps along the footprint)")
+    if anisotropy >= least and filter != "trilinear":
+        raise ValueError(f"anisotropy = {anisotropy} needs filter='trilinear' (the taps are trilinear samples)")
+    if want_taps and anisotropy < least:
+        raise ValueError("want_taps needs anisotropy > 1")
+    return anisotropy
+
+
 class MipLevels(C.Structure):  # dtp_mip_levels
     _fields_ = [("levels", C.c_int), ("h", C.c_int * 16), ("w", C.c_int * 16), ("offset", C.c_uint64 * 16), ("bytes", C.c_uint64)]
 
@@ -243,6 +258,10 @@ SYMBOLS = {
     "dtp_mesh_view_aa": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dtp_op_mesh_view_aa": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i,
                                  _vp]),
+    "dtp_mesh_view_aniso": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp]),
+    "dtp_op_mesh_view_aniso": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _i, _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

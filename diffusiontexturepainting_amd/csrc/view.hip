@@ -14,6 +14,9 @@
 // It is a second template parameter; the instantiations without it are the code they were.  dtp_mesh_view_aa draws the
 // same frames with s x s samples per pixel: project, scan and fill run for the frame of s H x s W, and a raster kernel of its own
 // (view_raster_aa_kernel) keeps a winner per sample in registers and sums the samples' bytes in LDS: the larger frame is never stored.
+// dtp_mesh_view_aniso is a third value of the filter parameter of both raster kernels: the two footprint vectors are
+// kept apart, the level comes from the shorter one, and up to 16 trilinear taps along the longer one are averaged in a rolled loop.
+// The instantiations with filter 0 and 1 are the code they were.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stddef.h>
@@ -49,6 +52,9 @@ struct ViewShade { int shade; float ambient, unpainted[3]; unsigned int backgrou
 // them out, and the map of lod (or null)
 template <int FILTER> struct ViewFilter {};
 template <> struct ViewFilter<1> { const unsigned int* mips; float* lod; int levels; };
+// 2: up to max_aniso trilinear taps along the longer axis of the footprint, the level from the shorter one (dtp_mesh_view_aniso, DESIGN.md
+// 3.29); the map of the number of taps (or null)
+template <> struct ViewFilter<2> { const unsigned int* mips; float* lod; int levels, max_aniso; unsigned char* taps; };
 // and of the near-plane clip: what the ray of a pixel and the clip itself need of the camera
 template <int CLIP> struct ViewClip {};
 template <> struct ViewClip<1> { float fx, fy, near; };
@@ -216,7 +222,9 @@ __device__ __forceinline__ void view_sample(const unsigned int* __restrict__ tex
 
 // The texel of a covered centre: `best` won pixel (row, col) of an H x W frame, centre (px, py), ray (gx, gy) (CLIP alone), with q_k = bq
 // and their sum best_d.  The perspective-correct UV, the sample (FILTER 1: the footprint from the face at the two neighbouring centres,
-// the level walk, two levels blended; lod is written), the shade, the bytes with alpha 255.  This is the text of view_raster_kernel's
+// the level walk, two levels blended; lod is written.  FILTER 2: the two footprint vectors kept apart, the level from the shorter one,
+// ntap trilinear taps along the longer one in a rolled loop, their plain mean; lod and ntap are written), the shade, the bytes with
+// alpha 255.  This is the text of view_raster_kernel's
 // own shading below, for the anti-aliased kernel alone: calling it from view_raster_kernel too changes that kernel's register
 // allocation and argument loads, and the instantiations of 3.24 - 3.27 are to stay the code they are.  A change to one is a change to
 // both; the anti-aliased tests compare the two byte for byte.
@@ -224,7 +232,7 @@ template <int FILTER, int CLIP>
 __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ rec, const float* __restrict__ uvs, const unsigned int* __restrict__ tex,
                                                    int TH, int TW, int H, int W, ViewShade sh, ViewFilter<FILTER> fl,
                                                    ViewClip<CLIP> cl, int best, const float bq[3], float best_d, int col, int row, int px,
-                                                   int py, float gx, float gy, float& lod) {
+                                                   int py, float gx, float gy, float& lod, int& ntap) {
   const float* uv = uvs + (size_t)6 * best;
   const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
   float tc[4];
@@ -256,12 +264,27 @@ __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ r
     }
     const float dx = (qx[0] + qx[1]) + qx[2], dy = (qy[0] + qy[1]) + qy[2];
     float rho2 = INFINITY;  // beyond the horizon, or a footprint that is not finite: the last level
+    [[maybe_unused]] float du = 0.f, dv = 0.f;  // FILTER 2: the longer axis of the footprint in UV, along which the taps lie
+    [[maybe_unused]] int n_taps = 1;
     if (isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f) {
       const float fw = (float)TW, fh = (float)TH;
-      const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
-      const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
-      rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
-      if (!isfinite(rho2)) rho2 = INFINITY;
+      if constexpr (FILTER == 1) {
+        const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
+        const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
+        rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
+        if (!isfinite(rho2)) rho2 = INFINITY;
+      } else {
+        const float dua = interp(qx, uv[0], uv[2], uv[4]) / dx - u, dva = interp(qx, uv[1], uv[3], uv[5]) / dx - v;
+        const float dub = interp(qy, uv[0], uv[2], uv[4]) / dy - u, dvb = interp(qy, uv[1], uv[3], uv[5]) / dy - v;
+        const float ax = dua * fw, ay = dva * fh, bx = dub * fw, by = dvb * fh;
+        const float la2 = ax * ax + ay * ay, lb2 = bx * bx + by * by;
+        if (isfinite(la2) && isfinite(lb2)) {
+          const float pmax2 = fmaxf(la2, lb2), pmin2 = fminf(la2, lb2), m = (float)(fl.max_aniso * fl.max_aniso);
+          du = la2 >= lb2 ? dua : dub; dv = la2 >= lb2 ? dva : dvb;
+          rho2 = fminf(pmax2, fmaxf(fmaxf(pmin2, 1.0f), pmax2 / m));  // the shorter axis; no finer than a texel, nor than max_aniso taps span
+          while (n_taps < fl.max_aniso && !(pmax2 <= (float)(n_taps * n_taps) * rho2)) ++n_taps;
+        }
+      }
     }
     // level l of hl x wl texels at `at` of the pyramid (l >= 1), level l + 1 at `next`; p4 = 4^l
     int l = 0, hl = TH, wl = TW;
@@ -273,12 +296,35 @@ __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ r
     }
     const float f = (l + 1 == fl.levels || rho2 <= p4) ? 0.f : ((rho2 / p4) - 1.0f) / 3.0f;
     lod = (float)l + f;
-    view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
-    if (f > 0.f) {
-      float tn[4];
-      view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
+    if constexpr (FILTER == 1) {
+      view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
+      if (f > 0.f) {
+        float tn[4];
+        view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
 #pragma unroll
-      for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+        for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+      }
+    } else {  // n_taps trilinear samples of this l and f, spread along (du, dv) about (u, v); their plain average
+      const unsigned int* here = l == 0 ? tex : fl.mips + at;
+      const float twice = (float)(2 * n_taps);
+      float sum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+      for (int i = 0; i < n_taps; ++i) {
+        const float o = (float)(2 * i + 1) / twice - 0.5f;
+        const float ui = u + du * o, vi = v + dv * o;
+        view_sample(here, hl, wl, ui, vi, tc);
+        if (f > 0.f) {
+          float tn[4];
+          view_sample(fl.mips + next, mip_half(hl), mip_half(wl), ui, vi, tn);
+#pragma unroll
+          for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+        }
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) sum[ch] = sum[ch] + tc[ch];
+      }
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) tc[ch] = sum[ch] / (float)n_taps;
+      ntap = n_taps;
     }
   }
   const float s = sh.shade ? sh.ambient + (1.0f - sh.ambient) * fabsf(rec[best].nzu) : 1.0f;
@@ -379,6 +425,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   const size_t pix = (size_t)row * W + col;
   unsigned int out = sh.background;
   float dist = 0.f, lod = 0.f;
+  [[maybe_unused]] int ntap = 0;
   if (best >= 0) {
     const float* uv = uvs + (size_t)6 * best;
     const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
@@ -411,12 +458,27 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
       }
       const float dx = (qx[0] + qx[1]) + qx[2], dy = (qy[0] + qy[1]) + qy[2];
       float rho2 = INFINITY;  // beyond the horizon, or a footprint that is not finite: the last level
+      [[maybe_unused]] float du = 0.f, dv = 0.f;  // FILTER 2: the longer axis of the footprint in UV, along which the taps lie
+      [[maybe_unused]] int n_taps = 1;
       if (isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f) {
         const float fw = (float)TW, fh = (float)TH;
-        const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
-        const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
-        rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
-        if (!isfinite(rho2)) rho2 = INFINITY;
+        if constexpr (FILTER == 1) {
+          const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
+          const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
+          rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
+          if (!isfinite(rho2)) rho2 = INFINITY;
+        } else {
+          const float dua = interp(qx, uv[0], uv[2], uv[4]) / dx - u, dva = interp(qx, uv[1], uv[3], uv[5]) / dx - v;
+          const float dub = interp(qy, uv[0], uv[2], uv[4]) / dy - u, dvb = interp(qy, uv[1], uv[3], uv[5]) / dy - v;
+          const float ax = dua * fw, ay = dva * fh, bx = dub * fw, by = dvb * fh;
+          const float la2 = ax * ax + ay * ay, lb2 = bx * bx + by * by;
+          if (isfinite(la2) && isfinite(lb2)) {
+            const float pmax2 = fmaxf(la2, lb2), pmin2 = fminf(la2, lb2), m = (float)(fl.max_aniso * fl.max_aniso);
+            du = la2 >= lb2 ? dua : dub; dv = la2 >= lb2 ? dva : dvb;
+            rho2 = fminf(pmax2, fmaxf(fmaxf(pmin2, 1.0f), pmax2 / m));  // the shorter axis; no finer than a texel, nor than max_aniso taps span
+            while (n_taps < fl.max_aniso && !(pmax2 <= (float)(n_taps * n_taps) * rho2)) ++n_taps;
+          }
+        }
       }
       // level l of hl x wl texels at `at` of the pyramid (l >= 1), level l + 1 at `next`; p4 = 4^l
       int l = 0, hl = TH, wl = TW;
@@ -428,12 +490,35 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
       }
       const float f = (l + 1 == fl.levels || rho2 <= p4) ? 0.f : ((rho2 / p4) - 1.0f) / 3.0f;
       lod = (float)l + f;
-      view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
-      if (f > 0.f) {
-        float tn[4];
-        view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
+      if constexpr (FILTER == 1) {
+        view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
+        if (f > 0.f) {
+          float tn[4];
+          view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
 #pragma unroll
-        for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+          for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+        }
+      } else {  // n_taps trilinear samples of this l and f, spread along (du, dv) about (u, v); their plain average
+        const unsigned int* here = l == 0 ? tex : fl.mips + at;
+        const float twice = (float)(2 * n_taps);
+        float sum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int i = 0; i < n_taps; ++i) {
+          const float o = (float)(2 * i + 1) / twice - 0.5f;
+          const float ui = u + du * o, vi = v + dv * o;
+          view_sample(here, hl, wl, ui, vi, tc);
+          if (f > 0.f) {
+            float tn[4];
+            view_sample(fl.mips + next, mip_half(hl), mip_half(wl), ui, vi, tn);
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
+          }
+#pragma unroll
+          for (int ch = 0; ch < 4; ++ch) sum[ch] = sum[ch] + tc[ch];
+        }
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) tc[ch] = sum[ch] / (float)n_taps;
+        ntap = n_taps;
       }
     }
     const float s = sh.shade ? sh.ambient + (1.0f - sh.ambient) * fabsf(rec[best].nzu) : 1.0f;
@@ -451,6 +536,9 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   if (depth) depth[pix] = dist;
   if constexpr (FILTER != 0) {
     if (fl.lod) fl.lod[pix] = lod;
+  }
+  if constexpr (FILTER == 2) {
+    if (fl.taps) fl.taps[pix] = (unsigned char)ntap;
   }
 }
 
@@ -582,6 +670,7 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
     for (int j = 0; j < P; ++j) f = j == p ? best[j] : f;
     unsigned int out = sh.background;
     float dist = 0.f, lod = 0.f;
+    int ntap = 0;
     if (f >= 0) {
       const ViewRec& r = rec[f];
       const int px = 256 * col + 128, py = 256 * row + 128;
@@ -605,7 +694,7 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
         for (int c = 0; c < 3; ++c) q[c] = w[c] * r.iw[c];
       }
       const float d = (q[0] + q[1]) + q[2];
-      out = view_shade<FILTER, CLIP>(rec, uvs, tex, TH, TW, FH, FW, sh, fl, cl, f, q, d, col, row, px, py, gx, gy, lod);
+      out = view_shade<FILTER, CLIP>(rec, uvs, tex, TH, TW, FH, FW, sh, fl, cl, f, q, d, col, row, px, py, gx, gy, lod, ntap);
       dist = 1.0f / d;
     }
     const int at = (sy / S) * 16 + sx / S;  // the output pixel of the tile that this sample belongs to
@@ -618,6 +707,9 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
       if (depth) depth[pix] = dist;
       if constexpr (FILTER != 0) {
         if (fl.lod) fl.lod[pix] = lod;
+      }
+      if constexpr (FILTER == 2) {
+        if (fl.taps) fl.taps[pix] = (unsigned char)ntap;
       }
     }
   }
@@ -648,11 +740,11 @@ int view_reserve(const MeshGeom& g) {
 }
 
 // every check, then zero the counters -> project -> scan -> fill -> raster on s; nothing waits
-// filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null); clip: the faces across the near
-// plane are drawn too
+// filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null); 2 = up to max_aniso trilinear
+// taps along the footprint, with the maps of lod and of taps (or null); clip: the faces across the near plane are drawn too
 int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* o,
              uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s, int filter = 0, const uint8_t* mips = nullptr, float* lod = nullptr,
-             int clip = 0, int samples = 0, uint8_t* coverage = nullptr) {
+             int clip = 0, int samples = 0, uint8_t* coverage = nullptr, int max_aniso = 1, uint8_t* taps = nullptr) {
   if (!mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
   if (const char* why = view_check(texture, TH, TW, cam, H, W, o, image, face_idx, depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
   if (samples)
@@ -683,6 +775,8 @@ int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, in
   const dim3 tiles((W + 15) / 16, (H + 15) / 16);
   ViewFilter<1> fl;
   fl.mips = (const unsigned int*)mips; fl.lod = lod; fl.levels = filter ? lay.levels : 1;
+  ViewFilter<2> fa;
+  fa.mips = fl.mips; fa.lod = lod; fa.levels = fl.levels; fa.max_aniso = max_aniso; fa.taps = taps;
   ViewClip<1> cl;
   cl.fx = cam->fx; cl.fy = cam->fy; cl.near = cam->near;
 #define RASTER(FILTER, CLIP, fl, cl)                                                                                                   \
@@ -698,7 +792,9 @@ int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, in
     else if (samples == 2) RASTER_AA(FILTER, CLIP, 2, fl, cl); \
     else RASTER_AA(FILTER, CLIP, 4, fl, cl);           \
   } while (0)
-  if (filter && clip) RASTER_S(1, 1, fl, cl);
+  if (filter == 2 && clip) RASTER_S(2, 1, fa, cl);
+  else if (filter == 2) RASTER_S(2, 0, fa, ViewClip<0>());
+  else if (filter && clip) RASTER_S(1, 1, fl, cl);
   else if (filter) RASTER_S(1, 0, fl, ViewClip<0>());
   else if (clip) RASTER_S(0, 1, ViewFilter<0>(), cl);
   else RASTER_S(0, 0, ViewFilter<0>(), ViewClip<0>());
@@ -780,6 +876,24 @@ int dtp_op_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, 
   if (!filter && (mips || lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
   if (samples != 1 && samples != 2 && samples != 4) { dtp_set_error("%s: %s", who, view_aa_check(samples, 1, 1)); return DTP_ERR_ARG; }
   return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, filter, mips, lod, clip, samples, coverage);
+}
+
+int dtp_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                        const dtp_view_opts* opts, int clip, int samples, int max_aniso, uint8_t* image, int* face_idx, float* depth, float* lod,
+                        uint8_t* taps, uint8_t* coverage, dtp_stream s) {
+  return dtp_op_mesh_view_aniso(mesh, texture, TH, TW, mips, cam, H, W, opts, clip, samples, max_aniso, image, face_idx, depth, lod, taps, coverage, 1, s);
+}
+
+// samples 1 without a coverage map runs the plain raster kernel, as dtp_mesh_view_mips does; every other call the anti-aliased one
+int dtp_op_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                           const dtp_view_opts* opts, int clip, int samples, int max_aniso, uint8_t* image, int* face_idx, float* depth, float* lod,
+                           uint8_t* taps, uint8_t* coverage, int binned, dtp_stream s) {
+  const char* who = binned == 1 ? "dtp_mesh_view_aniso" : "dtp_op_mesh_view_aniso";
+  if (max_aniso < 1 || max_aniso > VIEW_MAX_ANISO) { dtp_set_error("%s: max_aniso must lie in 1..%d", who, VIEW_MAX_ANISO); return DTP_ERR_ARG; }
+  if (clip != 0 && clip != 1) { dtp_set_error("%s: clip is 0 or 1", who); return DTP_ERR_ARG; }
+  if (samples != 1 && samples != 2 && samples != 4) { dtp_set_error("%s: %s", who, view_aa_check(samples, 1, 1)); return DTP_ERR_ARG; }
+  return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, 2, mips, lod, clip,
+                  samples == 1 && !coverage ? 0 : samples, coverage, max_aniso, taps);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@ constexpr int VIEW_MAX = 4096;                             // the largest frame 
 constexpr int VIEW_BIN_SHIFT = 6, VIEW_BIN = 1 << VIEW_BIN_SHIFT;  // bins of 64 x 64 pixels = 4 x 4 tiles of 16 x 16
 constexpr int VIEW_MAX_BINS = (VIEW_MAX / VIEW_BIN) * (VIEW_MAX / VIEW_BIN);  // 4096: one workgroup scans them
 constexpr int VIEW_MAX_TEX = 32768;                        // as the strokes: a texture side
+constexpr int VIEW_MAX_ANISO = 16;                         // the most taps of an anisotropic sample (dtp_mesh_view_aniso)
 
 // The bins [bx0, bx1] x [by0, by1] that a face's pixel ranges (x0 | x1 << 16, y0 | y1 << 16; not empty) meet.  true: a SMALL face, at
 // most 2 x 2 bins, which gets one entry in each of them; false: a LARGE face, which every tile streams.

@@ -528,7 +528,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def render_view(self, mesh, texture, camera, size=None, cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128),
                     background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False, filter="bilinear", mips=None,
-                    want_lod=False, clip_near=False, samples=1, want_coverage=False):
+                    want_lod=False, clip_near=False, samples=1, want_coverage=False, anisotropy=1, want_taps=False):
         """A perspective view of the whole painted mesh (dtp_mesh_view; in the Kit app the viewport is Omniverse RTX):
         `mesh` from load_mesh, `texture` uint8 [TH, TW, 4] on the model's device, `camera` from mesh.view_camera, size = (H, W) (default
         the camera's; each side 1..4096).  -> the frame, uint8 [H, W, 4] on the device (RGB the texture under its alpha over `unpainted`,
@@ -557,9 +557,18 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         and the coverage in alpha.  face_idx, depth and lod are those of the sample just below and right of the pixel's centre; lod
         comes out about log2(samples) lower, because a sample covers that much less of the texture.  samples x each side <= 4096, so
         1080p takes samples=2.  want_coverage: also uint8 [H, W], how many of the pixel's samples a face covers (0 .. samples^2), last
-        in the tuple.  samples=1 without want_coverage is the call it always was, launch for launch."""
+        in the tuple.  samples=1 without want_coverage is the call it always was, launch for launch.
+        anisotropy=2..16 with filter="trilinear" (dtp_mesh_view_aniso): the trilinear filter takes one level from the
+        LONGER axis of the pixel's footprint, so a floor running away from the eye -- every surface of a room seen from inside -- is
+        sampled several levels too coarse and turns grey.  With this the level comes from the shorter axis (never finer than a texel,
+        never more than `anisotropy` times finer than the longer axis) and up to `anisotropy` trilinear taps spread along the longer
+        axis are averaged: stripes across the line of sight stay stripes.  Works with clip_near, samples, mips, out, live, want_lod and
+        want_coverage as before; a magnified frame is still the bilinear one byte for byte, and visibility, face_idx and depth do not
+        change.  want_taps: also uint8 [H, W], the number of taps the pixel took (0 where no face is), after lod and before coverage.
+        anisotropy=1 is the call without the keyword."""
         if filter not in ("bilinear", "trilinear"):
             raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
+        anisotropy = _lib.view_anisotropy_check(anisotropy, filter, want_taps, least=2)
         trilinear = filter == "trilinear"
         if not trilinear and (mips is not None or want_lod):
             raise ValueError("mips and want_lod need filter='trilinear'")
@@ -595,6 +604,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             depth = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_depth else None
             lod = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_lod else None
             coverage = torch.empty(H, W, dtype=torch.uint8, device=self._device) if want_coverage else None
+            taps = torch.empty(H, W, dtype=torch.uint8, device=self._device) if want_taps else None
             if build:
                 key = (texture.shape[0], texture.shape[1])
                 if key not in self._view_mips:
@@ -608,7 +618,11 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         vs = C.c_void_p(self.view_stream.cuda_stream)
         if trilinear and build:
             check(self._lib.dtp_texture_mips(ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), need, vs), "dtp_texture_mips")
-        if aa:
+        if anisotropy > 1:
+            check(self._lib.dtp_mesh_view_aniso(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), C.byref(cam), H, W,
+                                                C.byref(opts), int(bool(clip_near)), samples, anisotropy, ptr(out), ptr(face_idx), ptr(depth),
+                                                ptr(lod), ptr(taps), ptr(coverage), vs), "dtp_mesh_view_aniso")
+        elif aa:
             check(self._lib.dtp_mesh_view_aa(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips) if trilinear else None,
                                              C.byref(cam), H, W, C.byref(opts), int(trilinear), int(bool(clip_near)), samples, ptr(out),
                                              ptr(face_idx), ptr(depth), ptr(lod), ptr(coverage), vs), "dtp_mesh_view_aa")
@@ -626,10 +640,10 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         for t in (texture, given, None if build else mips):
             if t is not None:
                 t.record_stream(self.view_stream)
-        for t in (None if given is not None else out, face_idx, depth, lod, coverage):
+        for t in (None if given is not None else out, face_idx, depth, lod, taps, coverage):
             if t is not None:
                 t.record_stream(cur)
-        extra = tuple(t for t in (face_idx, depth, lod, coverage) if t is not None)
+        extra = tuple(t for t in (face_idx, depth, lod, taps, coverage) if t is not None)
         return (out,) + extra if extra else out
 
     def _mip_bytes(self, texture):

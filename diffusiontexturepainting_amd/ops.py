@@ -626,7 +626,7 @@ def mesh_pick(mesh, origins, directions):
 
 
 def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True, want_depth=True, clip_near=False, filter="bilinear", mips=None,
-              want_lod=False, samples=1, want_coverage=False, **opts):
+              want_lod=False, samples=1, want_coverage=False, anisotropy=None, want_taps=False, **opts):
     """dtp_op_mesh_view: the frame of MI355ConditionalInpainter.render_view on the current stream -> (image u8 [H,W,4], face_idx i32
     [H,W] or None, depth f32 [H,W] or None).  binned=False puts every drawn face on the list that every tile streams (the arm a
     measurement compares the bins with); the frame is the same bytes.  opts: cull, flip_normals, shade, ambient, unpainted, background.
@@ -635,7 +635,11 @@ def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True,
     build_mips / ops.texture_mips) and want_lod appends lod f32 [H,W] to the tuple.
     samples in (2, 4) (dtp_op_mesh_view_aa): samples x samples centres per pixel, averaged (render_view has the rule); filter="trilinear"
     then needs no clip_near.  want_coverage (any samples) appends coverage u8 [H,W], the number of the pixel's samples a face covers, last.
-    samples=1 without want_coverage is the call it always was."""
+    samples=1 without want_coverage is the call it always was.
+    anisotropy in 1..16 (dtp_op_mesh_view_aniso; needs filter="trilinear" and mips): up to that many trilinear taps along the longer axis
+    of the footprint, the level from the shorter one (render_view has the rule), with clip_near, samples and binned as above; 1 runs that
+    entry too and gives the trilinear frame.  want_taps appends taps u8 [H,W], the number of taps per pixel, after lod and before
+    coverage.  None is today's routing."""
     from . import mesh as _mesh
     lib = _lib.load()
     H, W = (int(v) for v in (camera.size if size is None else size))
@@ -644,8 +648,12 @@ def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True,
     if filter not in ("bilinear", "trilinear"):
         raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
     samples = _lib.view_samples_check(samples, H, W)
+    if anisotropy is None and want_taps:
+        raise ValueError("want_taps needs anisotropy (an integer in 1..16)")
+    if anisotropy is not None:
+        anisotropy = _lib.view_anisotropy_check(anisotropy, filter, want_taps, least=1)
     aa = samples > 1 or bool(want_coverage)
-    if not clip_near and not aa and (filter != "bilinear" or mips is not None or want_lod):
+    if not clip_near and not aa and anisotropy is None and (filter != "bilinear" or mips is not None or want_lod):
         raise ValueError("filter, mips and want_lod need clip_near=True or samples > 1 here (render_view(filter='trilinear') is the unclipped "
                          "filtered frame)")
     if aa and filter == "bilinear" and (mips is not None or want_lod):
@@ -654,6 +662,14 @@ def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True,
     image = torch.empty(H, W, 4, dtype=torch.uint8, device=texture.device)
     face_idx = torch.empty(H, W, dtype=torch.int32, device=texture.device) if want_face_idx else None
     depth = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_depth else None
+    if anisotropy is not None:
+        lod = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_lod else None
+        taps = torch.empty(H, W, dtype=torch.uint8, device=texture.device) if want_taps else None
+        coverage = torch.empty(H, W, dtype=torch.uint8, device=texture.device) if want_coverage else None
+        check(lib.dtp_op_mesh_view_aniso(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], ptr(mips), C.byref(cam), H, W, C.byref(o),
+                                         int(bool(clip_near)), samples, anisotropy, ptr(image), ptr(face_idx), ptr(depth), ptr(lod), ptr(taps),
+                                         ptr(coverage), int(bool(binned)), _stream()), "mesh_view_aniso")
+        return (image, face_idx, depth) + ((lod,) if want_lod else ()) + ((taps,) if want_taps else ()) + ((coverage,) if want_coverage else ())
     if aa:
         lod = torch.empty(H, W, dtype=torch.float32, device=texture.device) if want_lod else None
         coverage = torch.empty(H, W, dtype=torch.uint8, device=texture.device) if want_coverage else None

@@ -28,7 +28,7 @@ extern "C" {
  * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) and the
  * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state)
  * and the view clipped at the near plane (dtp_mesh_view_clip, dtp_op_mesh_view_clip) and the anti-aliased view (dtp_mesh_view_aa,
- * dtp_op_mesh_view_aa) are additions; nothing that existed at
+ * dtp_op_mesh_view_aa) and the anisotropic view (dtp_mesh_view_aniso, dtp_op_mesh_view_aniso) are additions; nothing that existed at
  * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -450,7 +450,7 @@ int dtp_mesh_path_plan(const dtp_mesh_hit* hits, int n, float stamp_distance, dt
  * c_ch = (t_ch t_A + (unpainted_ch / 255) (1 - t_A)) s for R, G, B; the byte is (unsigned char)(fminf(c_ch, 1) 255 + 0.5f) and the
  * alpha byte 255.  face_idx = the winner, depth = 1.0f / d (the distance from the eye along the view direction).  A pixel no face
  * covers gets the four bytes of background, face_idx -1, depth 0.  No colour management, no mip or anisotropic filtering, one sample
- * per pixel: the frame aliases under minification and along silhouettes.
+ * per pixel: the frame aliases under minification and along silhouettes (the sections below add each of them as an entry of its own).
  *
  * dtp_mesh_view: texture device u8 [TH][TW][4] (1..32768 a side), image device u8 [H][W][4], face_idx device i32 [H][W] or NULL,
  * depth device f32 [H][W] or NULL; all 4-byte aligned; 1 <= H, W <= 4096; ambient in 0..1; cull, flip_normals, shade 0 or 1.  Every
@@ -510,7 +510,8 @@ int dtp_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const 
  *  6. t_l = the taps and blend of byte / 255 of dtp_mesh_view at level l with that level's h[l], w[l] in place of TH, TW.  If f > 0,
  *     t = t_l + (t_(l + 1) - t_l) f per channel (a difference, a product, a sum); otherwise t = t_l and level l + 1 is not read.
  *     The shade, the unpainted mix, the byte conversion and the background are dtp_mesh_view's.
- * A frame with rho2 <= 1 everywhere is dtp_mesh_view's frame byte for byte.  No anisotropic filtering, no anti-aliasing of silhouettes. */
+ * A frame with rho2 <= 1 everywhere is dtp_mesh_view's frame byte for byte.  No anti-aliasing of silhouettes (dtp_mesh_view_aa), and ONE
+ * level from the longer axis of the footprint: a surface at a grazing angle is sampled too coarse (dtp_mesh_view_aniso samples along it). */
 typedef struct { int levels; int h[16], w[16]; uint64_t offset[16]; uint64_t bytes; } dtp_mip_levels;
 int dtp_mip_layout(int TH, int TW, dtp_mip_levels* out);
 int dtp_texture_mips(const uint8_t* texture, int TH, int TW, uint8_t* mips, uint64_t mips_bytes, dtp_stream s);
@@ -584,10 +585,52 @@ int dtp_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, c
  * view's per-mesh buffers are those of dtp_mesh_view whatever s is.  The checks are dtp_mesh_view_clip's (mips and lod must be NULL
  * with filter 0), plus clip in {0, 1}, samples in {1, 2, 4} and s H, s W <= 4096 (the pixel ranges of a face are packed in 16 bits and
  * there are 4096 bin counters, of the fine frame); every check comes before any device call and a refused call writes nothing.  The call
- * only enqueues on `s`: a memset and four kernels.  Not here: a rotated or jittered pattern, anisotropic filtering. */
+ * only enqueues on `s`: a memset and four kernels.  Not here: a rotated or jittered pattern; anisotropic filtering is dtp_mesh_view_aniso, below,
+ * with the same samples. */
 int dtp_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                      const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
                      uint8_t* coverage, dtp_stream s);
+
+/* ---------------------------------------------------------------- an anisotropic view
+ * The trilinear filter picks ONE level from the LONGER of the two footprint axes.  A surface seen at a grazing angle -- the floor under
+ * the camera, the walls of a room painted from inside: the poses clip exists for -- has a footprint many times longer than wide, is
+ * sampled several levels too coarse, and what was painted across the line of sight turns grey a few metres out.
+ * dtp_mesh_view_aniso takes the level from the SHORTER axis instead and averages up to max_aniso trilinear taps spread along the longer
+ * one.  It is an addition to the dtp_mesh_view_mips contract: fp32, one rounded operation at a time in the order written, no
+ * contraction; nothing is compared under a tolerance.  M = max_aniso, an integer in 1..16.  Per covered pixel:
+ *  1. (u, v), the two neighbour evaluations of the winner face and the two footprint vectors in level-0 texels are those of steps 1-3
+ *     of dtp_mesh_view_mips (the integer path, or the ray path of a face across the near plane: see dtp_mesh_view_clip, filter 1):
+ *     du_a = u'_x - u, dv_a = v'_x - v, a = (du_a TW, dv_a TH); du_b, dv_b, b likewise from the y neighbour; la2 = a.x a.x + a.y a.y,
+ *     lb2 = b.x b.x + b.y b.y.
+ *  2. If a neighbour's d' is not finite or not > 0, or la2 or lb2 is not finite: the level is L - 1, f = 0, N = 1, one tap at (u, v) --
+ *     the beyond-the-horizon branch of dtp_mesh_view_mips.  (That rule takes fmaxf of the two, which ignores a NaN on one axis alone;
+ *     here such a pixel takes this branch.  It needs UVs whose products overflow fp32.)
+ *  3. Otherwise pmax2 = fmaxf(la2, lb2), pmin2 = fminf(la2, lb2); the major axis is a if la2 >= lb2, else b, and (du, dv) is the major
+ *     axis's UV difference BEFORE the scale by TW, TH.
+ *  4. rho2 = fminf(pmax2, fmaxf(fmaxf(pmin2, 1.0f), pmax2 / (float)(M M))): the level comes from the minor axis, is never finer than a
+ *     texel, never more than M times finer than the major axis asks for, and never coarser than the trilinear one.
+ *  5. N = the smallest n in 1..M with pmax2 <= (float)(n n) rho2 (the product rounded once); M if there is none.
+ *  6. l and f from rho2 by step 5 of dtp_mesh_view_mips, unchanged; lod = (float)l + f.
+ *  7. For i = 0 .. N - 1: o_i = (float)(2 i + 1) / (float)(2 N) - 0.5f; u_i = u + du o_i, v_i = v + dv o_i (a product, a sum);
+ *     t_i = step 6 of dtp_mesh_view_mips at (u_i, v_i) with this l and f for every tap: level l + 1 is not read when f = 0, and the
+ *     taps clamp at the level's border as they do there.
+ *  8. t = (((t_0 + t_1) + t_2) + ... + t_(N-1)) / (float)N per channel, all four channels, plain: the same non-weighted rule as the bilinear
+ *     blend and the level blend, so a tap on an unpainted texel pulls colour and alpha towards 0 as a bilinear tap does.
+ *  9. The shade, the unpainted mix, the byte conversion and the background are dtp_mesh_view's.
+ * What follows from the rule: M = 1 gives rho2 = pmax2, N = 1 and o_0 = 0, so image, lod, face_idx and depth are dtp_mesh_view_mips'
+ * byte for byte; where pmax2 <= 1 (magnified) N = 1, l = 0, f = 0 and the pixel is dtp_mesh_view's; where la2 == lb2 >= 1 the pixel is
+ * the trilinear one; visibility, face_idx and depth never depend on the filter.  Not here: elliptical (EWA) weights, the true axes of a
+ * sheared footprint (the longer of the two screen-axis vectors is the major axis), an alpha-weighted tap average.
+ *
+ * dtp_mesh_view_aniso: the arguments, checks, buffers and launches (a memset and four kernels) of dtp_mesh_view_aa with the filter
+ * implied: mips is required (it may be NULL only when the layout has 1 level), clip in {0, 1}, samples in {1, 2, 4} with the fine
+ * frame's rules (the footprint is measured between neighbouring FINE pixels), plus max_aniso in 1..16 (DTP_ERR_ARG outside, naming the
+ * range) and taps: device u8 [H][W] or NULL, the N of the pixel (of the sample that stores face_idx, depth and lod), 0 where no face
+ * is.  Every check comes before any device call and a refused call writes nothing.  max_aniso 1 is legal and runs this entry's own
+ * kernels. */
+int dtp_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                        const dtp_view_opts* opts, int clip, int samples, int max_aniso, uint8_t* image, int* face_idx, float* depth,
+                        float* lod, uint8_t* taps, uint8_t* coverage, dtp_stream s);
 
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
@@ -1056,6 +1099,11 @@ int dtp_op_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW
 int dtp_op_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                         const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
                         uint8_t* coverage, int binned, dtp_stream s);
+/* dtp_mesh_view_aniso (the contract: see "an anisotropic view") with the binning switched, as dtp_op_mesh_view_aa switches it: binned 1
+ * is dtp_mesh_view_aniso exactly.  The frame is the same bytes either way. */
+int dtp_op_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
+                           const dtp_view_opts* opts, int clip, int samples, int max_aniso, uint8_t* image, int* face_idx, float* depth,
+                           float* lod, uint8_t* taps, uint8_t* coverage, int binned, dtp_stream s);
 #ifdef __cplusplus
 }
 #endif
