@@ -105,6 +105,9 @@ def view_anisotropy_check(anisotropy, filter, want_taps, least=1):
     return anisotropy
 
 
+SELECT_OPS = {"replace": 0, "add": 1, "subtract": 2}  # DTP_SELECT_*
+
+
 class MipLevels(C.Structure):  # dtp_mip_levels
     _fields_ = [("levels", C.c_int), ("h", C.c_int * 16), ("w", C.c_int * 16), ("offset", C.c_uint64 * 16), ("bytes", C.c_uint64)]
 
@@ -262,6 +265,11 @@ SYMBOLS = {
                                  _vp]),
     "dtp_op_mesh_view_aniso": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(ViewCam), _i, _i, C.POINTER(ViewOpts), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _i, _vp]),
+    "dtp_mesh_select": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
+    "dtp_mesh_stroke_masked": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(MeshStamp), _i, C.POINTER(Settings), C.POINTER(MeshStrokeOpts), _vp, _i, _vp, _i,
+                                    _vp]),
+    "dtp_view_tint": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.POINTER(C.c_uint8 * 3), _i, _vp]),
+    "dtp_op_mesh_backproject_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

@@ -9,6 +9,8 @@
 // the mesh covers take the nearest covered texel, by the same integer coverage.
 // Picking (dtp_mesh_pick) is the render's visibility rule at one sample per ray: the closest hit of N rays, from the
 // vertices, faces and UVs alone, so that it runs on a stream of its own beside a stroke.
+// Masked strokes (dtp_mesh_stroke_masked): a face set keeps the faces whose bit is 0 out of the valid list; nothing else
+// of a stamp changes.  The lasso that makes a set and the tint that shows one are select.hip's.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stdio.h>
@@ -21,6 +23,7 @@
 
 #include "mesh_dev.h"
 #include "mesh_host.h"
+#include "select_host.h"
 #include "stamp.h"
 
 namespace {
@@ -61,6 +64,7 @@ struct Mesh {
   dtp_mesh_hit* pick_out = nullptr;           // [pick_cap]
   char* pick_host = nullptr;                  // pinned: [pick_cap] PickRay, then [pick_cap] dtp_mesh_hit
   int pick_cap = 0;
+  int* sel_poly = nullptr;  // [2 * 1024]: the snapped polygon of the lasso in flight (select.hip); no stroke, pick or view touches it
   void* view = nullptr;  // the buffers of dtp_mesh_view (view.hip): allocated at the first view; no stroke or pick touches them
 };
 
@@ -196,15 +200,17 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const FaceRec* __restr
   for (int ch = 0; ch < 4; ++ch) canvas[(size_t)ch * RR + pix] = out[ch];
 }
 
-// The faces that are backprojected (get_valid_faces, render.py:113-130): front, not steep, and the winner of at least one pixel.  Those
-// with a texel centre in their UV bounding box go to `val`, and the union of their texel ranges to st->bb.
+// The faces that are backprojected (get_valid_faces, render.py:113-130): front, not steep, and the winner of at least one pixel; with a
+// face set `sel` (or null: every face) also selected: bit f % 32 of word f / 32.  Those with a texel centre in their UV
+// bounding box go to `val`, and the union of their texel ranges to st->bb.
 __global__ __launch_bounds__(256) void mesh_valid_kernel(const FaceRec* __restrict__ rec, const int* __restrict__ owned,
                                                          const int4* __restrict__ win, const float* __restrict__ uvs, int F, int H,
-                                                         int W, int4* __restrict__ val, MeshState* st) {
+                                                         int W, int4* __restrict__ val, MeshState* st, const unsigned int* __restrict__ sel) {
   const int n_win = min(st->n_win, F);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n_win; i += gridDim.x * 256) {
     const int f = win[i].x;
     if ((rec[f].flags & (MF_FRONT | MF_UPRIGHT)) != (MF_FRONT | MF_UPRIGHT) || !owned[f]) continue;
+    if (sel && !((sel[f >> 5] >> (f & 31)) & 1u)) continue;  // (f < F: inside the set's (F + 31) / 32 words)
     int X[3], Y[3], x0, x1, y0, y1;
     snap_uvs(uvs + (size_t)6 * f, H, W, X, Y);
     if (orient(X[0], Y[0], X[1], Y[1], X[2], Y[2]) == 0) continue;
@@ -587,6 +593,7 @@ bool mesh_alive(const Mesh* m) {
 void mesh_free(Mesh* m) {
   (void)hipFree(m->verts); (void)hipFree(m->faces); (void)hipFree(m->uvs); (void)hipFree(m->rec); (void)hipFree(m->owned);
   (void)hipFree(m->win); (void)hipFree(m->val); (void)hipFree(m->state); (void)hipFree(m->cov);
+  (void)hipFree(m->sel_poly);
   (void)hipFree(m->pick_rays); (void)hipFree(m->pick_slots); (void)hipFree(m->pick_out);
   if (m->pick_host) (void)hipHostFree(m->pick_host);
   view_free(m->view);
@@ -675,10 +682,11 @@ int enqueue_render(Mesh* m, const float cam[12], float fov, int flip, const unsi
 
 // valid (-> journal) -> backproject of the window rendered last on this mesh; dec null: erase.  journal (or null): the one whose open record
 // guards this texture; the tiles of the valid faces' texel box grown by `grow` (the bleed that follows) are saved before they are written.
+// sel (or null): the face set outside which no face is valid.
 int enqueue_backproject(Mesh* m, const float* dec, int finished, const unsigned char* mask, const int* face_idx, int R, unsigned char* texture, int H, int W,
-                        hipStream_t s, Journal* journal = nullptr, int grow = 0) {
+                        hipStream_t s, Journal* journal = nullptr, int grow = 0, const unsigned int* sel = nullptr) {
   hipLaunchKernelGGL(mesh_valid_kernel, dim3(std::min((m->F + 255) / 256, 1024)), dim3(256), 0, s, m->rec, m->owned, m->win, m->uvs, m->F, H,
-                     W, m->val, m->state);
+                     W, m->val, m->state, sel);
   if (journal) RC(journal_save_box(journal, m->state->bb, grow, s));
   hipLaunchKernelGGL(mesh_backproject_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->rec, m->val, m->state, m->F, m->uvs, dec,
                      finished, mask, face_idx, R, (unsigned int*)texture, H, W);
@@ -748,9 +756,17 @@ struct MeshStep {
   StampPlan plan;
 };
 
-// dtp_mesh_stroke (bleed 0) and dtp_mesh_stroke_bleed: `who` names the entry point in a refusal
+// a caller's face set (or null: none) against the mesh: (F + 31) / 32 words, 4-byte aligned
+int check_face_mask(const char* who, const Mesh* m, const uint32_t* face_mask, int mask_words) {
+  char why[160];
+  if (face_mask && select_check_set(face_mask, mask_words, m->F, why)) { dtp_set_error("%s: face_mask: %s", who, why); return DTP_ERR_ARG; }
+  return DTP_OK;
+}
+
+// dtp_mesh_stroke (bleed 0), dtp_mesh_stroke_bleed and dtp_mesh_stroke_masked (face_mask or null): `who` names the entry point in a refusal
 int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
-                const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s_) {
+                const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s_, const uint32_t* face_mask = nullptr,
+                int mask_words = 0) {
   Ctx* c = (Ctx*)ctx;
   Mesh* m = (Mesh*)mesh;
   hipStream_t s = (hipStream_t)s_;
@@ -763,6 +779,8 @@ int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture,
   if (!c->finalized) { dtp_set_error("%s: weights not finalized", who); return DTP_ERR_STATE; }
   if (!mesh_alive(m)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
   if (m->ctx != c) { dtp_set_error("%s: the mesh belongs to another handle", who); return DTP_ERR_ARG; }
+  RC(check_face_mask(who, m, face_mask, mask_words));
+  const unsigned int* sel = (const unsigned int*)face_mask;
   const int R = c->R;
   RC(check_texture(who, texture, H, W));
   if (n < 1) { dtp_set_error("%s: n=%d stamps (at least 1)", who, n); return DTP_ERR_ARG; }
@@ -816,12 +834,12 @@ int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture,
     if (q.skip) continue;
     RC(enqueue_render(m, q.cam, t.fov, o->flip_normals != 0, texture, H, W, R, t.mode, o->over_y, o->over_x, c->canvas32, face_idx, s));
     if (t.mode == DTP_STROKE_ERASE) {
-      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s, journal, bleed));
+      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s, journal, bleed, sel));
       if (bleed) RC(enqueue_bleed(m, texture, H, W, bleed, nullptr, s));
       continue;
     }
     q.plan.paste = [=](const float* dec, int, int, hipStream_t q_s) {
-      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s, journal, bleed));
+      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s, journal, bleed, sel));
       return bleed ? enqueue_bleed(m, texture, H, W, bleed, nullptr, q_s) : DTP_OK;
     };
     RC(stamp_enqueue(c, q.plan, s));
@@ -835,7 +853,7 @@ int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture,
 bool mesh_geom(dtp_mesh* mesh, MeshGeom* out) {
   Mesh* m = (Mesh*)mesh;
   if (!mesh_alive(m)) return false;
-  *out = MeshGeom{m->ctx, m->F, m->verts, m->faces, m->uvs, &m->view};
+  *out = MeshGeom{m->ctx, m->F, m->verts, m->faces, m->uvs, &m->view, m->sel_poly};
   return true;
 }
 
@@ -892,6 +910,7 @@ int dtp_mesh_create(dtp_ctx* ctx, const float* vertices, int V, const int* faces
   if (e == hipSuccess) e = hipMalloc((void**)&m->win, nf * sizeof(int4));
   if (e == hipSuccess) e = hipMalloc((void**)&m->val, nf * sizeof(int4));
   if (e == hipSuccess) e = hipMalloc((void**)&m->state, sizeof(MeshState));
+  if (e == hipSuccess) e = hipMalloc((void**)&m->sel_poly, (size_t)2 * SELECT_MAX_VERTS * sizeof(int));
   if (e == hipSuccess) e = hipMemcpy(m->verts, vertices, (size_t)V * 12, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->faces, faces, nf * 12, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->uvs, face_uvs, nf * 24, hipMemcpyHostToDevice);
@@ -933,6 +952,11 @@ int dtp_mesh_stroke(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W
 int dtp_mesh_stroke_bleed(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
                           const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s) {
   return mesh_stroke("dtp_mesh_stroke_bleed", ctx, mesh, texture, H, W, stamps, n, st, o, paste_mask, bleed, s);
+}
+
+int dtp_mesh_stroke_masked(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
+                           const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, const uint32_t* face_mask, int mask_words, dtp_stream s) {
+  return mesh_stroke("dtp_mesh_stroke_masked", ctx, mesh, texture, H, W, stamps, n, st, o, paste_mask, bleed, s, face_mask, mask_words);
 }
 
 int dtp_mesh_bleed_offsets(int radius, int* count, signed char* di_dj) {
@@ -1039,6 +1063,19 @@ int dtp_op_mesh_backproject(dtp_mesh* mesh, const float* dec, int dec_finished, 
   RC(check_texture("dtp_op_mesh_backproject", texture, H, W));
   HIP_CHECK(hipSetDevice(m->ctx->device));
   return enqueue_backproject(m, dec, dec_finished != 0, mask, face_idx, R, texture, H, W, (hipStream_t)s);
+}
+
+int dtp_op_mesh_backproject_masked(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R, uint8_t* texture,
+                                   int H, int W, const uint32_t* face_mask, int mask_words, dtp_stream s) {
+  const char* who = "dtp_op_mesh_backproject_masked";
+  Mesh* m = (Mesh*)mesh;
+  if (!m || !mask || !face_idx || !texture) { dtp_set_error("%s: NULL argument (dec alone may be NULL: erase; face_mask: no set)", who); return DTP_ERR_ARG; }
+  if (!mesh_alive(m)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
+  RC(check_face_mask(who, m, face_mask, mask_words));
+  if (R < 1 || R > MAX_WIN) { dtp_set_error("%s: R=%d (1..%d)", who, R, MAX_WIN); return DTP_ERR_ARG; }
+  RC(check_texture(who, texture, H, W));
+  HIP_CHECK(hipSetDevice(m->ctx->device));
+  return enqueue_backproject(m, dec, dec_finished != 0, mask, face_idx, R, texture, H, W, (hipStream_t)s, nullptr, 0, (const unsigned int*)face_mask);
 }
 
 }  // extern "C"

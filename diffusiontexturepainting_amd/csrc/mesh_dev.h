@@ -82,7 +82,7 @@ __device__ __forceinline__ bool ranges_meet(int packed, int lo, int hi) { return
 // ---------------------------------------------------------------- a mesh, as the view sees it
 struct Ctx;
 // what a view reads of a mesh (vertices [V][3], faces [F][3], UVs [F][3][2]: never written after dtp_mesh_create), and the slot in which
-// the mesh keeps the view's own buffers
+// the mesh keeps the view's own buffers; sel_poly: the mesh's buffer for the snapped polygon of a lasso (select.hip), 2 x 1024 ints
 struct MeshGeom {
   Ctx* ctx;
   int F;
@@ -90,6 +90,7 @@ struct MeshGeom {
   const int* faces;
   const float* uvs;
   void** view;
+  int* sel_poly;
 };
 bool mesh_geom(dtp_mesh* mesh, MeshGeom* out);  // mesh.hip: false = not a live mesh (nothing is followed)
 void view_free(void* view);                     // view.hip: frees what *MeshGeom::view holds (null: nothing); called when the mesh is freed

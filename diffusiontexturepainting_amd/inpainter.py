@@ -103,6 +103,13 @@ def _stroke_stamps(positions, seeds=None, modes=None, slots=None):
     return arr
 
 
+def _tint_args(color, opacity):
+    """(the 3 bytes of a tint as a ctypes array, the opacity as an int); ValueError outside 0..255."""
+    if len(color) != 3 or not all(0 <= int(v) <= 255 for v in color) or isinstance(opacity, bool) or not 0 <= int(opacity) <= 255:
+        raise ValueError(f"a tint is 3 bytes in 0..255 and an opacity in 0..255, got {color!r} and {opacity!r}")
+    return (C.c_uint8 * 3)(*[int(v) for v in color]), int(opacity)
+
+
 def plan_stroke(positions, H, W, R, modes=None, wrap=False, max_group=1):
     """The groups dtp_stroke makes of a stroke on an H x W texture with R x R windows (dtp_stroke_plan, host only: needs no GPU): the
     list group_of, one non-decreasing group id per stamp.  Stamp i joins the current group iff the group has fewer than max_group
@@ -435,7 +442,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def paint_mesh_stroke(self, mesh, texture, positions, normals, prev_positions, fov, seeds=None, modes=None, slots=None,
                           flip_normals=False, margin=1, overpaint_margins=(10, 25), mask=None, sample_vae=True, strength=1.0, bleed=0,
-                          **settings):
+                          face_mask=None, **settings):
         """Paint a stroke on a textured mesh without a host round trip per stamp: TexturePainterManager.stamp (manager.py:199-271) as one
         dtp_mesh_stroke call.  Per stamp, in order: an orthographic look-at camera from positions[i] + normals[i] at positions[i] with
         up = prev_positions[i] - positions[i] (mesh_camera), the render of `mesh` with `texture` (uint8 [H,W,4] on the model's device,
@@ -447,7 +454,12 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         every stamp the texels no face of the mesh covers (the gutter between UV charts) take the nearest covered texel within that
         radius, inside the stamp's texel bounding box grown by the radius, so that the next stamp's render and any filtered view of the
         texture see no unpainted line along the seams (dtp_mesh_stroke_bleed; the first use with a texture size builds the mesh's
-        coverage mask and waits for it once).  0: no pass, dtp_mesh_stroke exactly."""
+        coverage mask and waits for it once).  0: no pass, dtp_mesh_stroke exactly.
+        face_mask: a face set (DESIGN.md 3.30; mesh.faceset_from_bool, select_faces): int32 [(F + 31) // 32] on the model's device,
+        contiguous.  A face whose bit is 0 is never backprojected, so the stroke paints the texels of the selected faces alone; the
+        render still shows the whole mesh and the stamp is the stamp it would have been (dtp_mesh_stroke_masked).  The set is read on
+        the device when the stroke runs: the stroke's stream first waits for self.view_stream, so select-then-paint needs no
+        synchronisation, and the tensor must stay unchanged until the stroke has run.  None: the call without the keyword."""
         if not self._slots:
             raise _lib.DtpError("no brush set: call set_brush() first")
         R = self._resolution
@@ -471,15 +483,23 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
             if tuple(mask.shape) != (R, R):
                 raise ValueError(f"mask must be {R} x {R}, got {tuple(mask.shape)}")
             mask = (mask.detach().to(self._device) > 0).to(torch.uint8).contiguous()
+        if face_mask is not None:
+            _mesh.faceset_check(face_mask, mesh.num_faces, self._device)
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
-        if int(bleed) == 0:
+        if face_mask is not None:
+            if self._view_stream is not None:
+                self.stream.wait_stream(self._view_stream)  # a select_faces that is still writing the set
+            check(self._lib.dtp_mesh_stroke_masked(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n,
+                                                   C.byref(st), C.byref(opts), ptr(mask), int(bleed), ptr(face_mask), face_mask.shape[0],
+                                                   self._s()), "dtp_mesh_stroke_masked")
+        elif int(bleed) == 0:
             check(self._lib.dtp_mesh_stroke(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n, C.byref(st),
                                             C.byref(opts), ptr(mask), self._s()), "dtp_mesh_stroke")
         else:
             check(self._lib.dtp_mesh_stroke_bleed(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n,
                                                   C.byref(st), C.byref(opts), ptr(mask), int(bleed), self._s()), "dtp_mesh_stroke_bleed")
         torch.cuda.current_stream(self._device).wait_stream(self.stream)
-        for t in (texture, mask):  # keep them alive until the stream has consumed them
+        for t in (texture, mask, face_mask):  # keep them alive until the stream has consumed them
             if t is not None:
                 t.record_stream(self.stream)
         if self._check_finite and not self.last_stamp_finite():
@@ -507,7 +527,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         directions) -> mesh.plan_path(hits, radius / stamps_per_radius, state) -> paint_mesh_stroke with the planned stamps.  radius:
         the brush radius in world units; fov defaults to it.  state: None for a new path, or what the last call returned, so that a
         path can be painted as the pointer events arrive.  Every other keyword is paint_mesh_stroke's (seeds, modes -- one mode for the
-        whole path --, bleed, mask, settings ...); a stamp whose camera is refused is refused by the stroke as always.  A path that
+        whole path --, bleed, mask, face_mask, settings ...); a stamp whose camera is refused is refused by the stroke as always.  A path that
         plans no stamp (all rays miss, or the pointer has not moved far enough) paints nothing.  -> (texture, state, stamps painted)."""
         hits = self.pick(mesh, origins, directions)
         positions, normals, prevs, state = _mesh.plan_path(hits, float(radius) / float(stamps_per_radius), state)
@@ -528,7 +548,8 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def render_view(self, mesh, texture, camera, size=None, cull=False, flip_normals=False, shade=True, ambient=0.25, unpainted=(128, 128, 128),
                     background=(0, 0, 0, 0), out=None, want_face_idx=False, want_depth=False, live=False, filter="bilinear", mips=None,
-                    want_lod=False, clip_near=False, samples=1, want_coverage=False, anisotropy=1, want_taps=False):
+                    want_lod=False, clip_near=False, samples=1, want_coverage=False, anisotropy=1, want_taps=False, selection=None,
+                    selection_color=(255, 160, 0), selection_opacity=128):
         """A perspective view of the whole painted mesh (dtp_mesh_view; in the Kit app the viewport is Omniverse RTX):
         `mesh` from load_mesh, `texture` uint8 [TH, TW, 4] on the model's device, `camera` from mesh.view_camera, size = (H, W) (default
         the camera's; each side 1..4096).  -> the frame, uint8 [H, W, 4] on the device (RGB the texture under its alpha over `unpainted`,
@@ -565,7 +586,14 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         axis are averaged: stripes across the line of sight stay stripes.  Works with clip_near, samples, mips, out, live, want_lod and
         want_coverage as before; a magnified frame is still the bilinear one byte for byte, and visibility, face_idx and depth do not
         change.  want_taps: also uint8 [H, W], the number of taps the pixel took (0 where no face is), after lod and before coverage.
-        anisotropy=1 is the call without the keyword."""
+        anisotropy=1 is the call without the keyword.
+        selection: a face set; the pixels that show one of its faces are tinted after the raster, as
+        tint_selection(frame, face_idx, selection, selection_color, selection_opacity) does.  None: no pass."""
+        if selection is not None:
+            if not isinstance(mesh, _mesh.Mesh):
+                raise ValueError("mesh must come from load_mesh()")
+            _mesh.faceset_check(selection, mesh.num_faces, self._device, what="selection")
+            color, opacity = _tint_args(selection_color, selection_opacity)
         if filter not in ("bilinear", "trilinear"):
             raise ValueError(f"filter {filter!r}: choose 'bilinear' or 'trilinear'")
         anisotropy = _lib.view_anisotropy_check(anisotropy, filter, want_taps, least=2)
@@ -600,7 +628,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         with torch.cuda.stream(self.view_stream):  # the outputs belong to the view's stream: a live view waits for no other
             if out is None:
                 out = torch.empty(H, W, 4, dtype=torch.uint8, device=self._device)
-            face_idx = torch.empty(H, W, dtype=torch.int32, device=self._device) if want_face_idx else None
+            face_idx = torch.empty(H, W, dtype=torch.int32, device=self._device) if want_face_idx or selection is not None else None
             depth = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_depth else None
             lod = torch.empty(H, W, dtype=torch.float32, device=self._device) if want_lod else None
             coverage = torch.empty(H, W, dtype=torch.uint8, device=self._device) if want_coverage else None
@@ -636,15 +664,83 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         else:
             check(self._lib.dtp_mesh_view(mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], C.byref(cam), H, W, C.byref(opts), ptr(out),
                                           ptr(face_idx), ptr(depth), vs), "dtp_mesh_view")
+        if selection is not None:
+            check(self._lib.dtp_view_tint(self._h, ptr(out), ptr(face_idx), H, W, ptr(selection), selection.shape[0], mesh.num_faces,
+                                          C.byref(color), opacity, vs), "dtp_view_tint")
         cur.wait_stream(self.view_stream)
-        for t in (texture, given, None if build else mips):
+        for t in (texture, given, None if build else mips, selection):
             if t is not None:
                 t.record_stream(self.view_stream)
         for t in (None if given is not None else out, face_idx, depth, lod, taps, coverage):
             if t is not None:
                 t.record_stream(cur)
-        extra = tuple(t for t in (face_idx, depth, lod, taps, coverage) if t is not None)
+        extra = tuple(t for t in (face_idx if want_face_idx else None, depth, lod, taps, coverage) if t is not None)
         return (out,) + extra if extra else out
+
+    def select_faces(self, mesh, face_idx, polygon, op="replace", out=None):
+        """Lasso selection (dtp_mesh_select): the faces of `mesh` that a frame shows inside a polygon, as a face set --
+        int32 [(F + 31) // 32] on the model's device, bit f % 32 of word f // 32 = face f (mesh.faceset_to_bool unpacks it; |, & and ~
+        are union, intersection and complement).  face_idx: int32 [H, W] on the device, as render_view(want_face_idx=True) returns it
+        (-1: no face; with samples > 1 the centre sample's face).  polygon: float [n, 2] as (x, y) in the frame's pixel coordinates,
+        mesh.view_rays' convention (the centre of pixel (i, j) is (j + 0.5, i + 0.5)), 3 <= n <= 1024 and finite, else DtpError; a
+        rectangle is four vertices.  A pixel is inside when its centre is, by the even-odd rule in exact integers on vertices snapped
+        to 1 / 256 pixel, so a self-intersecting lasso follows even-odd; a face is selected when it is face_idx at one or more inside
+        pixels: what the user sees, not hidden, back-facing or sub-pixel faces.  op: "replace" (out is zeroed first), "add" or
+        "subtract" (out is the set to edit).  out: default a fresh zeroed set.  The call only enqueues, on self.view_stream, behind
+        the frame it reads and behind the caller's current stream, which then waits for the set (on the device).  One select of a
+        mesh at a time."""
+        if not isinstance(mesh, _mesh.Mesh):
+            raise ValueError("mesh must come from load_mesh()")
+        if op not in _lib.SELECT_OPS:
+            raise ValueError(f"op {op!r}: choose one of {', '.join(_lib.SELECT_OPS)}")
+        if not (isinstance(face_idx, torch.Tensor) and face_idx.dtype == torch.int32 and face_idx.dim() == 2 and face_idx.device == self._device
+                and face_idx.is_contiguous()):
+            raise ValueError(f"face_idx must be a contiguous int32 [H, W] tensor on {self._device}")
+        poly, n = _mesh.lasso_polygon(polygon)
+        if out is not None:
+            _mesh.faceset_check(out, mesh.num_faces, self._device, what="out")
+        cur = torch.cuda.current_stream(self._device)
+        given = out
+        with torch.cuda.stream(self.view_stream):
+            if out is None:
+                out = _mesh.faceset_empty(mesh.num_faces, self._device)
+        self.view_stream.wait_stream(cur)
+        src = poly if n else torch.zeros(1, 2, dtype=torch.float32)  # (an empty tensor has no address; n = 0 is the library's to refuse)
+        check(self._lib.dtp_mesh_select(mesh.handle, ptr(face_idx), face_idx.shape[0], face_idx.shape[1], ptr(src), n,
+                                        _lib.SELECT_OPS[op], ptr(out), out.shape[0], C.c_void_p(self.view_stream.cuda_stream)), "dtp_mesh_select")
+        cur.wait_stream(self.view_stream)
+        for t in (face_idx, given):
+            if t is not None:
+                t.record_stream(self.view_stream)
+        if given is None:
+            out.record_stream(cur)
+        return out
+
+    def tint_selection(self, frame, face_idx, sel, color=(255, 160, 0), opacity=128, num_faces=None):
+        """Show a face set on a finished frame, in place (dtp_view_tint): frame uint8 [H, W, 4] and face_idx int32
+        [H, W] of one render_view call, on the model's device.  Where face_idx is a face of `sel`, each of R, G, B becomes
+        (c * (255 - opacity) + color * opacity + 127) // 255; alpha and every other pixel are untouched.  num_faces: the mesh's F, so
+        that stray bits of ~sel beyond it are ignored even against a hand-made face_idx (default: 32 per word, which a frame of the
+        mesh never reaches).  The call only enqueues, on self.view_stream, as select_faces does.  -> frame."""
+        color, opacity = _tint_args(color, opacity)
+        if not (isinstance(frame, torch.Tensor) and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 4
+                and frame.device == self._device and frame.is_contiguous()):
+            raise ValueError(f"frame must be a contiguous uint8 [H, W, 4] tensor on {self._device} (it is tinted in place)")
+        H, W = frame.shape[0], frame.shape[1]
+        if not (isinstance(face_idx, torch.Tensor) and face_idx.dtype == torch.int32 and tuple(face_idx.shape) == (H, W)
+                and face_idx.device == self._device and face_idx.is_contiguous()):
+            raise ValueError(f"face_idx must be a contiguous int32 [{H}, {W}] tensor on {self._device}")
+        if num_faces is None and isinstance(sel, torch.Tensor) and sel.dim() == 1:
+            num_faces = 32 * sel.shape[0]
+        _mesh.faceset_check(sel, num_faces or 0, self._device, what="sel")
+        cur = torch.cuda.current_stream(self._device)
+        self.view_stream.wait_stream(cur)
+        check(self._lib.dtp_view_tint(self._h, ptr(frame), ptr(face_idx), H, W, ptr(sel), sel.shape[0], int(num_faces), C.byref(color), opacity,
+                                      C.c_void_p(self.view_stream.cuda_stream)), "dtp_view_tint")
+        cur.wait_stream(self.view_stream)
+        for t in (frame, face_idx, sel):
+            t.record_stream(self.view_stream)
+        return frame
 
     def _mip_bytes(self, texture):
         lay = _lib.MipLevels()

@@ -4,7 +4,9 @@ are ops.mesh_render / ops.mesh_backproject.  The bleed pass that pads the UV cha
 MI355ConditionalInpainter.bleed_texture; ops.mesh_coverage / ops.mesh_bleed_offsets show what it works from.  Picking:
 the host-only ray frame and the stamp spacing of a pointer path live here; the pick itself is MI355ConditionalInpainter.pick and the
 pointer-to-paint call paint_mesh_path.  The view (DESIGN.md 3.24): the host-only perspective camera and the rays of its pixels live here;
-the frame itself is MI355ConditionalInpainter.render_view (ops.mesh_view at op level)."""
+the frame itself is MI355ConditionalInpainter.render_view (ops.mesh_view at op level).  Face sets: the packing of a
+set of faces into int32 words and its checks live here; the lasso is MI355ConditionalInpainter.select_faces, the stroke that respects a
+set paint_mesh_stroke(face_mask=), the tint tint_selection."""
 import ctypes as C
 
 import torch
@@ -144,6 +146,61 @@ def view_opts(cull=False, flip_normals=False, shade=True, ambient=0.25, unpainte
         raise ValueError(f"unpainted is 3 and background 4 bytes in 0..255, got {unpainted!r} and {background!r}")
     return _lib.ViewOpts(int(bool(cull)), int(bool(flip_normals)), int(bool(shade)), float(ambient), (C.c_uint8 * 3)(*[int(v) for v in unpainted]),
                          (C.c_uint8 * 4)(*[int(v) for v in background]))
+
+
+# ---------------------------------------------------------------- face sets
+def faceset_words(F):
+    """The int32 words of a face set of F faces."""
+    return (int(F) + 31) // 32
+
+
+def faceset_empty(F, device):
+    """The empty face set of a mesh of F faces: int32 [(F + 31) // 32] of zeros on `device`.  Bit f % 32 of word f // 32 is face f; the
+    bits at positions >= F are ignored by every kernel, so ~sel is a face set, and | and & are union and intersection."""
+    return torch.zeros(faceset_words(F), dtype=torch.int32, device=device)
+
+
+def faceset_from_bool(mask):
+    """bool [F] (any device) -> the face set with exactly those faces, on the same device."""
+    mask = torch.as_tensor(mask)
+    if mask.dim() != 1 or mask.dtype != torch.bool:
+        raise ValueError(f"a bool [F] tensor expected, got {mask.dtype} {tuple(mask.shape)}")
+    F = mask.shape[0]
+    bits = torch.zeros(32 * faceset_words(F), dtype=torch.int64, device=mask.device)
+    bits[:F] = mask
+    w = (bits.reshape(-1, 32) << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(dim=1)  # 0 .. 2^32 - 1
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def faceset_to_bool(sel, F):
+    """A face set -> bool [F] on its device; stray bits at positions >= F (of ~sel, say) are dropped."""
+    if sel.dtype != torch.int32 or sel.dim() != 1 or sel.shape[0] != faceset_words(F):
+        raise ValueError(f"a face set of {F} faces is int32 [{faceset_words(F)}], got {sel.dtype} {tuple(sel.shape)}")
+    bits = (sel.to(torch.int64)[:, None] >> torch.arange(32, dtype=torch.int64, device=sel.device)) & 1
+    return bits.reshape(-1)[:int(F)].bool()
+
+
+def faceset_check(sel, F, device, what="face_mask"):
+    """ValueError for what a stroke, a select or a tint refuses of a face set: the wrong dtype, length or device, or a view that is not
+    contiguous.  Before anything is enqueued."""
+    if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int32:
+        raise ValueError(f"{what} must be a torch.int32 tensor (a face set), got {getattr(sel, 'dtype', type(sel))}")
+    if sel.dim() != 1 or sel.shape[0] != faceset_words(F):
+        raise ValueError(f"{what} must have (F + 31) // 32 = {faceset_words(F)} words for {F} faces, got shape {tuple(sel.shape)}")
+    if sel.device != torch.device(device):
+        raise ValueError(f"{what} must be on {device}, the mesh's device; it is on {sel.device}")
+    if not sel.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return sel
+
+
+def lasso_polygon(polygon):
+    """float [n, 2] as (x, y) pixel coordinates -> (contiguous float32 [n, 2] on the host, n); the count and the values are the
+    library's to refuse."""
+    p = torch.as_tensor(polygon).detach().to("cpu", torch.float32)
+    if p.dim() != 2 or p.shape[1] != 2:
+        raise ValueError(f"polygon must be [n, 2] as (x, y), got {tuple(p.shape)}")
+    return p.contiguous(), p.shape[0]
 
 
 class Mesh:

@@ -586,12 +586,16 @@ def mesh_render(mesh, camera, fov, texture, R, flip_normals=False, mode=0, over_
     return canvas, face_idx
 
 
-def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None):
+def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None, face_mask=None):
     """dtp_op_mesh_backproject, the other half: through the faces the LAST mesh_render of `mesh` showed (face_idx: that render's), the
     stamp image is carried into texture u8 [H,W,4] in place where the sampled mask u8 [R,R] * (face_idx != -1) is > 0.  The stamp image
     is dec f32 [R,R,4] (the VAE decoder's working layout, values around -1..1), or `painted` f32 [3,R,R] / [1,3,R,R] in 0..1 (what
-    generate_raw returns, used as it is); neither: erase.  Returns texture."""
+    generate_raw returns, used as it is); neither: erase.  face_mask: a face set (int32 [(F + 31) // 32] on the texture's device,
+    contiguous; dtp_op_mesh_backproject_masked): a face whose bit is 0 is not backprojected.  Returns texture."""
     lib = _lib.load()
+    if face_mask is not None:
+        from . import mesh as _mesh
+        _mesh.faceset_check(face_mask, mesh.num_faces, texture.device)
     finished = painted is not None
     if finished:
         if dec is not None:
@@ -599,6 +603,11 @@ def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None):
         R = face_idx.shape[0]
         dec = torch.zeros(R, R, 4, dtype=torch.float32, device=texture.device)
         dec[..., :3] = painted.reshape(3, R, R).permute(1, 2, 0)
+    if face_mask is not None:
+        check(lib.dtp_op_mesh_backproject_masked(mesh.handle, ptr(dec), int(finished), ptr(mask), ptr(face_idx), face_idx.shape[0], ptr(texture),
+                                                 texture.shape[0], texture.shape[1], ptr(face_mask), face_mask.shape[0], _stream()),
+              "mesh_backproject_masked")
+        return texture
     check(lib.dtp_op_mesh_backproject(mesh.handle, ptr(dec), int(finished), ptr(mask), ptr(face_idx), face_idx.shape[0], ptr(texture),
                                       texture.shape[0], texture.shape[1], _stream()), "mesh_backproject")
     return texture

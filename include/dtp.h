@@ -632,6 +632,63 @@ int dtp_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, 
                         const dtp_view_opts* opts, int clip, int samples, int max_aniso, uint8_t* image, int* face_idx, float* depth,
                         float* lod, uint8_t* taps, uint8_t* coverage, dtp_stream s);
 
+/* ---------------------------------------------------------------- face sets: a lasso, masked strokes, a tint
+ * Protecting part of a mesh from a stroke (Blender's "face selection masking").  A stamp writes every texel of every
+ * visible face in its window; the [R][R] paste mask lives in stamp space and knows no face.
+ *
+ * A FACE SET of a mesh of F faces is (F + 31) / 32 32-bit words on the mesh's device, 4-byte aligned: bit f % 32 of word f / 32 is face
+ * f.  It is the caller's memory and no object of this library.  Every kernel here ignores the bits at positions >= F of the last word,
+ * so the complement of a set, word by word, is a set; union and intersection are OR and AND of the words.
+ *
+ * dtp_mesh_select: the faces a frame shows inside a polygon.  face_idx: device i32 [H][W] as a view writes it (-1: no face; with samples
+ * > 1 the face of the sample that stores it), 1 <= H, W <= 4096.  polygon: host float [n][2], (x, y) in the frame's pixel coordinates, the
+ * convention of dtp_view_rays: the centre of pixel (row i, column j) is (j + 0.5, i + 0.5); 3 <= n <= 1024 and every coordinate finite.
+ * A rectangle is a polygon of four vertices.  The rule, in integers past the first step:
+ *  1. Each vertex is snapped on the host by the raster's snap: X = snap(256.0f * x), Y = snap(256.0f * y) in fp32, snap = rintf clamped
+ *     to +-2^26.  The centre of pixel (i, j) is P = (256 j + 128, 256 i + 128).
+ *  2. P is inside by the even-odd rule over the n edges (a, b) = (vertex k, vertex (k + 1) mod n), in int64: an edge counts iff
+ *     (a.y > P.y) != (b.y > P.y) and P lies strictly left of the edge's crossing of P's row, i.e.
+ *     D = (P.x - a.x)(b.y - a.y) - (P.y - a.y)(b.x - a.x) is not zero and D < 0 exactly when b.y - a.y > 0.  P is inside iff an odd
+ *     number of edges count.  (Every difference is below 2^27 + 2^20 and every product below 2^55.)  A horizontal edge never counts, a
+ *     centre ON an edge or a vertex is decided by the strict comparisons, and a self-intersecting polygon follows even-odd.
+ *  3. Face f is hit iff 0 <= f < F and f == face_idx[i][j] at one or more inside pixels.  A face_idx value outside -1 .. F - 1 is
+ *     skipped, never used as an index.
+ * op: DTP_SELECT_REPLACE: `out` is zeroed on the stream, then the bits of the hit faces are set; DTP_SELECT_ADD: they are set;
+ * DTP_SELECT_SUBTRACT: they are cleared; out: the set to write or edit, `words` = (F + 31) / 32.  The result is an OR / AND-NOT of single
+ * bits and does not depend on the order of the atomics.  This selects what the user SEES: a hidden, back-facing or sub-pixel face that
+ * won no pixel is not hit.  The call only enqueues on `s`: the memset of REPLACE, at most three launches that carry the snapped polygon
+ * to the mesh's 8 KB buffer in their arguments, and one workgroup per 16 x 16 pixels of the polygon's pixel bounding box clipped to the
+ * frame (no other tile is launched; a box without a centre launches nothing).  One select of a mesh at a time, or all on one stream.
+ * Refusals, DTP_ERR_ARG before anything is enqueued: n outside 3..1024, an unknown op, a side outside 1..4096, a vertex that is not finite
+ * (these four before the mesh is looked at), a NULL pointer, a mesh that is not alive, words != (F + 31) / 32, a misaligned pointer.
+ *
+ * dtp_mesh_stroke_masked: dtp_mesh_stroke_bleed (bleed 0: dtp_mesh_stroke) with a face set.  A face whose bit is 0 never enters the
+ * backprojection's valid list: valid = front, not steep, the winner of a pixel, AND selected.  Nothing else changes: the render shows
+ * the whole mesh, the stamp is the stamp it would have been, and the paste writes the texels whose centre a selected valid face covers
+ * (among several the lowest index wins); an Erase stamp follows the same rule.  The texel bounding box is that of the selected valid
+ * faces, so an open journal record saves less and the bleed pass runs over less; an empty list pastes nothing and is no error.  The set
+ * is read on the device in stream order, once per stamp: it must stay unchanged until the stroke has run.  face_mask NULL: the call
+ * dtp_mesh_stroke_bleed makes, launch for launch and byte for byte (mask_words is then ignored).  Refusals beyond that call's:
+ * mask_words != (F + 31) / 32 or a misaligned face_mask, DTP_ERR_ARG before anything is enqueued.
+ *
+ * dtp_view_tint: shows a set on a finished frame, in place.  frame: device u8 [H][W][4]; face_idx: that frame's; set, words, F as above
+ * (F is given because the call takes no mesh).  Where face_idx[i][j] is a face of the set, each of R, G, B becomes
+ * (c (255 - opacity) + color[ch] opacity + 127) / 255 in integers, 0 <= opacity <= 255; alpha is untouched, and every other pixel is
+ * neither read nor written.  One thread per pixel, one launch on `s`.  A pass of its own, so that no raster kernel changes.
+ *
+ * Not here: selecting through the mesh (hidden faces), growing a set to whole UV charts or by connectivity, texel-space stencils and the
+ * 2D dtp_stroke, an outline instead of a tint, a wire message. */
+#define DTP_SELECT_REPLACE 0
+#define DTP_SELECT_ADD 1
+#define DTP_SELECT_SUBTRACT 2
+int dtp_mesh_select(dtp_mesh* mesh, const int* face_idx, int H, int W, const float* polygon, int n, int op, uint32_t* out, int words,
+                    dtp_stream s);
+int dtp_mesh_stroke_masked(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n,
+                           const dtp_settings* st, const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed,
+                           const uint32_t* face_mask, int mask_words, dtp_stream s);
+int dtp_view_tint(dtp_ctx* ctx, uint8_t* frame, const int* face_idx, int H, int W, const uint32_t* set, int words, int F,
+                  const uint8_t color[3], int opacity, dtp_stream s);
+
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
  * the last 10 copies and uploads one on Ctrl+Z (kit_app/.../python/ui/brush.py:52-77,131-137; redo is a TODO there).  A journal keeps, on
@@ -1080,6 +1137,10 @@ int dtp_op_mesh_render(dtp_mesh* mesh, const float cam[12], float fov, int flip_
                        int over_y, int over_x, float* canvas, int* face_idx, dtp_stream s);
 int dtp_op_mesh_backproject(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R, uint8_t* texture, int H, int W,
                             dtp_stream s);
+/* dtp_op_mesh_backproject with a face set (the contract: see "face sets"): face_mask device u32 [mask_words], mask_words = (F + 31) / 32;
+ * a face whose bit is 0 is not valid.  face_mask NULL: dtp_op_mesh_backproject exactly. */
+int dtp_op_mesh_backproject_masked(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R,
+                                   uint8_t* texture, int H, int W, const uint32_t* face_mask, int mask_words, dtp_stream s);
 /* dtp_mesh_pick with the records left on the device (the contract: see "picking on a mesh"): rays host dtp_ray[n], out device
  * dtp_mesh_hit[n] (52 bytes each).  The same checks; it enqueues on `s` and waits for `s`, because the frames travel through the mesh's
  * pinned buffer. */
