@@ -199,6 +199,10 @@ SYMBOLS = {
     "dtp_op_groupnorm_stats_apply": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "dtp_op_pack_conv_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "dtp_op_pack_conv_ws_elems": (C.c_longlong, [_i, _i, _i]),
+    "dtp_op_pack_conv_ws_ups4": (_i, [_vp, _vp, _i, _i, _vp]),
+    "dtp_op_pack_conv_ws_ups4_elems": (C.c_longlong, [_i, _i]),
+    "dtp_op_conv_ups4": (_i, [C.POINTER(GemmDesc), _vp, _vp]),
+    "dtp_op_conv_ws_supported": (_i, [C.POINTER(GemmDesc), _vp, _i, _i]),
     "dtp_op_pack_linear_ws": (_i, [_vp, _i, _vp, _i, _i, _vp]),
     "dtp_op_pack_linear_ws_elems": (C.c_longlong, [_i, _i]),
     "dtp_op_groupnorm": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),

@@ -60,12 +60,9 @@ extern "C" {
 int dtp_abi_version(void) { return DTP_ABI_VERSION; }
 const char* dtp_last_error(void) { return g_err; }
 
-int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s) {
-  std::lock_guard<std::mutex> lk(g_ops_mu);
-  int rc = ops_init();
-  if (rc) return rc;
-  static bool halo_init = false;
-  if (!halo_init) { dtp_conv_halo_init(); dtp_gemm_wide_init(); dtp_lnlin_init(); dtp_conv_ws_init(); dtp_gemm_ws_init(); halo_init = true; }
+// the problem a dtp_gemm_desc describes (dtp_op_gemm, dtp_op_conv_ups4, dtp_op_conv_ws_supported); the tile and the split are applied by the
+// caller.  wfr4: the phase sets of an upsample2x conv (the descriptor has no field for them: it only grows by a new ABI version)
+static GemmParams desc_params(const dtp_gemm_desc* d, const void* wfr4) {
   GemmParams p = {};
   p.A = (const f16*)d->A; p.W = (const f16*)d->W; p.C = d->C; p.bias = d->bias; p.R = (const f16*)d->R;
   p.zero = g_ops.zero;
@@ -81,8 +78,18 @@ int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s) {
   p.st_out = d->st_out; p.st_in = d->st_in; p.st_parts = d->st_parts;
   if (p.batch > 1) p.st_rows = p.batch * p.M;  // statistics tables are [parts][batch * M][2]
   p.W8 = (const unsigned char*)d->W8; p.ldw8 = d->ldw8; p.a_scale = d->a_scale; p.w_scale = d->w_scale;
-  p.Wfr = (const f16*)d->Wfr;
+  p.Wfr = (const f16*)d->Wfr; p.Wfr4 = (const f16*)wfr4;
   p.gn_cpg = d->gn_cpg;
+  return p;
+}
+
+static int op_gemm(dtp_gemm_desc* d, const void* wfr4, dtp_stream s) {
+  std::lock_guard<std::mutex> lk(g_ops_mu);
+  int rc = ops_init();
+  if (rc) return rc;
+  static bool halo_init = false;
+  if (!halo_init) { dtp_conv_halo_init(); dtp_gemm_wide_init(); dtp_lnlin_init(); dtp_conv_ws_init(); dtp_gemm_ws_init(); halo_init = true; }
+  GemmParams p = desc_params(d, wfr4);
   static bool fp8_init = false;
   if (!fp8_init) { dtp_gemm_fp8_init(); fp8_init = true; }
   if (p.ldw < p.nkb * 64) { dtp_set_error("gemm: ldw=%d smaller than padded K=%d", p.ldw, p.nkb * 64); return DTP_ERR_ARG; }
@@ -103,6 +110,12 @@ int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s) {
   p.part = g_ops.ws;
   if (p.flags & GF_ROWSTATS) d->st_parts_out = dtp_tile_row_parts(p, tile);
   return dtp_launch_tile(p, tile, (hipStream_t)s);
+}
+
+int dtp_op_gemm(dtp_gemm_desc* d, dtp_stream s) { return op_gemm(d, nullptr, s); }
+int dtp_op_conv_ups4(dtp_gemm_desc* d, const void* wfr4, dtp_stream s) {
+  if (!d || !d->conv || !d->upsample2x || !wfr4) { dtp_set_error("conv_ups4: a 3x3 conv over the 2x upsample and its phase weights"); return DTP_ERR_ARG; }
+  return op_gemm(d, wfr4, s);
 }
 
 int dtp_op_gemm_f8f8(dtp_gemm_desc* d, dtp_stream s) {
@@ -188,6 +201,15 @@ int dtp_op_pack_linear_ws(const void* w, int ldw, void* out, int N, int K, dtp_s
 }
 long long dtp_op_pack_linear_ws_elems(int N, int K) { return (long long)dtp_gemm_ws_packed_elems(N, K); }
 long long dtp_op_pack_conv_ws_elems(int Cout, int Cin, int Cin2) { return (long long)dtp_conv_ws_packed_elems(Cout, Cin, Cin2); }
+int dtp_op_pack_conv_ws_ups4(const float* w, void* out, int Cout, int Cin, dtp_stream s) {
+  return dtp_launch_pack_conv_ws_ups4(w, (f16*)out, Cout, Cin, (hipStream_t)s);
+}
+long long dtp_op_pack_conv_ws_ups4_elems(int Cout, int Cin) { return (long long)dtp_conv_ws_ups4_packed_elems(Cout, Cin); }
+int dtp_op_conv_ws_supported(const dtp_gemm_desc* d, const void* wfr4, int tile, int splits) {
+  const DtpTile t = dtp_tile(tile);
+  if (!d || t.fam != TF_CONVWS) return 0;
+  return dtp_conv_ws_supported(desc_params(d, wfr4), t.var, splits < 1 ? 1 : splits) ? 1 : 0;
+}
 
 int dtp_op_groupnorm(const void* x, int ldx, void* y, int ldy, const float* gamma, const float* beta, int B, int HW, int C,
                      int groups, float eps, int silu, dtp_stream s) {

@@ -381,6 +381,7 @@ int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg,
     if (!sp) { dtp_set_error("push_gemm: no lnlin configuration for the GroupNorm-on-load Linear (M %d N %d K %d)", p.M, p.N, p.K); return DTP_ERR_ARG; }
   }
   if (c->autotune) RC(tune_gemm(c, p, &tile, &sp));
+  if (c->ups_phase >= 2 && dtp_conv_ws_supported(p, 2 + c->ups_phase, 1)) { tile = DTP_TILE_WSUPS4 + c->ups_phase - 2; sp = 1; }  // forced (tests, A/B)
   (void)dtp_tile_apply(p, tile, sp);
   const DtpTile t = dtp_tile(tile);
   if (emit) {  // the consumer must know how many partials this launch configuration writes per row
@@ -398,7 +399,7 @@ int push_gemm(Ctx* c, Prog* prog, GemmParams p, int bias_step_off, double k_alg,
   char lab[160];
   const bool f8tile = t.fam == TF_FP8;  // an fp8 problem may have kept an fp16 tile (tune_gemm)
   snprintf(lab, sizeof(lab), "%s M=%d N=%d K=%d tile=%d splits=%d%s%s%s%s", (p.flags & GF_CONV3) ? "conv3" : "gemm", p.M, p.N, p.K, tile,
-           t.split == SPLIT_COLS ? p.col_ranges : p.splits, (p.flags & GF_UPS2) ? " ups" : "", (p.flags & GF_GEGLU) ? (f8tile ? " geglu fp8" : " geglu") : (f8tile ? " fp8" : ""), p.stride == 2 ? " s2" : "",
+           t.split == SPLIT_COLS ? p.col_ranges : p.splits, (p.flags & GF_UPS2) ? (t.fam == TF_CONVWS && t.var >= 4 ? " ups4" : " ups") : "", (p.flags & GF_GEGLU) ? (f8tile ? " geglu fp8" : " geglu") : (f8tile ? " fp8" : ""), p.stride == 2 ? " s2" : "",
            p.batch > 1 ? (" x" + std::to_string(p.batch)).c_str() : "");
   const double flops = 2.0 * nb * p.M * (double)p.N * k_alg;
   prog_push(c, prog, t.pk, flops, bytes, make_gemm_op(c, p, tile, bias_step_off), lab);
@@ -425,6 +426,7 @@ int Builder::conv3(const T& x, const ConvW& w, int stride, int pad, bool ups, in
   if (o.tail) { p.A2 = o.tail->p; p.lda2 = o.tail->ld; p.Cin2 = w.cin2; }
   p.Wcb = w.wcb;
   p.Wfr = w.wfr;
+  if (ups && c->ups_phase) p.Wfr4 = w.wfr4;
   if (o.extra_flags & GF_GNAPPLY) {
     if (!o.gn.part) { dtp_set_error("conv3: GF_GNAPPLY without GroupNorm parameters"); return DTP_ERR_ARG; }
     p.gn_part = o.gn.part; p.gn_gamma = o.gn.gamma; p.gn_beta = o.gn.beta; p.gn_eps = o.gn.eps;

@@ -268,6 +268,8 @@ struct GemmParams {
   const f16* Wcb;    // same 3x3 weights packed channel-block-major (k' = (cb*9+tap)*64 + c) for conv_halo_kernel; may be null
   const f16* Wfr;    // same 3x3 weights (+ the fused shortcut's 1x1 weights behind them) in MFMA fragment order for convws_kernel (conv_ws.hip), or the
                      // dense weights in fragment order for gemmws_kernel (gemm_ws.hip); may be null
+  const f16* Wfr4;   // GF_UPS2 convs: the four phase sets of collapsed 2x2 weights for the phase build of convws_kernel (tile ids 56 / 57,
+                     // pack_conv_ws_ups4_kernel in conv_ws.hip); may be null
   void* C;           // fp16 [M][ldc] (or fp32 with GF_OUT_F32)
   float* part;       // split-K partial slabs [splits][M][N] fp32 (when splits > 1)
   const float* bias; // fp32
@@ -518,9 +520,10 @@ void dtp_gemm_wide_init();
 // conv_halo.hip: variant 0..3 = (8x16|8x8 pixel tile) x (64|128 output channels); kb_per_split counts 64-channel blocks
 constexpr int DTP_TILE_LNLIN = 50;  // lnlin_kernel (lnlin.hip): the "splits" of a tune entry are its column ranges, K is not split
 constexpr int DTP_TILE_WS0 = 51;    // convws_kernel (conv_ws.hip): 51 = three 8 x 8 images, 52 = one 16 x 16 image, 53 = an 8 x 16 pixel tile x 64 channels per workgroup, 54 = the same for two co-resident workgroups per CU; splits = K-slices
-constexpr int DTP_WS_VARIANTS = 4;
+constexpr int DTP_WS_VARIANTS = 6;  // convws variants: 0..3 = tile ids 51..54, 4 / 5 = tile ids 56 / 57
 constexpr int DTP_TILE_GEMMWS = 55; // gemmws_kernel (gemm_ws.hip): dense problems with the fragment-order packing; splits = K-slices
-constexpr int DTP_TILE_IDS = 56;    // tile ids are 0 .. DTP_TILE_IDS - 1
+constexpr int DTP_TILE_WSUPS4 = 56; // convws_kernel, phase build for GF_UPS2 (four 2x2 phase convs over the stored map, needs Wfr4): 56 / 57 = the geometry of 53 / 54; unsplit
+constexpr int DTP_TILE_IDS = 58;    // tile ids are 0 .. DTP_TILE_IDS - 1
 
 // profiling classes (dtp_profile_rows): 0-11 = gemm_kernel<BM,BN,NS> variants (id = shape + 4*(NS-2)), then the rest
 enum { PK_GEMM0 = 0, PK_ATTN = 12, PK_GN = 13, PK_LN = 14, PK_ELEM = 15, PK_SOFTMAX = 16, PK_HALO0 = 17, PK_BIG0 = 21, PK_WIDE0 = 25, PK_FP8 = 27, PK_KH2 = 28, PK_LW = 36, PK_XATTN = 44, PK_HALO3 = 45, PK_LNLIN = 47, PK_WS0 = 48, PK_GEMMWS = 52, PK_F8F8 = 53, PK_QUANT8 = 54, PK_COUNT = 55 };
@@ -538,7 +541,7 @@ enum DtpSplit : unsigned char {
 };
 struct DtpTile {
   DtpFamily fam;
-  int var;              // the variant the family's launcher takes: halo 0..5, wide 0..1, fp8 0..4, convws 0..3
+  int var;              // the variant the family's launcher takes: halo 0..5, wide 0..1, fp8 0..4, convws 0..5
   int bm, bn, ns;       // output tile and pipeline depth (0: the family has none)
   int kh, lw;           // gemm_kernel: 1 / 2 k-halves (4 / 8 waves), loader waves (0 = none)
   DtpSplit split;
@@ -548,7 +551,7 @@ struct DtpTile {
 // 0..3.  16..19: gemm_kernel {256x128, 256x128, 128x256, 128x256} at depth {2, 3, 2, 3}.  20 / 21: gemm_wide_kernel 256 x 256 /
 // 256 x 320 (8 waves).  24..27: gemm_fp8_kernel, the shapes of ids 0..3; 28: its 8-wave 256 x 256.  32..39: gemm_kernel with 8 waves
 // (KH = 2), shape (id & 3) at depth 2 + (id - 32) / 4.  40..47: gemm_kernel at depth 3 with 4 (40..43) or 8 loader waves.
-// 48 / 49: conv_halo_kernel variants 4 / 5 (three images per workgroup).  50 / 51..54 / 55: see DTP_TILE_*.  22, 23 and 29..31 are
+// 48 / 49: conv_halo_kernel variants 4 / 5 (three images per workgroup).  50 / 51..54 / 55 / 56..57: see DTP_TILE_*.  22, 23 and 29..31 are
 // holes: TF_NONE, as is any id outside 0 .. DTP_TILE_IDS - 1.
 inline DtpTile dtp_tile(int id) {
   static constexpr int sm[4] = {128, 128, 64, 64}, sn[4] = {128, 64, 64, 128};
@@ -563,7 +566,9 @@ inline DtpTile dtp_tile(int id) {
   if (id >= 40 && id < 48) return {TF_GEMM, 0, sm[s], sn[s], 3, 1, id < 44 ? 4 : 8, SPLIT_K, PK_LW + id - 40};
   if (id == 48 || id == 49) return {TF_HALO, id - 44, 0, 0, 0, 0, 0, SPLIT_HALO, PK_HALO3 + id - 48};
   if (id == DTP_TILE_LNLIN) return {TF_LNLIN, 0, 0, 0, 0, 0, 0, SPLIT_COLS, PK_LNLIN};
-  if (id >= DTP_TILE_WS0 && id < DTP_TILE_WS0 + DTP_WS_VARIANTS) return {TF_CONVWS, id - DTP_TILE_WS0, 0, 0, 0, 0, 0, SPLIT_BLOCKS, PK_WS0 + id - DTP_TILE_WS0};
+  if (id >= DTP_TILE_WS0 && id < DTP_TILE_WS0 + 4) return {TF_CONVWS, id - DTP_TILE_WS0, 0, 0, 0, 0, 0, SPLIT_BLOCKS, PK_WS0 + id - DTP_TILE_WS0};
+  if (id == DTP_TILE_WSUPS4 || id == DTP_TILE_WSUPS4 + 1)  // variants 4 / 5, profiled with the classes of the builds they share a geometry with
+    return {TF_CONVWS, 4 + id - DTP_TILE_WSUPS4, 0, 0, 0, 0, 0, SPLIT_BLOCKS, PK_WS0 + 2 + id - DTP_TILE_WSUPS4};
   if (id == DTP_TILE_GEMMWS) return {TF_GEMMWS, 0, 64, 64, 0, 0, 0, SPLIT_BLOCKS, PK_GEMMWS};
   return {};
 }
@@ -596,13 +601,16 @@ inline int dtp_tile_row_parts(const GemmParams& p, int tile) {
 bool dtp_lnlin_supported(const GemmParams& p, int nsplit);
 int dtp_launch_lnlin(const GemmParams& p, int nsplit, hipStream_t s);
 void dtp_lnlin_init();
-// conv_ws.hip: weight-streaming 3x3 conv (variant 0: three 8 x 8 images, 1: one 16 x 16 image, 2: an 8 x 16 tile x 64 channels per workgroup)
+// conv_ws.hip: weight-streaming 3x3 conv (variant 0: three 8 x 8 images, 1: one 16 x 16 image, 2: an 8 x 16 tile x 64 channels per workgroup,
+// 3: 2 for two co-resident workgroups, 4 / 5: the phase builds of 2 / 3 for GF_UPS2)
 bool dtp_conv_ws_supported(const GemmParams& p, int variant, int nsplit);
 int dtp_launch_conv_ws(const GemmParams& p, int variant, hipStream_t s);
 void dtp_conv_ws_init();
 size_t dtp_conv_ws_packed_elems(int Cout, int Cin, int Cin2);
 int dtp_conv_ws_gn_chunks(int Ho, int Wo);  // GF_GNSTATS partials per image (two per 8 x 16 pixel tile, partial tiles included)
 int dtp_launch_pack_conv_ws(const float* w, const float* w1, f16* out, int Cout, int Cin, int Cin2, hipStream_t s);
+size_t dtp_conv_ws_ups4_packed_elems(int Cout, int Cin);  // the four phase sets of a GF_UPS2 conv (variants 4 / 5)
+int dtp_launch_pack_conv_ws_ups4(const float* w, f16* out, int Cout, int Cin, hipStream_t s);
 // gemm_ws.hip: weight-streaming dense GEMM (64 x 64 per workgroup, the waves split the contraction by k-blocks)
 bool dtp_gemm_ws_supported(const GemmParams& p, int nsplit);
 int dtp_launch_gemm_ws(const GemmParams& p, hipStream_t s);

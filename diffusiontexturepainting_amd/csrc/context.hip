@@ -53,6 +53,7 @@ int dtp_create(int device, int resolution, int max_batch, dtp_ctx** out) {
   c->tune_lnlin = !on("DTP_NO_LNLIN"); c->tune_halo3 = !on("DTP_NO_HALO3");
   c->xchain = !on("DTP_NO_XCHAIN"); c->xattn_tiles = !on("DTP_XATTN_CT1");
   if (const char* e = getenv("DTP_FFCHAIN")) c->ffchain = atoi(e);
+  if (const char* e = getenv("DTP_UPS_PHASE")) c->ups_phase = std::min(std::max(atoi(e), 0), 3);
   *out = (dtp_ctx*)c;
   return DTP_OK;
 }
@@ -234,6 +235,16 @@ int dtp_set_option(dtp_ctx* ctx, const char* name, int value) {
   if (!strcmp(name, "use_graph")) { c->use_graph = value != 0; return DTP_OK; }
   if (!strcmp(name, "autotune")) { c->autotune = value != 0; return DTP_OK; }
   if (!strcmp(name, "check_finite")) { c->check_finite = value != 0; return DTP_OK; }
+  if (!strcmp(name, "ups_phase")) {  // 1 = the tuner decides, 2 / 3 = tile 56 / 57 wherever it applies, 0 = never (the packing itself is chosen at dtp_create: $DTP_UPS_PHASE)
+    if (value < 0 || value > 3) { dtp_set_error("dtp_set_option: ups_phase %d is not 0 .. 3", value); return DTP_ERR_ARG; }
+    if (!c->unet_progs.empty() || !c->enc_progs.empty() || !c->dec_progs.empty()) {
+      dtp_set_error("dtp_set_option: ups_phase must be chosen before the first launch program is built");
+      return DTP_ERR_STATE;
+    }
+    if (value && !c->ups_phase && c->finalized) { dtp_set_error("dtp_set_option: ups_phase was 0 when the weights were packed"); return DTP_ERR_STATE; }
+    c->ups_phase = value;
+    return DTP_OK;
+  }
   if (!strcmp(name, "fuse_gn_conv")) {
 #ifndef DTP_EXPERIMENTAL
     if (value) { dtp_set_error("dtp_set_option: fuse_gn_conv is an experiment (slower: DESIGN.md 3.6) -- build with DTP_EXPERIMENTAL=1"); return DTP_ERR_ARG; }

@@ -44,7 +44,7 @@ __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)
 // CO: the configuration for TWO co-resident workgroups per CU (<= 80 KB of LDS, <= 256 registers): the four partial tiles are combined
 // one n-tile at a time (the combine area is then no larger than the three patch buffers) and the patch fragments use two register
 // sets instead of three (no request across the channel-block boundary: the co-resident workgroup's waves cover that latency).
-template <int TH, int TW, int NI, int NT, bool CO = false>
+template <int TH, int TW, int NI, int NT, bool CO = false, int TAPS = 9>
 struct WsGeom {
   static constexpr int PW = TW + 3, PH = TH + 2;        // patch pitch (odd) and rows, in pixel slots
   static constexpr int HP1 = PH * PW, HP = NI * HP1;    // slots per image / per pixel group
@@ -58,11 +58,12 @@ struct WsGeom {
   static constexpr int STATB = (NI == 1 && NT == 2) ? (4 * NT * 32 * 2 + NT * 32 * 2) * 8 : 0;  // GF_GNSTATS: per-wave and per-workgroup channel sums (fp64)
   static constexpr int LDS = MAINB + STATB;
   static constexpr int LT = (HL - 1) / (NT * TM);       // the tap in which the last patch piece of a channel block is issued
-  static constexpr int WAITB = (17 - LT) * NT;          // vmcnt at the per-block barrier (see the main loop)
+  static constexpr int WAITB = (2 * TAPS - 1 - LT) * NT;  // vmcnt at the per-block barrier (see the main loop)
   static_assert(TW == 8 || TW == 16, "pixel tile width");
   static_assert(TH % RPT == 0 && (NI * TH * TW) % 32 == 0, "whole MFMA tiles");
   static_assert(HP * 128 < 65536, "fragment offsets are 16-bit immediates");
-  static_assert(LT < 8 && WAITB < 64, "patch pieces fit in the taps before the barrier; vmcnt is a 6-bit counter");
+  static_assert(TAPS == 9 || (TAPS == 4 && TH == 8 && TW == 16 && NI == 1 && NT == 2), "nine taps, or the four of the phase build");
+  static_assert(LT < TAPS - 1 && WAITB < 64, "patch pieces fit in the taps before the barrier; vmcnt is a 6-bit counter");
   static_assert(LDS <= (CO ? 80 : 160) * 1024, "LDS");
 };
 
@@ -95,6 +96,39 @@ __global__ void pack_conv_ws_tail_kernel(const float* __restrict__ w, f16* __res
   }
 }
 
+// Phase weights of a conv over the nearest-2x upsample (GF_UPS2; the TAPS = 4 build below).  Output row 2 i + py reads upsampled rows
+// 2 i + py - 1 .. 2 i + py + 1 = source rows (i - 1, i, i) for py = 0 and (i, i, i + 1) for py = 1, columns alike: the nine taps of an
+// output pixel of parity (py, px) fall on a 2 x 2 block of source pixels, and the conv is four 2 x 2 convs over the stored map whose
+// kernels are sums of the original taps -- parity 0: {0}, {1, 2}; parity 1: {0, 1}, {2}.  Phase tap r of parity py reads source row
+// i - 1 + py + r.  Four fragment-ordered sets, phase-major: fragment f = (((ph * nts + nt) * ncb + cb) * 4 + w) * 4 + tap, ph = 2 py + px,
+// tap = 2 ry + rx; elements as in pack_conv_ws_kernel.  A collapsed weight is summed in fp32 (ky ascending, kx ascending inside) and
+// rounded to fp16 ONCE.
+__global__ void pack_conv_ws_ups4_kernel(const float* __restrict__ w, f16* __restrict__ out, int Cout, int Cin, long long total) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int e = (int)(i & 7), l = (int)((i >> 3) & 63);
+    long long f = i >> 9;
+    const int tap = (int)(f & 3); f >>= 2;
+    const int wq = (int)(f & 3); f >>= 2;
+    const int ncb = Cin >> 6, nts = (Cout + 31) >> 5;
+    const int cb = (int)(f % ncb); f /= ncb;
+    const int nt = (int)(f % nts), ph = (int)(f / nts);
+    const int py = ph >> 1, px = ph & 1, ry = tap >> 1, rx = tap & 1;
+    const int ky0 = ry ? 1 + py : 0, ky1 = ry ? 2 : py, kx0 = rx ? 1 + px : 0, kx1 = rx ? 2 : px;  // the tap set [k0, k1] of (parity, phase tap)
+    const int n = nt * 32 + (l & 31), ch = cb * 64 + 16 * wq + 8 * (l >> 5) + e;
+    float sum = 0.f;
+    if (n < Cout) {
+      const float* src = w + ((size_t)n * Cin + ch) * 9;
+      bool first = true;
+      for (int ky = ky0; ky <= ky1; ++ky)
+        for (int kx = kx0; kx <= kx1; ++kx) {
+          sum = first ? src[ky * 3 + kx] : sum + src[ky * 3 + kx];
+          first = false;
+        }
+    }
+    out[i] = (f16)sum;
+  }
+}
+
 // fragment of tile J for tap row KY: the lane's column term + a compile-time row offset (tile J = image J / TPI, rows RPT * (J % TPI) ..)
 template <class G, int KY, int J>
 __device__ __forceinline__ void rd_frags(f16x8 (&dst)[G::TM], uint32_t ct) {
@@ -106,10 +140,26 @@ __device__ __forceinline__ void rd_frags(f16x8 (&dst)[G::TM], uint32_t ct) {
 
 // RAG (GF_RAGGED): the map is covered by ceil(H / TH) x ceil(W / TW) tiles; pixels of the last row / column of tiles that
 // lie outside it read zeros (patch and shortcut), store nothing and add nothing to the GroupNorm sums.  RAG = false is the aligned build.
-template <int TH, int TW, int NI, int NT, bool NTW, bool CO = false, bool RAG = false>
+//
+// TAPS = 4, the phase build (GF_UPS2 with Ho = 2 Hi, Wo = 2 Wi; variants 4 / 5 = the geometry of variants 2 / 3): the window slides over
+// the STORED Hi x Wi map and a workgroup computes ONE output parity (py, px) of its 8 x 16 source tile with the phase's four collapsed
+// taps (pack_conv_ws_ups4_kernel) -- 4 x the workgroups, K = 4 Cin each: 4/9 of the multiply-adds of the fused gather.  What changes:
+//   * decode: the phase is the low two bits of the unit index, so the pixel groups of one (n-range, phase) -- the readers of one weight
+//     stream -- follow the placement rule of the units below (4 x the units: a multiple of 8 whenever the n-range count is even);
+//   * the patch is the same 10 x 19 slots with the one-pixel halo (all of it is staged; the phase reads 9 x 17 of it), the phase is a
+//     workgroup-uniform shift inside it: phase tap (ry, rx) of pixel (y, x) reads slot (y + ry + py, x + rx + px) -- colterm[rx] carries
+//     + px columns and + py rows, the same three column shifts 0 .. 2 as the nine-tap build (so the same conflict-free lane groups);
+//   * the epilogue stores pixel (y, x) of the tile at (2 y + py, 2 x + px) of the 2 Hi x 2 Wi output; the GroupNorm partials of
+//     (source tile t, phase) go to chunk pair 4 t + phase of the (2 Hi / 8)(2 Wi / 16) = 4 x source-tile pairs the consumer expects;
+//   * the counts that were derived from nine taps, re-derived in the main loop's comment.
+// Unsplit only, no fused shortcut (dtp_conv_ws_supported).
+template <int TH, int TW, int NI, int NT, bool NTW, bool CO = false, bool RAG = false, int TAPS = 9>
 __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParams p) {
-  using G = WsGeom<TH, TW, NI, NT, CO>;
+  using G = WsGeom<TH, TW, NI, NT, CO, TAPS>;
   constexpr int TM = G::TM, HL = G::HL, PW = G::PW, PH = G::PH, HP1 = G::HP1, PB = G::PBYTES, NTM = NT * TM;
+  constexpr bool PHASE = TAPS == 4;
+  constexpr int LAST = TAPS - 1, KW = PHASE ? 2 : 3;  // the last tap of a channel block; taps per window row
+  static_assert(!(PHASE && RAG), "the phase build covers aligned maps only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -126,19 +176,23 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
   // (round 5: this decode was nine integer divisions, two of them 64-bit -- ~500 instructions in front of the first memory request of
   // a 20-50 us launch.  Map sizes and tile counts are powers of two everywhere in this model: shifts on that path, one division pair
   // for the block index, none for the K-slices of an unsplit launch; the general forms stay as the fallback.)
-  const int H = p.Ho, W = p.Wo;
+  // (phase build: H x W = the stored map; the output has 4 H W pixels per image)
+  const int H = PHASE ? p.Hi : p.Ho, W = PHASE ? p.Wi : p.Wo;
   const int tiles_x = RAG ? (W + TW - 1) / TW : W / TW, tiles_y = RAG ? (H + TH - 1) / TH : H / TH;  // (TW, TH: compile-time powers of two)
   const int hw = H * W;
   const bool pow2 = ((hw & (hw - 1)) | (tiles_x & (tiles_x - 1)) | (tiles_y & (tiles_y - 1))) == 0;
-  const int images = pow2 ? (p.M >> __builtin_ctz(hw)) : p.M / hw;
+  const int mrows = PHASE ? p.M >> 2 : p.M;  // rows of the map the window slides over
+  const int images = pow2 ? (mrows >> __builtin_ctz(hw)) : mrows / hw;
   const int npg = (images / NI) * tiles_y * tiles_x;
   const int nts = (p.N + 31) >> 5, nrs = (nts + NT - 1) / NT, S = p.splits;
-  const int units = nrs * S;
+  const int units = nrs * S * (PHASE ? 4 : 1);
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
   int pg, u;
   if ((units & 7) == 0) { const int q = idx / npg; pg = idx - q * npg; u = q * 8 + xcd; }
   else { const int pgq = (npg + 7) >> 3; const int q = idx / pgq; pg = (idx - q * pgq) * 8 + xcd; u = q; }
   if (u >= units || pg >= npg) return;
+  const int phase = PHASE ? u & 3 : 0, phy = phase >> 1, phx = phase & 1;  // output parity (phase build)
+  if (PHASE) u >>= 2;
   const int ncb = p.Cin >> 6;
   int z = 0, nr = u, mb0 = 0, mb1 = ncb;  // channel blocks [mb0, mb1)
   if (S > 1) {
@@ -156,23 +210,23 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
 
   // ---- weight ring first: fragment (n-tile, cb, tap) of this wave's channel quarter; the loads of the first channel block are in
   // flight while the patch addresses are computed.  An n-tile beyond N (odd n-tile count, NT = 2) loads zeros.
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wfr, 0, (int)0x80000000u, 0x00020000);
+  const auto rsW = __builtin_amdgcn_make_buffer_rsrc((void*)(PHASE ? p.Wfr4 : p.Wfr), 0, (int)0x80000000u, 0x00020000);
   constexpr int OOB = (int)0x80000000u;
-  int wvoff[NT], wbase[NT];  // fragment index = ((wbase + cb * 4) * 9 + tap)
+  int wvoff[NT], wbase[NT];  // fragment index = ((wbase + cb * 4) * TAPS + tap); phase build: the phase's set = nts n-tiles further each
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int nt = nr * NT + i;
     wvoff[i] = nt < nts ? lane * 16 : OOB;
-    wbase[i] = (nt < nts ? nt : 0) * ncb * 4 + wave;
+    wbase[i] = (phase * nts + (nt < nts ? nt : 0)) * ncb * 4 + wave;
   }
   auto wload = [&](int i, int cb, int tap) -> f16x8 {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsW, wvoff[i], ((wbase[i] + cb * 4) * 9 + tap) * 1024, NTW ? 2 : 0);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsW, wvoff[i], ((wbase[i] + cb * 4) * TAPS + tap) * 1024, NTW ? 2 : 0);
     return __builtin_bit_cast(f16x8, v);
   };
-  f16x8 wf[NT][9];
+  f16x8 wf[NT][TAPS];
   if (mb0 < mb1) {
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+    for (int t = 0; t < TAPS; ++t)
 #pragma unroll
       for (int i = 0; i < NT; ++i) wf[i][t] = wload(i, mb0, t);
   }
@@ -185,7 +239,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)0x80000000u, 0x00020000);
   int voffA[HL];
   {
-    const int ups = (p.flags & GF_UPS2) ? 1 : 0;
+    const int ups = (!PHASE && (p.flags & GF_UPS2)) ? 1 : 0;  // (phase build: the patch is a tile of the stored map itself)
     const int s0 = wave * 8 + (lane >> 3);  // < 32 <= HP1
     int il = 0, hy = s0 / PW, hx = s0 - hy * PW;
     constexpr int DY = 32 / PW, DX = 32 - DY * PW;
@@ -217,8 +271,8 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
   const int pxl = frow % TW, pyl = frow / TW;
   uint32_t colterm[3];
 #pragma unroll
-  for (int kx = 0; kx < 3; ++kx)
-    colterm[kx] = lds_addr(smem) + (pyl * PW + pxl + kx) * 128 + ((((2 * wave + fhalf) ^ ((pxl + kx) & 7))) << 4);
+  for (int kx = 0; kx < KW; ++kx)  // (phase build: + phx columns, + phy rows; column pxl + kx + phx <= TW + 1, row <= PH - 1: inside the patch)
+    colterm[kx] = lds_addr(smem) + ((pyl + phy) * PW + pxl + kx + phx) * 128 + ((((2 * wave + fhalf) ^ ((pxl + kx + phx) & 7))) << 4);
 
   f32x16 acc[NT][TM];
 #pragma unroll
@@ -238,10 +292,21 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
   // vmcnt at the barrier: the ops younger than the last piece of patch(cb + 1) (issued in tap LT of cb - 1) are wload(cb, LT..8) and,
   // during cb, the pieces of patch(cb + 2) (if any) and wload(cb + 1, 0..7): (17 - LT) NT, + HL -- waiting for the smaller count is
   // exact or stricter.
-  constexpr int NBF = CO ? 2 : 3;
+  // Phase build (TAPS = 4), the same schedule counted again:
+  //   * weight ring: wf[NT][4] -- fragment (cb + 1, t) is requested right after tap t of cb, a whole channel block = 4 taps = 4 NT TM
+  //     MFMAs ahead of its use (nine-tap build: 9 taps); the ring is as deep as the block is long in both;
+  //   * fragment sets: tap t uses set t % 2 and requests set (t + 1) % 2.  4 = 0 mod 2: tap 3 uses set 1 and set 0 (last read by tap 2's
+  //     MFMAs) is free for tap 0 of the next block, requested right behind the barrier -- TWO sets roll across the block boundary, in the
+  //     co-resident build too (nine taps: 9 = 1 mod 2 is why that build requests tap 0 only after tap 8's MFMAs);
+  //   * patch pieces: HL = 6 <= NT TM = 8, all of patch(cb + 2) is issued in tap 0 of cb: LT = 0 < 3, the barrier's tap;
+  //   * vmcnt at the barrier (start of tap 3 of cb): younger than the last piece of patch(cb + 1) (tap 0 of cb - 1) are
+  //     wload(cb, 0..3) and, during cb, the pieces of patch(cb + 2) (if any) and wload(cb + 1, 0..2): (4 + 3) NT = 14 = (2 TAPS - 1 - LT) NT,
+  //     + HL -- the general form of the nine-tap (17 - LT) NT.
+  constexpr bool XB = !CO || PHASE;  // tap 0 of the next block is requested before the last tap's MFMAs (a free fragment set exists)
+  constexpr int NBF = PHASE ? 2 : CO ? 2 : 3;
   f16x8 bf[NBF][TM];
   auto rd = [&](auto tapc, uint32_t bo, f16x8 (&dst)[TM]) {
-    constexpr int TAP = decltype(tapc)::value, KY = TAP / 3, KX = TAP % 3;
+    constexpr int TAP = decltype(tapc)::value, KY = TAP / KW, KX = TAP % KW;
 #ifndef DTP_WS_NO_LDSREAD
     rd_frags<G, KY, 0>(dst, colterm[KX] + bo);
 #else
@@ -264,7 +329,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
 #else
 #define DTP_WS_WAIT(n, f) wait_lds_frags<n, TM>(f)
 #endif
-        if constexpr (TAP < 8) {
+        if constexpr (TAP < LAST) {
           rd(std::integral_constant<int, TAP + 1>{}, bo, bf[NXT]);
           __builtin_amdgcn_sched_barrier(0);
           DTP_WS_WAIT(TM, bf[CUR]);
@@ -273,7 +338,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
           if constexpr (MORE) {
             wait_vmcnt<G::WAITB>();
             __builtin_amdgcn_s_barrier();
-            if constexpr (!CO) {
+            if constexpr (XB) {
               rd(std::integral_constant<int, 0>{}, bo1, bf[NXT]);
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -305,13 +370,16 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
           for (int i = 0; i < NT; ++i) wf[i][TAP] = wload(i, cb + 1, TAP);
 #endif
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (CO && TAP == 8) rd(std::integral_constant<int, 0>{}, bo1, bf[0]);  // two sets: tap 8 has just released set 0
+          if constexpr (!XB && TAP == LAST) rd(std::integral_constant<int, 0>{}, bo1, bf[0]);  // two sets, nine taps: tap 8 has just released set 0
         }
       };
 #undef DTP_WS_WAIT
       tap(std::integral_constant<int, 0>{}); tap(std::integral_constant<int, 1>{}); tap(std::integral_constant<int, 2>{});
-      tap(std::integral_constant<int, 3>{}); tap(std::integral_constant<int, 4>{}); tap(std::integral_constant<int, 5>{});
-      tap(std::integral_constant<int, 6>{}); tap(std::integral_constant<int, 7>{}); tap(std::integral_constant<int, 8>{});
+      tap(std::integral_constant<int, 3>{});
+      if constexpr (TAPS == 9) {
+        tap(std::integral_constant<int, 4>{}); tap(std::integral_constant<int, 5>{});
+        tap(std::integral_constant<int, 6>{}); tap(std::integral_constant<int, 7>{}); tap(std::integral_constant<int, 8>{});
+      }
     };
     typedef std::true_type Y;
     typedef std::false_type N_;
@@ -336,7 +404,7 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
   // waves x 32-byte pieces of every line = 4 x the L2 traffic, 13 us for the eight blocks of an M = 192 slice).  Tiles are requested
   // D tiles ahead (a register ring), across block boundaries; blocks beyond the slice carry
   // out-of-range offsets: zeros, which add nothing.  Weight fragments of block tb: tbase + tb * 4 + k-step, behind the 3x3 fragments.
-  if (p.A2 && !(p.sm_valid & 1)) {
+  if (TAPS == 9 && p.A2 && !(p.sm_valid & 1)) {  // (the phase build takes no shortcut: dtp_conv_ws_supported)
     const int ntb = p.Cin2 >> 6;
     const int tk0 = (int)((long long)z * ntb / S), tk1 = (int)((long long)(z + 1) * ntb / S);
     if (tk0 < tk1) {
@@ -459,7 +527,8 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
         for (int e = 0; e < 4; ++e) v[e] = ((v0[e] + v1[e]) + v2[e]) + v3[e];
         const int il = j / G::TPI, py = G::RPT * (j % G::TPI) + epyl;
         if (RAG && (y0 + py >= H || x0 + epxl >= W)) continue;  // outside the map: no store, no residual, no statistics
-        const size_t m = ((size_t)(img0 + il) * H + y0 + py) * W + x0 + epxl;
+        const size_t m = PHASE ? ((size_t)(img0 + il) * p.Ho + 2 * (y0 + py) + phy) * p.Wo + 2 * (x0 + epxl) + phx  // parity (phy, phx) of the 2 H x 2 W output
+                               : ((size_t)(img0 + il) * H + y0 + py) * W + x0 + epxl;
         if (!ncol) continue;
         if (p.splits > 1) {
           *(f32x4*)(p.part + ((size_t)z * p.M + m) * p.N + n) = v;
@@ -514,7 +583,8 @@ __global__ __launch_bounds__(256, CO ? 2 : 1) void convws_kernel(const GemmParam
         const int a = max(g * cpg, c_lo), b = min((g + 1) * cpg, c_hi);
         double sg = 0.0, qg = 0.0;
         for (int c = a; c < b; ++c) { sg += tot[(c - c_lo) * 2]; qg += tot[(c - c_lo) * 2 + 1]; }
-        const int ntile = tiles_x * tiles_y, pt = ty * tiles_x + tx;
+        // (phase build: pair 4 t + phase of the 4 tiles_x tiles_y pairs of the output map -- a bijection onto the consumer's chunk indices)
+        const int ntile = tiles_x * tiles_y * (PHASE ? 4 : 1), pt = (ty * tiles_x + tx) * (PHASE ? 4 : 1) + phase;
         float* const base = p.st_out + ((size_t)img0 * 2 * ntile + 2 * pt) * groups * 2;
         float* const mine = base + (size_t)(nr & 1) * groups * 2 + g * 2;
         mine[0] = (float)sg; mine[1] = (float)qg;
@@ -553,6 +623,27 @@ int launch_ws(const GemmParams& p, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
 }
 
+// the phase build of variants 2 / 3 (TAPS = 4): pixel groups = 8 x 16 tiles of the STORED map, 4 x the units (the phase rides in the unit)
+template <bool CO>
+int launch_ws_phase(const GemmParams& p, hipStream_t s) {
+  using G = WsGeom<8, 16, 1, 2, CO, 4>;
+  const int npg = (p.M / (p.Ho * p.Wo)) * (p.Hi / 8) * (p.Wi / 16);
+  const int units = (((p.N + 31) >> 5) + 1) / 2 * 4;
+  const int blocks = (units & 7) == 0 ? units * npg : ((npg + 7) >> 3) * 8 * units;  // the kernel's two block -> (pixel group, unit) maps
+  static const int dbg = [] { const char* e = getenv("DTP_WS_DEBUG"); return e ? atoi(e) : 0; }();
+  GemmParams q = p;
+  q.sm_valid = dbg & 3;
+  const bool nt = (dbg & 4) ? false : (dbg & 8) ? true : npg == 1;  // (as launch_ws: one reader per fragment streams past the caches)
+  if (nt) hipLaunchKernelGGL((convws_kernel<8, 16, 1, 2, true, CO, false, 4>), dim3(blocks), dim3(256), G::LDS, s, q);
+  else hipLaunchKernelGGL((convws_kernel<8, 16, 1, 2, false, CO, false, 4>), dim3(blocks), dim3(256), G::LDS, s, q);
+  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
+}
+template <bool CO>
+void set_ws_phase_attr() {
+  (void)hipFuncSetAttribute((const void*)convws_kernel<8, 16, 1, 2, true, CO, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<8, 16, 1, 2, CO, 4>::LDS);
+  (void)hipFuncSetAttribute((const void*)convws_kernel<8, 16, 1, 2, false, CO, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<8, 16, 1, 2, CO, 4>::LDS);
+}
+
 template <int TH, int TW, int NI, int NT, bool CO = false>
 void set_ws_attr() {
   (void)hipFuncSetAttribute((const void*)convws_kernel<TH, TW, NI, NT, true, CO>, hipFuncAttributeMaxDynamicSharedMemorySize, WsGeom<TH, TW, NI, NT, CO>::LDS);
@@ -570,6 +661,8 @@ void dtp_conv_ws_init() {
   set_ws_attr<16, 16, 1, 1>();
   set_ws_attr<8, 16, 1, 2>();
   set_ws_attr<8, 16, 1, 2, true>();
+  set_ws_phase_attr<false>();
+  set_ws_phase_attr<true>();
 }
 
 // GF_GNSTATS partials per image of a variant 2 / 3 launch: two per 8 x 16 pixel tile (ragged maps: the partial tiles count)
@@ -592,13 +685,36 @@ int dtp_launch_pack_conv_ws(const float* w, const float* w1, f16* out, int Cout,
   return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
 }
 
+// elements of the four phase sets of a conv over the nearest-2x upsample (pack_conv_ws_ups4_kernel): 16/9 of the nine-tap packing
+size_t dtp_conv_ws_ups4_packed_elems(int Cout, int Cin) { return (size_t)((Cout + 31) / 32) * (size_t)(Cin / 64) * 4 * 16 * 512; }
+
+// w: [Cout][Cin][3][3] -> the four phase sets
+int dtp_launch_pack_conv_ws_ups4(const float* w, f16* out, int Cout, int Cin, hipStream_t s) {
+  if (Cout < 1 || Cin < 64 || (Cin & 63)) { dtp_set_error("pack_conv_ws_ups4: Cin %d must be a multiple of 64", Cin); return DTP_ERR_ARG; }
+  const long long total = (long long)dtp_conv_ws_ups4_packed_elems(Cout, Cin);
+  const int blocks = (int)((total + 255) / 256 > 65535 ? 65535 : (total + 255) / 256);
+  hipLaunchKernelGGL(pack_conv_ws_ups4_kernel, dim3(blocks), dim3(256), 0, s, w, out, Cout, Cin, total);
+  return hipGetLastError() == hipSuccess ? DTP_OK : DTP_ERR_HIP;
+}
+
 // variant 0: pixel group = three 8 x 8 images (the image IS the tile), one n-tile per workgroup; variant 1: one 16 x 16 image, one
 // n-tile; variant 2: an 8 x 16 pixel tile of one image of any size (H % 8 == 0, W % 16 == 0), TWO n-tiles (64 output channels) per
 // workgroup; variant 3: variant 2 built for two co-resident workgroups per CU (WsGeom CO).  Variants 2 / 3 with GF_RAGGED: a map of any
 // size (ceil(H / 8) x ceil(W / 16) tiles, the ragged build), and with GF_UPS2 an output of 2 Hi - 1 (the upsample cropped by one row /
 // column: the reference's interpolate(size=skip) at an odd level).  Stride 1, pad 1 (optionally over the nearest-2x upsample of the input: GF_UPS2), Cin % 64 == 0 (and Cin2 % 64 == 0 with a fused shortcut).  nsplit K-slices (<= Cin / 64), each a
 // range of whole channel blocks; nsplit > 1 leaves fp32 slabs.
+// Variants 4 / 5: the phase build of variants 2 / 3 (tile ids 56 / 57) -- GF_UPS2 with the output exactly 2 Hi x 2 Wi, Hi % 8 == 0,
+// Wi % 16 == 0, the phase weights (Wfr4), no fused shortcut, unsplit.  The cropped 2 Hi - 1 output of GF_RAGGED is refused: there the
+// row / column behind the crop is zero padding, not upsampled data, and the collapsed taps would be wrong.  Everything else as variants 2 / 3.
 bool dtp_conv_ws_supported(const GemmParams& p, int variant, int nsplit) {
+  if (variant == 4 || variant == 5) {
+    if (!p.Wfr4 || !(p.flags & GF_UPS2) || p.A2 || nsplit != 1) return false;
+    if (p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi || (p.Hi & 7) || (p.Wi & 15)) return false;
+    if (dtp_conv_ws_ups4_packed_elems(p.N, p.Cin) * 2 >= ((size_t)1 << 31)) return false;
+    GemmParams q = p;
+    if (!q.Wfr) q.Wfr = q.Wfr4;  // (the nine-tap packing is not what this build reads)
+    return dtp_conv_ws_supported(q, variant - 2, 1);
+  }
   if (!p.Wfr || !(p.flags & GF_CONV3) || p.batch > 1) return false;
   if (p.A2 && ((p.Cin2 & 63) || (p.lda2 & 7) || (size_t)p.M * p.lda2 * 2 >= ((size_t)1 << 31))) return false;
   if (p.flags & (GF_GEGLU | GF_OUT_F32 | GF_LNFOLD | GF_ROWSTATS | GF_BIAS_M | GF_GELU | GF_QUICKGELU | GF_SILU | GF_GNAPPLY | GF_SOFTMAX16)) return false;
@@ -628,7 +744,8 @@ int dtp_launch_conv_ws(const GemmParams& pin, int variant, hipStream_t s) {
     dtp_set_error("conv_ws: unsupported problem (M %d N %d Cin %d %dx%d flags %#x, variant %d, %d slices)", pin.M, pin.N, pin.Cin, pin.Hi, pin.Wi, pin.flags, variant, pin.splits);
     return DTP_ERR_ARG;
   }
-  const int rc = variant == 0 ? launch_ws<8, 8, 3, 1>(pin, s) : variant == 1 ? launch_ws<16, 16, 1, 1>(pin, s) : variant == 2 ? launch_ws<8, 16, 1, 2>(pin, s) : launch_ws<8, 16, 1, 2, true>(pin, s);
+  const int rc = variant == 0 ? launch_ws<8, 8, 3, 1>(pin, s) : variant == 1 ? launch_ws<16, 16, 1, 1>(pin, s) : variant == 2 ? launch_ws<8, 16, 1, 2>(pin, s)
+               : variant == 3 ? launch_ws<8, 16, 1, 2, true>(pin, s) : variant == 4 ? launch_ws_phase<false>(pin, s) : launch_ws_phase<true>(pin, s);
   if (rc != DTP_OK) { dtp_set_error("conv_ws launch failed: %s", hipGetErrorString(hipGetLastError())); return rc; }
   if (pin.splits > 1 && !(pin.flags & GF_NOREDUCE)) return dtp_launch_splitk_reduce(pin, s);
   return DTP_OK;

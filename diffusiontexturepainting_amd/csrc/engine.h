@@ -29,6 +29,7 @@ struct ConvW {  // 3x3 (taps = 9) or 1x1 (taps = 1) convolution / any Linear (ta
   f16* wcb = nullptr;  // 3x3 only: channel-block-major packing for conv_halo_kernel (Cin % 64 == 0, no fused shortcut)
   f16* wfr = nullptr;  // UNet only: MFMA-fragment-order packing -- of a 3x3 conv for convws_kernel (conv_ws.hip; Cin % 64 == 0, + the fused shortcut),
                        // of a Linear for gemmws_kernel (gemm_ws.hip; K % 64 == 0)
+  f16* wfr4 = nullptr; // upsampler convs (GF_UPS2) only: the four phase sets of collapsed 2x2 weights (load_conv_ups4; conv_ws.hip tile ids 56 / 57)
   float* b = nullptr;  // fp32 bias (may be null)
   float* lns = nullptr;  // LayerNorm folded in: row sums of the packed weights (GF_LNFOLD)
   int cout = 0, cin = 0 /* padded */, cin_true = 0, taps = 1, K = 0, ldw = 0;
@@ -338,6 +339,8 @@ struct Ctx {
   bool fuse_reduce_gn = true;     // fold a split-K conv's reduce into the GroupNorm that consumes it ($DTP_NO_FUSE_REDUCE_GN=1: off, A/B)
   bool pack_ws = false;           // load_conv also builds the fragment-order packing (set while the UNet's / VAE's weights load, from the two below)
   bool conv_ws = true, conv_ws_vae = true;  // weight-streaming conv: packing + tuner candidates / the VAE's packing ($DTP_NO_WS=1 / $DTP_NO_WS_VAE=1: off, A/B)
+  int ups_phase = 1;              // phase form of the upsampler convs: 0 = no phase packing, 1 = packed, a tuner candidate, 2 / 3 = tile 56 / 57 forced
+                                  // wherever it applies ($DTP_UPS_PHASE, option "ups_phase": tests, A/B)
   bool gemm_ws = false;           // fragment-order packing of the Linears for gemmws_kernel, tile 55 ($DTP_GEMMWS=1: on, A/B)
   bool gn_epilogue = true;        // GroupNorm statistics from the producing conv's epilogue (Builder::claim_stats; $DTP_NO_GN_EPILOGUE=1: off, A/B)
   bool reduce_in_concat_gn = true;  // ... the split-K reduce folded into a GroupNorm over a concatenation too ($DTP_NO_REDUCE_IN_CONCAT_GN=1: off, A/B)
@@ -412,6 +415,7 @@ int ctx_upload_f32(Ctx* c, const std::vector<float>& v, float** out);
 int load_norm(Ctx* c, const std::string& name, NormW& n);
 // conv weight [Cout][Cin][k][k] -> packed; cin_pad = padded input channels (>= Cin, multiple of 8)
 int load_conv(Ctx* c, const std::string& name, ConvW& w, int cin_pad = 0, bool bias = true);
+int load_conv_ups4(Ctx* c, const std::string& name, ConvW& w);  // after load_conv of a conv that runs over a nearest-2x upsample: its phase sets (ConvW::wfr4)
 // ResBlock tail: conv2 (3x3) and the 1x1 shortcut conv packed as ONE contraction [W2 | Wsc], bias = b2 + bsc
 int load_conv_with_shortcut(Ctx* c, const std::string& conv, const std::string& shortcut, ConvW& w);
 // two Linears in a row with only a residual between them, out = Wb (Wa f + ba + r) + bb, merged into ONE contraction over

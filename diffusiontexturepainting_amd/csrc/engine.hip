@@ -132,6 +132,18 @@ int load_conv(Ctx* c, const std::string& name, ConvW& w, int cin_pad, bool bias)
   return DTP_OK;
 }
 
+// The four phase sets of an upsampler conv (conv_ws.hip, pack_conv_ws_ups4_kernel), next to its nine-tap fragment packing: 16/9 of that
+// packing's bytes.  Only where load_conv built the fragment packing (Ctx::pack_ws, Cin % 64 == 0): without it no weight-streaming tile runs.
+int load_conv_ups4(Ctx* c, const std::string& name, ConvW& w) {
+  if (!c->ups_phase || !w.wfr || w.taps != 9 || w.cin2) return DTP_OK;
+  const Staged* s = ctx_find(c, name + ".weight");
+  if (!s) { dtp_set_error("missing weight '%s.weight'", name.c_str()); return DTP_ERR_MISSING; }
+  void* p;
+  RC(ctx_arena_alloc(c, dtp_conv_ws_ups4_packed_elems(w.cout, w.cin_true) * 2, &p));
+  w.wfr4 = (f16*)p;
+  return dtp_launch_pack_conv_ws_ups4(s->d, w.wfr4, w.cout, w.cin_true, 0);
+}
+
 int load_conv_with_shortcut(Ctx* c, const std::string& conv, const std::string& shortcut, ConvW& w) {
   const Staged *s = ctx_find(c, conv + ".weight"), *t = ctx_find(c, shortcut + ".weight");
   const Staged *sb = ctx_find(c, conv + ".bias"), *tb = ctx_find(c, shortcut + ".bias");

@@ -160,6 +160,8 @@ int tune_gemm(Ctx* c, const GemmParams& p, int* tile, int* sp) {
   bool ws_any = false;
   for (int v = 0; v < DTP_WS_VARIANTS; ++v) { ws_ok[v] = p.Wfr && (p.flags & GF_CONV3) && dtp_conv_ws_supported(p, v, 1); ws_any = ws_any || ws_ok[v]; }
   if (ws_any) kl += snprintf(key + kl, sizeof(key) - kl, ",ws2");
+  // ... and the upsampler convs the phase build takes (variants 4 / 5 = tile ids 56 / 57) were tuned without it: theirs carries another
+  if (ws_ok[4] || ws_ok[5]) kl += snprintf(key + kl, sizeof(key) - kl, ",u4");
   // ... and so do the plain problems the activation-stationary Linear takes since round 4 (attention output projection, grouped proj_in)
   if (!(p.flags & GF_LNFOLD)) {
     bool ll = false;

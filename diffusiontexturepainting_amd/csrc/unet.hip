@@ -155,7 +155,10 @@ int load_unet_weights(Ctx* c) {
       RC(load_res(c, P + "up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), u.up_res[i][j], true, toff, &tn));
       if (i > 0) RC(load_xf(c, P + "up_blocks." + std::to_string(i) + ".attentions." + std::to_string(j), u.up_xf[i][j], kvn));
     }
-    if (i < 3) RC(load_conv(c, P + "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", u.up_conv[i]));
+    if (i < 3) {
+      RC(load_conv(c, P + "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", u.up_conv[i]));
+      RC(load_conv_ups4(c, P + "up_blocks." + std::to_string(i) + ".upsamplers.0.conv", u.up_conv[i]));
+    }
   }
   RC(load_norm(c, P + "conv_norm_out", u.norm_out));
   RC(load_conv(c, P + "conv_out", u.conv_out));

@@ -54,7 +54,10 @@ int load_vae_weights(Ctx* c) {
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < 3; ++j)
       RC(load_res_v(c, P + "decoder.up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j), v.dec_res[i][j]));
-    if (i < 3) RC(load_conv(c, P + "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv", v.dec_up[i]));
+    if (i < 3) {
+      RC(load_conv(c, P + "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv", v.dec_up[i]));
+      RC(load_conv_ups4(c, P + "decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv", v.dec_up[i]));
+    }
   }
   RC(load_norm(c, P + "decoder.conv_norm_out", v.dec_norm_out));
   RC(load_conv(c, P + "decoder.conv_out", v.dec_out));

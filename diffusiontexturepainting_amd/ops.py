@@ -64,6 +64,17 @@ def pack_conv_ws(w, w1=None):
     return out
 
 
+def pack_conv_ws_ups4(w):
+    """w f32 [Cout,Cin,3,3] (Cin % 64 == 0) -> the four phase sets of collapsed 2x2 weights, in MFMA fragment order, that the phase
+    build of convws_kernel streams for a conv over the nearest-2x upsample (tile ids 56 / 57; conv3x3(..., upsample=True, wfr4=))."""
+    lib = _lib.load()
+    cout, cin = w.shape[:2]
+    out = torch.zeros(lib.dtp_op_pack_conv_ws_ups4_elems(cout, cin), dtype=torch.float16, device=w.device)
+    w = w.contiguous().float()
+    check(lib.dtp_op_pack_conv_ws_ups4(ptr(w), ptr(out), cout, cin, _stream()), "pack_conv_ws_ups4")
+    return out
+
+
 def pack_linear_ws(wp, n, k):
     """wp: packed f16 rows of pack_linear (k % 64 == 0) -> the MFMA-fragment-order copy gemmws_kernel streams (tile id 55)."""
     lib = _lib.load()
@@ -219,11 +230,9 @@ def gemm(a, wp, n, k=None, bias=None, resid=None, flags=0, tile=-1, splits=0, ou
     return out
 
 
-def conv3x3(x, wp, cout, stride=1, pad=1, upsample=False, bias=None, resid=None, tile=-1, splits=0, out_hw=None, flags=0,
-            tail=None, wcb=None, wfr=None, gn_groups=0):
-    """x f16 NHWC [B,H,W,C] -> f16 NHWC [B,Ho,Wo,cout].  pad is the top/left zero padding; bottom/right
-    padding is implied by out_hw (default: the symmetric-padding output size)."""
-    lib = _lib.load()
+def _conv3x3_desc(x, wp, cout, stride=1, pad=1, upsample=False, bias=None, resid=None, tile=-1, splits=0, out_hw=None, flags=0,
+                  tail=None, wcb=None, wfr=None, gn_groups=0, wfr4=None):
+    """the descriptor of conv3x3 with its output (and, with gn_groups, statistics) tensors"""
     b, h, w, cin = x.shape
     hv, wv = (2 * h, 2 * w) if upsample else (h, w)
     ho, wo = out_hw or ((hv + 2 * pad - 3) // stride + 1, (wv + 2 * pad - 3) // stride + 1)
@@ -245,12 +254,29 @@ def conv3x3(x, wp, cout, stride=1, pad=1, upsample=False, bias=None, resid=None,
     if wfr is not None:
         d.Wfr = wfr.data_ptr()
     st = None
-    if gn_groups:  # tiles 53 / 54, unsplit: also return the GroupNorm partial sums f32 [B, 2 * tiles, groups, 2] of the output
+    if gn_groups:  # tiles 53 / 54 / 56 / 57, unsplit: also return the GroupNorm partial sums f32 [B, 2 * tiles, groups, 2] of the output
         st = torch.full((b, 2 * ((ho + 7) // 8) * ((wo + 15) // 16), gn_groups, 2), float("nan"), dtype=torch.float32, device=x.device)
         d.st_out, d.gn_cpg = st.data_ptr(), cout // gn_groups
         d.flags |= _lib.GF_GNSTATS
-    check(lib.dtp_op_gemm(C.byref(d), _stream()), "conv3x3")
-    return (out, st) if gn_groups else out
+    return d, out, st
+
+
+def conv3x3(x, wp, cout, *args, **kw):
+    """x f16 NHWC [B,H,W,C] -> f16 NHWC [B,Ho,Wo,cout].  pad is the top/left zero padding; bottom/right
+    padding is implied by out_hw (default: the symmetric-padding output size).  Arguments: _conv3x3_desc; wfr4 (keyword, with
+    upsample=True): the phase sets of pack_conv_ws_ups4 that tiles 56 / 57 read -- the launch then goes through dtp_op_conv_ups4."""
+    d, out, st = _conv3x3_desc(x, wp, cout, *args, **kw)
+    if kw.get("wfr4") is not None:
+        check(_lib.load().dtp_op_conv_ups4(C.byref(d), ptr(kw["wfr4"]), _stream()), "conv3x3")
+    else:
+        check(_lib.load().dtp_op_gemm(C.byref(d), _stream()), "conv3x3")
+    return (out, st) if st is not None else out
+
+
+def conv_ws_supported(x, wp, cout, tile, splits=1, **kw):
+    """Does convws_kernel tile `tile` (51 .. 54, 56 / 57) take the conv conv3x3(x, wp, cout, **kw) would launch?"""
+    d, _, _ = _conv3x3_desc(x, wp, cout, tile=tile, splits=splits, **kw)
+    return bool(_lib.load().dtp_op_conv_ws_supported(C.byref(d), ptr(kw.get("wfr4")), tile, splits))
 
 
 def groupnorm(x, gamma, beta, groups=32, eps=1e-5, silu=False):

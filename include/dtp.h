@@ -940,7 +940,10 @@ typedef struct {
                         51 .. 54 = convws_kernel (weight-streaming 3x3 conv, needs Wfr): 51 = 8x8 images in groups of three (image
                         count % 3 == 0), 52 = 16x16 images, 53 = 8x16 pixel tiles of images with H % 8 == 0, W % 16 == 0 and two
                         n-tiles (64 output channels) per workgroup, 54 = 53 built for two co-resident workgroups per CU; stride 1, pad 1, Cin % 64 == 0 (Cin2 % 64 == 0); `splits` =
-                        K-slices (ranges of whole 64-channel blocks) */
+                        K-slices (ranges of whole 64-channel blocks);
+                        56 / 57 = the phase build of 53 / 54 for upsample2x convs (needs Wfr4): four 2x2 convs over the stored map, one
+                        per output parity -- Ho = 2 Hi, Wo = 2 Wi, Hi % 8 == 0, Wi % 16 == 0, no A2, unsplit (dtp_op_conv_ws_supported);
+                        the phase weights are not in this struct: such a launch goes through dtp_op_conv_ups4 */
   int splits;        /* 0 = heuristic; >=1 = forced split-K factor (conv_halo_kernel: slices are whole 64-channel blocks) */
   const float* lns;  /* DTP_GF_LNFOLD: row sums of the packed weights (dtp_op_rowsum) */
   float ln_eps;
@@ -1017,6 +1020,19 @@ int dtp_op_pack_conv_cb(const float* w, void* out, int Cout, int Cin, int ldw, d
  * or f32 [Cout][Cin2], Cin2 % 64 == 0) = the 1x1 weights of a fused shortcut (desc.A2), packed behind them */
 int dtp_op_pack_conv_ws(const float* w, const float* w1, void* out, int Cout, int Cin, int Cin2, dtp_stream s);
 long long dtp_op_pack_conv_ws_elems(int Cout, int Cin, int Cin2);
+/* w f32 [Cout][Cin][3][3] (Cin % 64 == 0) -> out f16, dtp_op_pack_conv_ws_ups4_elems(Cout, Cin) elements (16/9 of the nine-tap packing):
+ * the weights of the four 2x2 phase convs that equal the 3x3 conv over the nearest-2x upsample, phase = 2 py + px major.  Phase tap
+ * (ry, rx) of parity (py, px) is the sum of the original taps ky in S(py, ry), kx in S(px, rx) with S(0, .) = {0}, {1, 2} and
+ * S(1, .) = {0, 1}, {2}, added in fp32 (ky ascending, kx ascending inside) and rounded to f16 once.  1 KB fragments in the order
+ * ((phase, n-tile of 32 output channels, 64-channel block, channel quarter, tap = 2 ry + rx), lane, 8 channels) */
+int dtp_op_pack_conv_ws_ups4(const float* w, void* out, int Cout, int Cin, dtp_stream s);
+long long dtp_op_pack_conv_ws_ups4_elems(int Cout, int Cin);
+/* dtp_op_gemm for a 3x3 conv with upsample2x that also carries wfr4 = the phase sets of dtp_op_pack_conv_ws_ups4 (not NULL): d->tile
+ * 56 / 57 runs the phase build, any other tile (or -1) runs as dtp_op_gemm would */
+int dtp_op_conv_ups4(dtp_gemm_desc* d, const void* wfr4, dtp_stream s);
+/* 1 when convws_kernel tile `tile` (51 .. 54, 56, 57) takes the conv problem *d (wfr4: its phase sets or NULL) with `splits` K-slices,
+ * else 0 (also for other tiles) */
+int dtp_op_conv_ws_supported(const dtp_gemm_desc* d, const void* wfr4, int tile, int splits);
 /* w f16: the packed rows [>= N][ldw] of dtp_op_pack_linear (K % 64 == 0) -> out f16, dtp_op_pack_linear_ws_elems(N, K) elements: 1 KB
    fragments (32-column n-tile, 64-wide k-block, 16-wide k-step) in the order the weight-streaming GEMM (tile 55) loads them */
 int dtp_op_pack_linear_ws(const void* w, int ldw, void* out, int N, int K, dtp_stream s);
