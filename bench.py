@@ -7,15 +7,18 @@ resident in HBM.  N=1 runs BASELINE.json configs[1] (single 512x512 patch, 20 st
 mode); with N>1 every rank runs the same per-GPU workload on its own stamps (weak scaling) and the
 decoded u8 patches are gathered to rank 0 over RCCL inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--res R] [--ddim-steps S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--res R] [--ddim-steps S] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts its N ranks itself (launch_ranks: rank r -> GPU r, a free rendezvous port on
 127.0.0.1, the synthetic weights generated ONCE and mapped by every rank, one shared tune table that rank 0 completes before the
 others read it).  `--batch 8 --gpus 8` is BASELINE configs[3]: 64 stamps sharded over 8 GPUs, one RCCL gather of the u8 patches.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed inside this
-process) and `cpu_baseline` (the fp32 CPU oracle timed on a bounded sample, rank 0 / N=1 only).
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, the
+outputs if `--dump-outputs` asks for them, the line (`roofline`, `cpu_baseline` and `extra_configs` are null in it).  `--full` adds
+everything else the benchmark measures, each leg with its own `--no-...` switch: `roofline` (the measured MFMA / HBM ceilings before
+the warm-up, then one more stamp with HIP events around every launch), `cpu_baseline` (the fp32 CPU oracle timed on a bounded
+sample, rank 0 / N=1 only) and `extra_configs` (the other BASELINE configurations and the pixel error against the CPU oracle).
 """
 import argparse
 import json
@@ -465,7 +468,15 @@ def launch_classes(path):
             "standalone_splitk_reduce_launches": standalone}
 
 
-def main():
+def full_legs(a, rank, world):
+    """Which legs beyond the headline this rank runs: none without --full; with it, each one unless its own switch turns it off."""
+    flagship = (a.batch, a.res, a.ddim_steps) == (1, 512, 20)
+    return {"profile": a.full and not a.no_profile and rank == 0,
+            "cpu_baseline": a.full and not a.no_cpu_baseline and rank == 0 and world == 1,
+            "extras": a.full and not a.no_extras and rank == 0 and world == 1 and flagship}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10, help="timed stamp batches per rank")
@@ -473,17 +484,26 @@ def main():
     ap.add_argument("--batch", type=int, default=1, help="stamps per GPU per step (1 = configs[1], 8 = configs[2])")
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--ddim-steps", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (ceilings + a profiled stamp), CPU baseline, extra configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-config0", action="store_true", help="time BASELINE configs[0] in full on the host cores (CPU oracle) and exit")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra configurations (batch 8, 256 px, oracle pixel error)")
-    ap.add_argument("--dump-launches", default="", help="CSV with one line per profiled kernel launch")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the ceilings and the profiled stamp (roofline)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra configurations (batch 8, 256 px, oracle pixel error)")
+    ap.add_argument("--dump-launches", default="", help="with --full: CSV with one line per profiled kernel launch")
     ap.add_argument("--detail", default="", help="side file for the per-kernel tables (default gpurun_out/bench_detail.json)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="write what the last timed step returned (the u8 RGB patches, as float32) to DIR/patches.npy, at most 64 MB")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if (a.dump_launches or a.detail) and (not a.full or a.no_profile):
+        ap.error("--dump-launches and --detail are written by the profiled stamp: they need --full, without --no-profile")
+    return a
+
+
+def main():
+    a = parse_args()
     if a.cpu_config0:
         print(json.dumps(cpu_config0()))
         return
@@ -523,8 +543,10 @@ def main():
     # every launch program) before the other ranks start, so they find a complete tune table and never tune themselves.
     if world > 1 and rank != 0:
         D.barrier()
-    want_extras = not a.no_extras and rank == 0 and world == 1 and (a.batch, a.res, a.ddim_steps) == (1, 512, 20)
-    model = MI355ConditionalInpainter(a.res, device=local, weights=sd, max_batch=max(a.batch, 16 if want_extras else 8))
+    legs = full_legs(a, rank, world)
+    # the flagship engine has room for the extras' 16-stamp batch with or without --full: both kinds of run time the same engine
+    room16 = not a.no_extras and rank == 0 and world == 1 and (a.batch, a.res, a.ddim_steps) == (1, 512, 20)
+    model = MI355ConditionalInpainter(a.res, device=local, weights=sd, max_batch=max(a.batch, 16 if room16 else 8))
     model.set_conditioning(cond, uncond, brush)  # replicated on every rank
     canvas, lat, eps = canvas.to(dev), lat.to(dev), eps.to(dev)
     model._stamp(canvas, settings, composite=True, latents=lat, vae_eps=eps, output_u8=True)
@@ -532,7 +554,7 @@ def main():
     if world > 1 and rank == 0:
         D.barrier()
     gatherer = D.PatchGatherer(n_total, (a.res, a.res, 3), torch.uint8, dev, rank, world) if distributed else None
-    peak_tf, peak_gbs = measured_peaks() if rank == 0 else (None, None)
+    peak_tf, peak_gbs = measured_peaks() if legs["profile"] else (None, None)
 
     def one_step():
         out = model._stamp(canvas, settings, composite=True, latents=lat, vae_eps=eps, output_u8=True)
@@ -561,7 +583,7 @@ def main():
     info = model.stamp_info()
 
     roof = detail = None
-    if not a.no_profile and rank == 0:
+    if legs["profile"]:
         # one more pass of the same stamp with every launch bracketed by HIP events on its stream
         model.profile(True)
         model._stamp(canvas, settings, composite=True, latents=lat, vae_eps=eps, output_u8=True)
@@ -574,11 +596,11 @@ def main():
         model.profile(False)
         roof, detail = roofline_record(rows, classes, a.batch, a.res, a.ddim_steps, elapsed / a.steps, peak_tf, peak_gbs)
     cpu = None
-    if not a.no_cpu_baseline and rank == 0 and world == 1:
+    if legs["cpu_baseline"]:
         cpu = cpu_baseline(a.res, a.ddim_steps, sd, "bounded sample, not a full stamp")
 
     extras = None
-    if want_extras:
+    if legs["extras"]:
         extras = extra_measurements(model, sd)
 
     if rank == 0:

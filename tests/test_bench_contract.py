@@ -156,6 +156,37 @@ def test_plain_multi_gpu_command_starts_its_own_ranks():
     assert src.index("launch_ranks(a, sys.argv[1:])") < src.index("D.init_from_env(")
 
 
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest():
+    """`bench.py --gpus 1 --steps N --warmup W` runs no leg beyond the headline; `--full` runs every one, each still switched off by its
+    own --no-... option, on rank 0 (the CPU legs only without further ranks, the extras only for the flagship shape).  The ceilings
+    (measured_peaks) belong to the roofline leg.  Options that only the profiled stamp serves are refused without it."""
+    import pytest
+    bench = _bench()
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "somewhere"])
+    assert plain.full is False and not any(bench.full_legs(plain, 0, 1).values())
+    # the old switches alone turn nothing on
+    assert not any(bench.full_legs(bench.parse_args(["--no-cpu-baseline"]), 0, 1).values())
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.full_legs(full, 0, 1) == {"profile": True, "cpu_baseline": True, "extras": True}
+    assert bench.full_legs(full, 1, 2) == {"profile": False, "cpu_baseline": False, "extras": False}
+    assert bench.full_legs(full, 0, 2) == {"profile": True, "cpu_baseline": False, "extras": False}
+    assert bench.full_legs(bench.parse_args(["--full", "--res", "256"]), 0, 1) == {"profile": True, "cpu_baseline": True, "extras": False}
+    for switch, leg in (("--no-profile", "profile"), ("--no-cpu-baseline", "cpu_baseline"), ("--no-extras", "extras")):
+        legs = bench.full_legs(bench.parse_args(["--full", switch]), 0, 1)
+        assert legs.pop(leg) is False and all(legs.values()), switch
+    for argv in (["--dump-launches", "x.csv"], ["--detail", "x.json"], ["--full", "--no-profile", "--dump-launches", "x.csv"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse_args(argv)
+        assert e.value.code == 2, argv
+    assert bench.parse_args(["--full", "--dump-launches", "x.csv"]).dump_launches == "x.csv"
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    main_src = src[src.index("def main():"):]
+    assert 'measured_peaks() if legs["profile"] else' in main_src
+    for call in ("model.profile(True)", "cpu_baseline(a.res", "extra_measurements(model"):
+        guard = main_src[:main_src.index(call)].rstrip().splitlines()
+        assert any(ln.strip().startswith('if legs["') for ln in guard[-3:]), call
+
+
 def test_dump_outputs_writes_float32_within_the_budget_and_samples_the_same_way_every_time(tmp_path):
     """--dump-outputs: the last timed step's patches as DIR/<name>.npy in float32; a tensor larger than the budget becomes a fixed,
     seeded sample (whole stamps first, then the same values of each kept stamp), so two runs write identical files."""

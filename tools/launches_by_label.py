@@ -1,4 +1,4 @@
-"""bench.py --dump-launches CSV (one line per profiled launch: kind, us, tflops, algo_GBps, label) -> one line per label:
+"""bench.py --full --dump-launches CSV (one line per profiled launch: kind, us, tflops, algo_GBps, label) -> one line per label:
 kind, label, launches, total_ms, avg_us, tflops_last, algo_GBps_last.   python tools/launches_by_label.py in.csv out.csv"""
 import csv, sys
 from collections import OrderedDict

@@ -1,13 +1,14 @@
 # Round-4 profile refresh, one gpurun call (run from the repo root on the GPU box).  Order matters: the PMC traffic summary is
 # collected first and copied to profiles/ so that the bench lines of the same call can carry it (bench.py reports it only when its
 # kernel-source hash matches the running build).  Everything lands in gpurun_out/r04_*; copy what should be judged into profiles/.
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"  # the bench.py --full lines of this script, their logs and launch tables
 export DTP_ROUND=r04
 bash tools/pmc_unet.sh
 cp gpurun_out/r04_pmc_unet_traffic.json profiles/r04_pmc_unet_traffic.json
 export DTP_TUNE_CACHE=/tmp/tc.txt
-timeout 1200 python bench.py > gpurun_out/r04_b1.log 2>gpurun_out/r04_b1.err
-timeout 600 python bench.py --batch 8 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > gpurun_out/r04_b8.log 2>gpurun_out/r04_b8.err
-timeout 600 python bench.py --res 256 --no-cpu-baseline --no-extras > gpurun_out/r04_256.log 2>gpurun_out/r04_256.err
+timeout 1200 python bench.py --full > $OUT/r04_b1.log 2>$OUT/r04_b1.err
+timeout 600 python bench.py --full --batch 8 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/r04_b8.log 2>$OUT/r04_b8.err
+timeout 600 python bench.py --full --res 256 --no-cpu-baseline --no-extras > $OUT/r04_256.log 2>$OUT/r04_256.err
 DTP_BENCH_BACKEND=gloo DTP_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-profile > gpurun_out/r04_gpus2_same_device.log 2>gpurun_out/r04_gpus2_same_device.err
 DTP_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-profile > gpurun_out/r04_rccl_one_rank.log 2>gpurun_out/r04_rccl_one_rank.err
 timeout 600 python bench.py --cpu-config0 > gpurun_out/r04_cpu_config0.json 2>gpurun_out/r04_cpu_config0.err

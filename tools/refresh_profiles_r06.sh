@@ -1,6 +1,7 @@
 # Round-6 profile refresh, one gpurun call (run from the repo root on the GPU box).  Order matters: the PMC summaries (HBM traffic,
 # MFMA-busy) are collected first and copied to profiles/ so that the bench lines of the same call can carry them (bench.py reports them
 # only when their kernel-source hash matches the running build).  Everything lands in gpurun_out/r06_*; copy what should be judged into profiles/.
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"  # the bench.py --full lines of this script, their logs and launch tables
 export DTP_ROUND=r06
 export DTP_TUNE_CACHE=/tmp/tc.txt
 cp diffusiontexturepainting_amd/tune_seed.txt /tmp/tc.txt   # shapes the shipped table lacks are tuned here and appended: the result is the next shipped table
@@ -16,9 +17,9 @@ bash tools/pmc_unet.sh
 cp gpurun_out/r06_pmc_unet_traffic.json profiles/r06_pmc_unet_traffic.json
 bash tools/pmc_unet_mfma.sh > gpurun_out/r06_pmc_unet_mfma.log 2>&1
 cp gpurun_out/r06_pmc_unet_mfma.json profiles/r06_pmc_unet_mfma.json
-timeout 1500 python bench.py --dump-launches gpurun_out/r06_launches_b1.csv > gpurun_out/r06_b1.log 2>gpurun_out/r06_b1.err
-timeout 600 python bench.py --batch 8 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > gpurun_out/r06_b8.log 2>gpurun_out/r06_b8.err
-timeout 600 python bench.py --res 256 --no-cpu-baseline --no-extras > gpurun_out/r06_256.log 2>gpurun_out/r06_256.err
+timeout 1500 python bench.py --full --dump-launches $OUT/r06_launches_b1.csv > $OUT/r06_b1.log 2>$OUT/r06_b1.err
+timeout 600 python bench.py --full --batch 8 --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/r06_b8.log 2>$OUT/r06_b8.err
+timeout 600 python bench.py --full --res 256 --no-cpu-baseline --no-extras > $OUT/r06_256.log 2>$OUT/r06_256.err
 DTP_BENCH_BACKEND=gloo DTP_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-profile > gpurun_out/r06_gpus2_same_device.log 2>gpurun_out/r06_gpus2_same_device.err
 DTP_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-profile > gpurun_out/r06_rccl_one_rank.log 2>gpurun_out/r06_rccl_one_rank.err
 if [ -z "$DTP_REFRESH_SKIP_ORACLE" ]; then  # (the two long CPU-oracle legs: configs[0] in full on the host, configs[1] + configs[2] at full size -- the GPU suite below repeats the latter)
@@ -46,4 +47,4 @@ fi
 ( time DTP_FULLSIZE_JSON=gpurun_out/r06_fullsize_parity.json timeout 1500 python -m pytest tests -q -m gpu --durations=15 -x ) > gpurun_out/r06_gpu_suite.log 2>&1
 tail -3 gpurun_out/r06_gpu_suite.log
 cp /tmp/tc.txt gpurun_out/r06_tune_cache.txt
-for f in b1 b8 256; do grep "^{" gpurun_out/r06_$f.log | tail -1 | grep -o "\"ms_per_step\": [0-9.]*"; done
+for f in b1 b8 256; do grep "^{" $OUT/r06_$f.log | tail -1 | grep -o "\"ms_per_step\": [0-9.]*"; done
