@@ -274,6 +274,9 @@ SYMBOLS = {
                                     _vp]),
     "dtp_view_tint": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.POINTER(C.c_uint8 * 3), _i, _vp]),
     "dtp_op_mesh_backproject_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
+    "dtp_mesh_stroke_occluded": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(MeshStamp), _i, C.POINTER(Settings), C.POINTER(MeshStrokeOpts), _vp, _i, _vp, _i,
+                                      _f, _vp]),
+    "dtp_op_mesh_backproject_occluded": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _f, _f, _vp]),
     "dtp_journal_create": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dtp_journal_destroy": (_i, [_vp]),
     "dtp_journal_begin": (_i, [_vp, _vp]),

@@ -11,6 +11,8 @@
 // vertices, faces and UVs alone, so that it runs on a stream of its own beside a stroke.
 // Masked strokes (dtp_mesh_stroke_masked): a face set keeps the faces whose bit is 0 out of the valid list; nothing else
 // of a stamp changes.  The lasso that makes a set and the tint that shows one are select.hip's.
+// Occluded strokes (dtp_mesh_stroke_occluded): a second instantiation of the backprojection kernel leaves out the taps
+// that show a face in front of the texel's own; the render, the valid list, the bleed pass and the journal hook do not know of it.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stdio.h>
@@ -228,12 +230,15 @@ __global__ __launch_bounds__(256) void mesh_valid_kernel(const FaceRec* __restri
 // clamped value, A = mask * (face_idx != -1) -- is sampled there, and where the sampled A is > 0 all four bytes of the texel become
 // (unsigned char)(min(v, 1) * 255.0f); dec == null (Erase): 0 x 4 instead.  Other texels are neither read nor written.  `finished`: dec
 // holds the clamped 0..1 values already (dtp_op_mesh_backproject on what dtp_stamp returned).
-__global__ __launch_bounds__(256) void mesh_backproject_kernel(const FaceRec* __restrict__ rec, const int4* __restrict__ val,
-                                                               const MeshState* st, int F, const float* __restrict__ uvs,
-                                                               const float* __restrict__ dec, int finished,
-                                                               const unsigned char* __restrict__ mask,
-                                                               const int* __restrict__ face_idx, int R, unsigned int* __restrict__ tex,
-                                                               int H, int W) {
+//   OCC (the occluded instantiation): a tap whose pixel shows another face g that lies in front of the texel's face f by
+// more than `tol` at that pixel's centre -- both planes by weights_at from rec[g] and rec[f], which is re-read here after the loop, not
+// staged -- is rejected; a texel with a rejected tap blends the remaining taps and divides by the sum of their weights.  A texel without
+// one runs the arithmetic of the plain instantiation, operation for operation; OCC false compiles to the kernel this was before.
+template <bool OCC>
+__device__ __forceinline__ void backproject_texel(const FaceRec* __restrict__ rec, const int4* __restrict__ val, const MeshState* st, int F,
+                                                  const float* __restrict__ uvs, const float* __restrict__ dec, int finished,
+                                                  const unsigned char* __restrict__ mask, const int* __restrict__ face_idx, int R,
+                                                  unsigned int* __restrict__ tex, int H, int W, float tol) {
   __shared__ int s_n, s_face[CHUNK], s_X[CHUNK][3], s_Y[CHUNK][3];
   __shared__ float s_p[CHUNK][3], s_q[CHUNK][3];
   const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
@@ -275,7 +280,35 @@ __global__ __launch_bounds__(256) void mesh_backproject_kernel(const FaceRec* __
   const Taps tp = taps(p * (float)R - 0.5f, (1.0f - q) * (float)R - 0.5f, R, R);
   const int i00 = tp.y0 * R + tp.x0, i01 = tp.y0 * R + tp.x1, i10 = tp.y1 * R + tp.x0, i11 = tp.y1 * R + tp.x1;
   auto alpha = [&](int i) { return (mask[i] != 0 && face_idx[i] != -1) ? 1.0f : 0.0f; };
-  const float a = blend(tp, alpha(i00), alpha(i01), alpha(i10), alpha(i11));
+  Taps tq = tp;        // the taps a rejection left (OCC); tp itself otherwise
+  bool renorm = false;  // a tap was rejected: every blend is divided by S, the sum of the weights left
+  float S = 1.0f;
+  if constexpr (OCC) {
+    const int ti[4] = {i00, i01, i10, i11}, tx[4] = {tp.x0, tp.x1, tp.x0, tp.x1}, ty[4] = {tp.y0, tp.y0, tp.y1, tp.y1};
+    bool rej[4] = {false, false, false, false};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int g = face_idx[ti[k]];
+      if (g == best || (unsigned int)g >= (unsigned int)F) continue;  // (-1, and any value that is no face of the mesh: never an index)
+      const FaceRec &rg = rec[g], &rf = rec[best];
+      const int cx = 256 * tx[k] + 128, cy = 256 * ty[k] + 128;
+      float wg[3], wf[3];
+      if (!weights_at(rg.X, rg.Y, cx, cy, wg) || !weights_at(rf.X, rf.Y, cx, cy, wf)) continue;  // (both won a pixel: never)
+      const float zg = interp(wg, rg.z[0], rg.z[1], rg.z[2]), zf = interp(wf, rf.z[0], rf.z[1], rf.z[2]);
+      rej[k] = (zg - zf) > tol;  // (a NaN does not reject)
+    }
+    if (rej[0] || rej[1] || rej[2] || rej[3]) {
+      renorm = true;
+      if (rej[0]) tq.w00 = 0.f;
+      if (rej[1]) tq.w01 = 0.f;
+      if (rej[2]) tq.w10 = 0.f;
+      if (rej[3]) tq.w11 = 0.f;
+      S = ((tq.w00 + tq.w01) + tq.w10) + tq.w11;
+      if (!(S > 0.f)) return;
+    }
+  }
+  float a = blend(tq, alpha(i00), alpha(i01), alpha(i10), alpha(i11));
+  if (OCC && renorm) a = a / S;
   if (!(a > 0.f)) return;
   unsigned int texel = 0u;
   if (dec) {
@@ -283,11 +316,31 @@ __global__ __launch_bounds__(256) void mesh_backproject_kernel(const FaceRec* __
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       const float d00 = dec[(size_t)i00 * 4 + ch], d01 = dec[(size_t)i01 * 4 + ch], d10 = dec[(size_t)i10 * 4 + ch], d11 = dec[(size_t)i11 * 4 + ch];
-      const float v = finished ? blend(tp, d00, d01, d10, d11) : blend(tp, finish_value(d00), finish_value(d01), finish_value(d10), finish_value(d11));
+      float v = finished ? blend(tq, d00, d01, d10, d11) : blend(tq, finish_value(d00), finish_value(d01), finish_value(d10), finish_value(d11));
+      if (OCC && renorm) v = v / S;
       texel |= (unsigned int)(unsigned char)(fminf(v, 1.0f) * 255.0f) << (8 * ch);
     }
   }
   tex[(size_t)row * W + col] = texel;
+}
+
+__global__ __launch_bounds__(256) void mesh_backproject_kernel(const FaceRec* __restrict__ rec, const int4* __restrict__ val,
+                                                               const MeshState* st, int F, const float* __restrict__ uvs,
+                                                               const float* __restrict__ dec, int finished,
+                                                               const unsigned char* __restrict__ mask,
+                                                               const int* __restrict__ face_idx, int R, unsigned int* __restrict__ tex,
+                                                               int H, int W) {
+  backproject_texel<false>(rec, val, st, F, uvs, dec, finished, mask, face_idx, R, tex, H, W, 0.f);
+}
+
+// the same with the occlusion test (dtp_mesh_stroke_occluded): tol, in camera units, is the host's occlude 2 fov / R
+__global__ __launch_bounds__(256) void mesh_backproject_occluded_kernel(const FaceRec* __restrict__ rec, const int4* __restrict__ val,
+                                                                        const MeshState* st, int F, const float* __restrict__ uvs,
+                                                                        const float* __restrict__ dec, int finished,
+                                                                        const unsigned char* __restrict__ mask,
+                                                                        const int* __restrict__ face_idx, int R,
+                                                                        unsigned int* __restrict__ tex, int H, int W, float tol) {
+  backproject_texel<true>(rec, val, st, F, uvs, dec, finished, mask, face_idx, R, tex, H, W, tol);
 }
 
 // the Erase stamp's default mask: the analytic disc of radius R / 2 - 2 around the window's centre (the shape of the Kit app's circle_mask,
@@ -682,15 +735,25 @@ int enqueue_render(Mesh* m, const float cam[12], float fov, int flip, const unsi
 
 // valid (-> journal) -> backproject of the window rendered last on this mesh; dec null: erase.  journal (or null): the one whose open record
 // guards this texture; the tiles of the valid faces' texel box grown by `grow` (the bleed that follows) are saved before they are written.
-// sel (or null): the face set outside which no face is valid.
+// sel (or null): the face set outside which no face is valid.  tol (or null: the plain kernel): the occlusion test's tolerance.
 int enqueue_backproject(Mesh* m, const float* dec, int finished, const unsigned char* mask, const int* face_idx, int R, unsigned char* texture, int H, int W,
-                        hipStream_t s, Journal* journal = nullptr, int grow = 0, const unsigned int* sel = nullptr) {
+                        hipStream_t s, Journal* journal = nullptr, int grow = 0, const unsigned int* sel = nullptr, const float* tol = nullptr) {
   hipLaunchKernelGGL(mesh_valid_kernel, dim3(std::min((m->F + 255) / 256, 1024)), dim3(256), 0, s, m->rec, m->owned, m->win, m->uvs, m->F, H,
                      W, m->val, m->state, sel);
   if (journal) RC(journal_save_box(journal, m->state->bb, grow, s));
-  hipLaunchKernelGGL(mesh_backproject_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->rec, m->val, m->state, m->F, m->uvs, dec,
-                     finished, mask, face_idx, R, (unsigned int*)texture, H, W);
+  if (tol)
+    hipLaunchKernelGGL(mesh_backproject_occluded_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->rec, m->val, m->state, m->F, m->uvs,
+                       dec, finished, mask, face_idx, R, (unsigned int*)texture, H, W, *tol);
+  else
+    hipLaunchKernelGGL(mesh_backproject_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, m->rec, m->val, m->state, m->F, m->uvs, dec,
+                       finished, mask, face_idx, R, (unsigned int*)texture, H, W);
   return launch_ok();
+}
+
+// the occlusion test's setting (or null: off), before anything else of a call is looked at
+int check_occlude(const char* who, const float* occlude) {
+  if (occlude && !mesh_occlude_ok(*occlude)) { dtp_set_error("%s: occlude=%g (a finite value >= 0, in stamp pixels)", who, (double)*occlude); return DTP_ERR_ARG; }
+  return DTP_OK;
 }
 
 int check_bleed(const char* who, int bleed) {
@@ -750,6 +813,7 @@ int disc_mask(Ctx* c, hipStream_t s, const unsigned char** out) {
 struct MeshStep {
   float cam[12];
   bool skip = false;  // the window misses the mesh's bounding box
+  float tol = 0.f;    // the occlusion test's tolerance at this stamp's fov (dtp_mesh_stroke_occluded)
   dtp_settings st;
   uint64_t seed = 0;
   int slot = 0;
@@ -763,15 +827,17 @@ int check_face_mask(const char* who, const Mesh* m, const uint32_t* face_mask, i
   return DTP_OK;
 }
 
-// dtp_mesh_stroke (bleed 0), dtp_mesh_stroke_bleed and dtp_mesh_stroke_masked (face_mask or null): `who` names the entry point in a refusal
+// dtp_mesh_stroke (bleed 0), dtp_mesh_stroke_bleed, dtp_mesh_stroke_masked (face_mask or null) and dtp_mesh_stroke_occluded (occlude or
+// null: the plain backprojection): `who` names the entry point in a refusal
 int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
                 const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, dtp_stream s_, const uint32_t* face_mask = nullptr,
-                int mask_words = 0) {
+                int mask_words = 0, const float* occlude = nullptr) {
   Ctx* c = (Ctx*)ctx;
   Mesh* m = (Mesh*)mesh;
   hipStream_t s = (hipStream_t)s_;
   // ---- every check, before anything is enqueued
   RC(check_bleed(who, bleed));
+  RC(check_occlude(who, occlude));
   if (!c || !m || !texture || !stamps || !st || !o) {
     dtp_set_error("%s: NULL argument (ctx, mesh, texture, stamps, st and o are required)", who);
     return DTP_ERR_ARG;
@@ -798,6 +864,10 @@ int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture,
     }
     RC(check_over(who, i, t.mode, o->over_y, o->over_x, R));
     RC(make_camera(who, i, t.pos, t.normal, t.prev, t.fov, q.cam));
+    if (occlude && !mesh_occlude_tol(*occlude, t.fov, R, &q.tol)) {
+      dtp_set_error("%s: stamp %d: the tolerance of occlude=%g at fov=%g does not fit fp32", who, i, (double)*occlude, (double)t.fov);
+      return DTP_ERR_ARG;
+    }
     q.skip = !box_meets_window(m, q.cam, t.fov, R);
     if (t.mode == DTP_STROKE_ERASE) { any_erase = any_erase || !q.skip; continue; }  // (runs no stamp: its slot and seed are unused)
     if (t.slot < 0 || t.slot >= DTP_MAX_SLOTS) { dtp_set_error("%s: slot %d of stamp %d outside 0..%d", who, t.slot, i, DTP_MAX_SLOTS - 1); return DTP_ERR_ARG; }
@@ -832,14 +902,16 @@ int mesh_stroke(const char* who, dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture,
     const dtp_mesh_stamp& t = stamps[i];
     MeshStep& q = steps[i];
     if (q.skip) continue;
+    const bool occluded = occlude != nullptr;
+    const float tol = q.tol;  // (by value: the paste hook below keeps its own copy)
     RC(enqueue_render(m, q.cam, t.fov, o->flip_normals != 0, texture, H, W, R, t.mode, o->over_y, o->over_x, c->canvas32, face_idx, s));
     if (t.mode == DTP_STROKE_ERASE) {
-      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s, journal, bleed, sel));
+      RC(enqueue_backproject(m, nullptr, 0, disc, face_idx, R, texture, H, W, s, journal, bleed, sel, occluded ? &tol : nullptr));
       if (bleed) RC(enqueue_bleed(m, texture, H, W, bleed, nullptr, s));
       continue;
     }
     q.plan.paste = [=](const float* dec, int, int, hipStream_t q_s) {
-      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s, journal, bleed, sel));
+      RC(enqueue_backproject(m, dec, 0, square, face_idx, R, texture, H, W, q_s, journal, bleed, sel, occluded ? &tol : nullptr));
       return bleed ? enqueue_bleed(m, texture, H, W, bleed, nullptr, q_s) : DTP_OK;
     };
     RC(stamp_enqueue(c, q.plan, s));
@@ -959,6 +1031,12 @@ int dtp_mesh_stroke_masked(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H
   return mesh_stroke("dtp_mesh_stroke_masked", ctx, mesh, texture, H, W, stamps, n, st, o, paste_mask, bleed, s, face_mask, mask_words);
 }
 
+int dtp_mesh_stroke_occluded(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n, const dtp_settings* st,
+                             const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed, const uint32_t* face_mask, int mask_words, float occlude,
+                             dtp_stream s) {
+  return mesh_stroke("dtp_mesh_stroke_occluded", ctx, mesh, texture, H, W, stamps, n, st, o, paste_mask, bleed, s, face_mask, mask_words, &occlude);
+}
+
 int dtp_mesh_bleed_offsets(int radius, int* count, signed char* di_dj) {
   if (!count) { dtp_set_error("dtp_mesh_bleed_offsets: count is NULL"); return DTP_ERR_ARG; }
   if (radius < 1 || radius > MESH_MAX_BLEED) { dtp_set_error("dtp_mesh_bleed_offsets: radius=%d outside 1..%d", radius, MESH_MAX_BLEED); return DTP_ERR_ARG; }
@@ -1076,6 +1154,26 @@ int dtp_op_mesh_backproject_masked(dtp_mesh* mesh, const float* dec, int dec_fin
   RC(check_texture(who, texture, H, W));
   HIP_CHECK(hipSetDevice(m->ctx->device));
   return enqueue_backproject(m, dec, dec_finished != 0, mask, face_idx, R, texture, H, W, (hipStream_t)s, nullptr, 0, (const unsigned int*)face_mask);
+}
+
+int dtp_op_mesh_backproject_occluded(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R, uint8_t* texture,
+                                     int H, int W, const uint32_t* face_mask, int mask_words, float fov, float occlude, dtp_stream s) {
+  const char* who = "dtp_op_mesh_backproject_occluded";
+  Mesh* m = (Mesh*)mesh;
+  RC(check_occlude(who, &occlude));
+  if (R < 1 || R > MAX_WIN) { dtp_set_error("%s: R=%d (1..%d)", who, R, MAX_WIN); return DTP_ERR_ARG; }
+  if (!(fov > 0.f) || !std::isfinite(fov)) { dtp_set_error("%s: fov=%g (a finite value > 0)", who, (double)fov); return DTP_ERR_ARG; }
+  float tol;
+  if (!mesh_occlude_tol(occlude, fov, R, &tol)) {
+    dtp_set_error("%s: the tolerance of occlude=%g at fov=%g does not fit fp32", who, (double)occlude, (double)fov);
+    return DTP_ERR_ARG;
+  }
+  if (!m || !mask || !face_idx || !texture) { dtp_set_error("%s: NULL argument (dec alone may be NULL: erase; face_mask: no set)", who); return DTP_ERR_ARG; }
+  if (!mesh_alive(m)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
+  RC(check_face_mask(who, m, face_mask, mask_words));
+  RC(check_texture(who, texture, H, W));
+  HIP_CHECK(hipSetDevice(m->ctx->device));
+  return enqueue_backproject(m, dec, dec_finished != 0, mask, face_idx, R, texture, H, W, (hipStream_t)s, nullptr, 0, (const unsigned int*)face_mask, &tol);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // The host-only arithmetic of the bleed pass of the mesh strokes (include/dtp.h: dtp_mesh_bleed_offsets, dtp_mesh_bleed; DESIGN.md
 // 3.21): the table of candidate offsets in the contract's order and the clipping of a caller's rectangle; and of picking (dtp_mesh_pick,
-// dtp_mesh_path_plan): the ray frame, the exponent of a ray's grid and the stamp spacing of a pointer path.  No device
+// dtp_mesh_path_plan): the ray frame, the exponent of a ray's grid and the stamp spacing of a pointer path; and of the
+// occlusion test (dtp_mesh_stroke_occluded): the check of the setting and the tolerance it becomes.  No device
 // call, so the stand-alone sanitizer programs (tools/mesh_host_check.cpp, tools/mesh_pick_host_check.cpp) drive it directly.
 #pragma once
 #include <math.h>
@@ -50,6 +51,19 @@ inline int mesh_clip_rect(const int* rect, int H, int W, int out[4]) {
   out[0] = std::max(rect[0], 0); out[1] = std::max(rect[1], 0);
   out[2] = std::min(rect[2], W - 1); out[3] = std::min(rect[3], H - 1);
   return out[0] > out[2] || out[1] > out[3] ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- the occlusion test of the backprojection
+// occlude: a tolerance in stamp pixels, finite and >= 0
+inline bool mesh_occlude_ok(float occlude) { return std::isfinite(occlude) && occlude >= 0.f; }
+// The depth, in camera units, of `occlude` pixel widths of an R x R window that spans 2 fov camera units: ((occlude 2) fov) / R in double
+// from the fp32 inputs, rounded to fp32 once.  false: it does not fit fp32 (*tol untouched).
+inline bool mesh_occlude_tol(float occlude, float fov, int R, float* tol) {
+#pragma clang fp contract(off)
+  const float t = (float)((((double)occlude * 2.0) * (double)fov) / (double)R);
+  if (!std::isfinite(t)) return false;
+  *tol = t;
+  return true;
 }
 
 // ---------------------------------------------------------------- picking

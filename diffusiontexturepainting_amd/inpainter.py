@@ -442,7 +442,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
 
     def paint_mesh_stroke(self, mesh, texture, positions, normals, prev_positions, fov, seeds=None, modes=None, slots=None,
                           flip_normals=False, margin=1, overpaint_margins=(10, 25), mask=None, sample_vae=True, strength=1.0, bleed=0,
-                          face_mask=None, **settings):
+                          face_mask=None, occlude=None, **settings):
         """Paint a stroke on a textured mesh without a host round trip per stamp: TexturePainterManager.stamp (manager.py:199-271) as one
         dtp_mesh_stroke call.  Per stamp, in order: an orthographic look-at camera from positions[i] + normals[i] at positions[i] with
         up = prev_positions[i] - positions[i] (mesh_camera), the render of `mesh` with `texture` (uint8 [H,W,4] on the model's device,
@@ -459,7 +459,14 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         contiguous.  A face whose bit is 0 is never backprojected, so the stroke paints the texels of the selected faces alone; the
         render still shows the whole mesh and the stamp is the stamp it would have been (dtp_mesh_stroke_masked).  The set is read on
         the device when the stroke runs: the stroke's stream first waits for self.view_stream, so select-then-paint needs no
-        synchronisation, and the tensor must stay unchanged until the stroke has run.  None: the call without the keyword."""
+        synchronisation, and the tensor must stay unchanged until the stroke has run.  None: the call without the keyword.
+        occlude: the per-texel occlusion test of the backprojection (dtp_mesh_stroke_occluded).  Without it a face the
+        window shows is backprojected whole, the part of it that lies behind another face included, and those texels receive the
+        pixels of the face in front.  With it a tap of the stamp image that shows a face more than `occlude` stamp pixels of depth in
+        front of the texel's own face is left out, and a texel all of whose taps are is not written.  True: 1.0, which the bumps of a
+        smooth surface pass untouched; a float >= 0: that tolerance; None or False: off, the call without the keyword.  It composes
+        with bleed, face_mask and an open journal record."""
+        occlude = _mesh.occlude_arg(occlude)
         if not self._slots:
             raise _lib.DtpError("no brush set: call set_brush() first")
         R = self._resolution
@@ -486,9 +493,14 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         if face_mask is not None:
             _mesh.faceset_check(face_mask, mesh.num_faces, self._device)
         self.stream.wait_stream(torch.cuda.current_stream(self._device))
-        if face_mask is not None:
-            if self._view_stream is not None:
-                self.stream.wait_stream(self._view_stream)  # a select_faces that is still writing the set
+        if face_mask is not None and self._view_stream is not None:
+            self.stream.wait_stream(self._view_stream)  # a select_faces that is still writing the set
+        if occlude is not None:
+            check(self._lib.dtp_mesh_stroke_occluded(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n,
+                                                     C.byref(st), C.byref(opts), ptr(mask), int(bleed), ptr(face_mask),
+                                                     0 if face_mask is None else face_mask.shape[0], C.c_float(occlude), self._s()),
+                  "dtp_mesh_stroke_occluded")
+        elif face_mask is not None:
             check(self._lib.dtp_mesh_stroke_masked(self._h, mesh.handle, ptr(texture), texture.shape[0], texture.shape[1], stamps, n,
                                                    C.byref(st), C.byref(opts), ptr(mask), int(bleed), ptr(face_mask), face_mask.shape[0],
                                                    self._s()), "dtp_mesh_stroke_masked")
@@ -527,7 +539,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         directions) -> mesh.plan_path(hits, radius / stamps_per_radius, state) -> paint_mesh_stroke with the planned stamps.  radius:
         the brush radius in world units; fov defaults to it.  state: None for a new path, or what the last call returned, so that a
         path can be painted as the pointer events arrive.  Every other keyword is paint_mesh_stroke's (seeds, modes -- one mode for the
-        whole path --, bleed, mask, face_mask, settings ...); a stamp whose camera is refused is refused by the stroke as always.  A path that
+        whole path --, bleed, mask, face_mask, occlude, settings ...); a stamp whose camera is refused is refused by the stroke as always.  A path that
         plans no stamp (all rays miss, or the pointer has not moved far enough) paints nothing.  -> (texture, state, stamps painted)."""
         hits = self.pick(mesh, origins, directions)
         positions, normals, prevs, state = _mesh.plan_path(hits, float(radius) / float(stamps_per_radius), state)

@@ -6,7 +6,8 @@ the host-only ray frame and the stamp spacing of a pointer path live here; the p
 pointer-to-paint call paint_mesh_path.  The view (DESIGN.md 3.24): the host-only perspective camera and the rays of its pixels live here;
 the frame itself is MI355ConditionalInpainter.render_view (ops.mesh_view at op level).  Face sets: the packing of a
 set of faces into int32 words and its checks live here; the lasso is MI355ConditionalInpainter.select_faces, the stroke that respects a
-set paint_mesh_stroke(face_mask=), the tint tint_selection."""
+set paint_mesh_stroke(face_mask=), the tint tint_selection.  The occlusion test of the backprojection: the reading of
+the `occlude` keyword lives here; the test itself is paint_mesh_stroke(occlude=) and ops.mesh_backproject(fov=, occlude=)."""
 import ctypes as C
 
 import torch
@@ -192,6 +193,25 @@ def faceset_check(sel, F, device, what="face_mask"):
     if not sel.is_contiguous():
         raise ValueError(f"{what} must be contiguous")
     return sel
+
+
+OCCLUDE_DEFAULT = 1.0  # stamp pixels: what occlude=True means
+
+
+def occlude_arg(occlude):
+    """The `occlude` keyword of paint_mesh_stroke and ops.mesh_backproject -> None (off: None or False) or the tolerance in stamp pixels as
+    a float (True: OCCLUDE_DEFAULT).  ValueError for a value that is negative, not finite or not fp32-sized, before anything is enqueued."""
+    if occlude is None or occlude is False:
+        return None
+    if occlude is True:
+        return OCCLUDE_DEFAULT
+    try:
+        value = float(occlude)
+    except (TypeError, ValueError):
+        raise ValueError(f"occlude must be None, a bool or a float >= 0 (a tolerance in stamp pixels), got {occlude!r}") from None
+    if not (0.0 <= value <= 3.4028234663852886e38):
+        raise ValueError(f"occlude must be a finite float >= 0 that fits fp32 (a tolerance in stamp pixels), got {occlude!r}")
+    return value
 
 
 def lasso_polygon(polygon):

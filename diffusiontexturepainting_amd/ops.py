@@ -612,15 +612,20 @@ def mesh_render(mesh, camera, fov, texture, R, flip_normals=False, mode=0, over_
     return canvas, face_idx
 
 
-def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None, face_mask=None):
+def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None, face_mask=None, fov=None, occlude=None):
     """dtp_op_mesh_backproject, the other half: through the faces the LAST mesh_render of `mesh` showed (face_idx: that render's), the
     stamp image is carried into texture u8 [H,W,4] in place where the sampled mask u8 [R,R] * (face_idx != -1) is > 0.  The stamp image
     is dec f32 [R,R,4] (the VAE decoder's working layout, values around -1..1), or `painted` f32 [3,R,R] / [1,3,R,R] in 0..1 (what
     generate_raw returns, used as it is); neither: erase.  face_mask: a face set (int32 [(F + 31) // 32] on the texture's device,
-    contiguous; dtp_op_mesh_backproject_masked): a face whose bit is 0 is not backprojected.  Returns texture."""
+    contiguous; dtp_op_mesh_backproject_masked): a face whose bit is 0 is not backprojected.  occlude: the per-texel occlusion test
+    (dtp_op_mesh_backproject_occluded; True: 1.0, a float >= 0: the tolerance in stamp pixels, None or False: off); it needs fov, the fov
+    of that render.  Returns texture."""
     lib = _lib.load()
+    from . import mesh as _mesh
+    occlude = _mesh.occlude_arg(occlude)
+    if occlude is not None and fov is None:
+        raise ValueError("occlude needs fov, the fov of the render whose face_idx this is")
     if face_mask is not None:
-        from . import mesh as _mesh
         _mesh.faceset_check(face_mask, mesh.num_faces, texture.device)
     finished = painted is not None
     if finished:
@@ -629,6 +634,12 @@ def mesh_backproject(mesh, dec, mask, face_idx, texture, painted=None, face_mask
         R = face_idx.shape[0]
         dec = torch.zeros(R, R, 4, dtype=torch.float32, device=texture.device)
         dec[..., :3] = painted.reshape(3, R, R).permute(1, 2, 0)
+    if occlude is not None:
+        check(lib.dtp_op_mesh_backproject_occluded(mesh.handle, ptr(dec), int(finished), ptr(mask), ptr(face_idx), face_idx.shape[0], ptr(texture),
+                                                   texture.shape[0], texture.shape[1], ptr(face_mask),
+                                                   0 if face_mask is None else face_mask.shape[0], C.c_float(float(fov)), C.c_float(occlude),
+                                                   _stream()), "mesh_backproject_occluded")
+        return texture
     if face_mask is not None:
         check(lib.dtp_op_mesh_backproject_masked(mesh.handle, ptr(dec), int(finished), ptr(mask), ptr(face_idx), face_idx.shape[0], ptr(texture),
                                                  texture.shape[0], texture.shape[1], ptr(face_mask), face_mask.shape[0], _stream()),

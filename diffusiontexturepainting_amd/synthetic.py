@@ -84,6 +84,20 @@ def make_quad():
     return v, f, ((v[:, :2] + 1) / 2)[f.long()].contiguous()
 
 
+def make_table_on_floor():
+    """A floor and a table top that hides part of it: the floor is the square [-1, 1]^2 in the plane z = 0, the top the
+    square [-0.4, 0.4]^2 in the plane z = 0.5, two faces each (floor: faces 0 and 1, top: 2 and 3), all normals towards +z.  The floor's
+    chart fills u in [0.02, 0.48], the top's u in [0.52, 0.98]; v in [0.02, 0.98] for both.  Seen from +z the middle of the floor, a
+    part of two large faces, lies behind the top.  -> vertices f32 [8, 3], faces i32 [4, 3], face_uvs f32 [4, 3, 2]."""
+    corners = [(-1.0, -1.0), (1.0, -1.0), (1.0, 1.0), (-1.0, 1.0)]
+    v = torch.tensor([[x, y, 0.0] for x, y in corners] + [[0.4 * x, 0.4 * y, 0.5] for x, y in corners])
+    f = torch.tensor([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7]], dtype=torch.int32)
+    s = (torch.tensor(corners) + 1) / 2  # the corner in its chart's unit square
+    chart = torch.cat([torch.stack([0.02 + 0.46 * s[:, 0], 0.02 + 0.96 * s[:, 1]], dim=1),
+                       torch.stack([0.52 + 0.46 * s[:, 0], 0.02 + 0.96 * s[:, 1]], dim=1)])
+    return v, f, chart[f.long()].contiguous()
+
+
 def make_height_field(nx=17, ny=13, seed=0, bump=0.35):
     """A bumpy height field over [-1, 1] x [-0.75, 0.75]: nx x ny vertices, 2 (nx - 1)(ny - 1) faces with normals towards +z, and a
     two-chart UV atlas: the faces left of the middle column fill u in [0.03, 0.47], the others u in [0.53, 0.97] MIRRORED (u falls as x

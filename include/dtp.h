@@ -28,7 +28,8 @@ extern "C" {
  * (dtp_journal_*, dtp_op_journal_tiles) and the view of a mesh (dtp_view_camera, dtp_view_rays, dtp_mesh_view, dtp_op_mesh_view) and the
  * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state)
  * and the view clipped at the near plane (dtp_mesh_view_clip, dtp_op_mesh_view_clip) and the anti-aliased view (dtp_mesh_view_aa,
- * dtp_op_mesh_view_aa) and the anisotropic view (dtp_mesh_view_aniso, dtp_op_mesh_view_aniso) are additions; nothing that existed at
+ * dtp_op_mesh_view_aa) and the anisotropic view (dtp_mesh_view_aniso, dtp_op_mesh_view_aniso) and the occlusion test of the
+ * backprojection (dtp_mesh_stroke_occluded, dtp_op_mesh_backproject_occluded) are additions; nothing that existed at
  * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -689,6 +690,44 @@ int dtp_mesh_stroke_masked(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H
 int dtp_view_tint(dtp_ctx* ctx, uint8_t* frame, const int* face_idx, int H, int W, const uint32_t* set, int words, int F,
                   const uint8_t color[3], int opacity, dtp_stream s);
 
+/* ---------------------------------------------------------------- occlusion in the backprojection
+ * The render of a stamp decides visibility per pixel, the backprojection per face: a valid face (front, not steep, the winner of at
+ * least one pixel) is backprojected whole, so a large face that is only partly visible -- a floor under a table, a wall behind a pillar
+ * -- receives the stamp on the texels that lie behind the other face as well, and the pixels it samples there show the occluder
+ * (DESIGN.md 3.32).  dtp_mesh_stroke_occluded tests every tap of every texel.  No depth buffer: the per-face records of the stamp's
+ * projection and its face_idx are on the device already.  fp32, one rounded operation at a time in the order written, no contraction;
+ * nothing is compared under a tolerance but the one the caller gives.
+ *
+ * occlude: a tolerance in stamp pixels, finite and >= 0.  On the host tol = ((occlude 2) fov) / R in double from the fp32 occlude and
+ * fov, rounded to fp32 once: the depth, in camera units, of `occlude` pixel widths of a window that spans 2 fov camera units over R pixels.
+ * Per texel the winner face f and the four taps of the stamp image are the backprojection's, unchanged.  For tap i at pixel (x_i, y_i) of
+ * the window, g = face_idx[y_i][x_i].  If g is a face of the mesh (0 <= g < F; -1 and any other value are skipped, never used as an
+ * index) and g != f: both faces' planes are evaluated at the tap's pixel centre c_i = (256 x_i + 128, 256 y_i + 128) with NO inside test --
+ * w_k = (float)E_k / (float)|A| from the same sign-normalised int64 edge functions of the face's snapped window triangle as the
+ * coverage's, z = (w0 z0 + w1 z1) + w2 z2 of the vertices' camera z -- giving z_g and z_f.  The tap is REJECTED iff (z_g - z_f) > tol: one
+ * fp32 subtraction, one comparison; a NaN compares false and does not reject.  Larger camera z is nearer: a rejected tap shows a face in
+ * front of f's plane by more than the tolerance.  (g won a pixel and f is valid, so it won one too: neither triangle has a zero
+ * area; a record that has one, at op level, does not reject.)  The tap's mask byte plays no part in the test.
+ * A texel none of whose taps is rejected is computed by the backprojection's arithmetic, operation for operation.  Otherwise the weight
+ * of every rejected tap becomes 0; S = ((w00' + w01') + w10') + w11'; if !(S > 0) the texel is not written; a = blend'(alpha_i) / S with
+ * alpha_i = (mask != 0 && face_idx != -1) as always and blend' the same expression over the weights left, and if !(a > 0) the texel is not
+ * written; each colour is blend'(d_i) / S, an fp32 division; the bytes are then formed as always, (unsigned char)(min(v, 1) * 255.0f).
+ * An ERASE stamp follows the same written / not written rule.  The weights are renormalised because a rejected tap has to leave the
+ * colour as well as the alpha; and the tolerance cannot be 0, because two faces that share an edge differ at a centre near that edge by
+ * the distance to the edge times the difference of their slopes: 1 pixel absorbs a slope difference of about 0.7 between neighbours.
+ *
+ * dtp_mesh_stroke_occluded: dtp_mesh_stroke_masked (face_mask NULL: dtp_mesh_stroke_bleed; bleed 0: dtp_mesh_stroke) whose every stamp,
+ * ERASE stamps included, runs the occluded instantiation of the backprojection kernel with the tol of that stamp's fov.  The render, the
+ * stamp, the valid list, the texel bounding box, the journal and the bleed pass are unchanged; a texel the test leaves unwritten inside
+ * the box is saved by an open journal record and restored like any other.  Refusals beyond that call's, DTP_ERR_ARG before anything is
+ * enqueued and with the texture untouched: an occlude that is negative or not finite (checked with `bleed`, before the handles are looked at, naming "occlude"), a stamp whose tol
+ * does not fit fp32 (naming the stamp).  The entry points above never run the test: their launches and bytes are what they were.
+ * Not here: a configurable steepness threshold or an angle falloff (the per-face record has no room for the normal), occluders that
+ * belong to another mesh, a count of rejected texels in dtp_last_stroke_info, any change to what the stamp itself sees. */
+int dtp_mesh_stroke_occluded(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H, int W, const dtp_mesh_stamp* stamps, int n,
+                             const dtp_settings* st, const dtp_mesh_stroke_opts* o, const uint8_t* paste_mask, int bleed,
+                             const uint32_t* face_mask, int mask_words, float occlude, dtp_stream s);
+
 /* ---------------------------------------------------------------- undo / redo journal of a texture
  * Taking a stroke back without the host.  The reference copies the whole texture to the host before every stroke, keeps
  * the last 10 copies and uploads one on Ctrl+Z (kit_app/.../python/ui/brush.py:52-77,131-137; redo is a TODO there).  A journal keeps, on
@@ -1157,6 +1196,12 @@ int dtp_op_mesh_backproject(dtp_mesh* mesh, const float* dec, int dec_finished, 
  * a face whose bit is 0 is not valid.  face_mask NULL: dtp_op_mesh_backproject exactly. */
 int dtp_op_mesh_backproject_masked(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R,
                                    uint8_t* texture, int H, int W, const uint32_t* face_mask, int mask_words, dtp_stream s);
+/* dtp_op_mesh_backproject_masked with the occlusion test (the contract: see "occlusion in the backprojection"): fov the fov of the render
+ * whose records and face_idx these are, occlude the tolerance in stamp pixels; tol = ((occlude 2) fov) / R.  DTP_ERR_ARG, before the mesh is
+ * looked at: occlude negative or not finite, R outside 1..4096, fov not finite or not > 0, a tol that does not fit fp32. */
+int dtp_op_mesh_backproject_occluded(dtp_mesh* mesh, const float* dec, int dec_finished, const uint8_t* mask, const int* face_idx, int R,
+                                     uint8_t* texture, int H, int W, const uint32_t* face_mask, int mask_words, float fov, float occlude,
+                                     dtp_stream s);
 /* dtp_mesh_pick with the records left on the device (the contract: see "picking on a mesh"): rays host dtp_ray[n], out device
  * dtp_mesh_hit[n] (52 bytes each).  The same checks; it enqueues on `s` and waits for `s`, because the frames travel through the mesh's
  * pinned buffer. */

@@ -1,7 +1,7 @@
 // Stand-alone host check of csrc/mesh.hip for a sanitizer build: the part of it that needs no device -- dtp_mesh_camera, the argument
 // checks of dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_stroke and the two ops, all of which return before their first HIP call, and
-// the host side of the bleed pass (the offset table, the rectangle clipping of csrc/mesh_host.h, the argument checks) -- driven from its
-// own main().  The rest of the library is replaced by the stubs below; none of them may be reached.  Build and run:
+// the host side of the bleed pass (the offset table, the rectangle clipping of csrc/mesh_host.h, the argument checks), and of the
+// occlusion test (the setting, the rounding of its tolerance, the refusals of the two occluded entry points) -- driven from its own main().  The rest of the library is replaced by the stubs below; none of them may be reached.  Build and run:
 //   hipcc --offload-arch=gfx950 -std=c++17 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -I include -I diffusiontexturepainting_amd/csrc diffusiontexturepainting_amd/csrc/mesh.hip tools/mesh_host_check.cpp -o mesh_host_check
 //   ./mesh_host_check
@@ -155,6 +155,43 @@ int main() {
   EXPECT(dtp_mesh_stroke_bleed(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, -1, nullptr) == DTP_ERR_ARG);
   EXPECT(dtp_mesh_stroke_bleed(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 2, nullptr) == DTP_ERR_ARG &&
          strstr(g_err, "NULL"));
+
+  // ---- the occlusion test: the setting, the tolerance it becomes, and the refusals that come before everything else
+  EXPECT(mesh_occlude_ok(0.f) && mesh_occlude_ok(1.f) && mesh_occlude_ok(3.4e38f) && mesh_occlude_ok(-0.f));
+  EXPECT(!mesh_occlude_ok(-1e-30f) && !mesh_occlude_ok(NAN) && !mesh_occlude_ok(INFINITY) && !mesh_occlude_ok(-INFINITY));
+  float tol = -7.f;
+  EXPECT(mesh_occlude_tol(1.f, 1.f, 32, &tol) && tol == 0.0625f);
+  EXPECT(mesh_occlude_tol(0.f, 3e38f, 1, &tol) && tol == 0.f);
+  EXPECT(mesh_occlude_tol(0.25f, 0.45f, 64, &tol) && tol == (float)((0.25 * 2.0) * (double)0.45f / 64.0));
+  // rounded ONCE: the product in double, not in float (0.1f * 2 * 0.3f / 7 rounds differently when each step is rounded to fp32)
+  EXPECT(mesh_occlude_tol(0.1f, 0.3f, 7, &tol) && tol == (float)((((double)0.1f * 2.0) * (double)0.3f) / 7.0));
+  EXPECT(mesh_occlude_tol(3e38f, 3e38f, 4096, &tol) == false && mesh_occlude_tol(3.4e38f, 1.f, 1, &tol) == false);  // (2 x 3.4e38: above fp32)
+  EXPECT(tol == (float)((((double)0.1f * 2.0) * (double)0.3f) / 7.0));  // a refusal leaves *tol alone
+  EXPECT(mesh_occlude_tol(3.4e38f, 1.f, 2, &tol) && tol == 3.4e38f);
+  EXPECT(mesh_occlude_tol(1e-30f, 1e-30f, 4096, &tol) && tol == 0.f);  // an underflow is a tolerance of 0, not a refusal
+  EXPECT(dtp_mesh_stroke_occluded(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 0, nullptr, 0, -1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "dtp_mesh_stroke_occluded: occlude=-1"));
+  EXPECT(dtp_mesh_stroke_occluded(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 0, nullptr, 0, NAN, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "occlude=nan"));
+  EXPECT(dtp_mesh_stroke_occluded(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 0, nullptr, 0, INFINITY, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "occlude=inf"));
+  EXPECT(dtp_mesh_stroke_occluded(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 17, nullptr, 0, 1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "dtp_mesh_stroke_occluded: bleed=17"));
+  EXPECT(dtp_mesh_stroke_occluded(nullptr, (dtp_mesh*)not_a_mesh, tex, 1, 1, &stamp, 1, &st, &o, nullptr, 2, nullptr, 0, 1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "NULL"));
+  EXPECT(dtp_op_mesh_backproject_occluded((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr, 0, 1.f, -0.5f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "occlude=-0.5"));
+  EXPECT(dtp_op_mesh_backproject_occluded((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr, 0, 0.f, 1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "fov=0"));
+  EXPECT(dtp_op_mesh_backproject_occluded((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr, 0, NAN, 1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "fov=nan"));
+  EXPECT(dtp_op_mesh_backproject_occluded((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 4097, tex, 1, 1, nullptr, 0, 1.f, 1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "R=4097"));
+  EXPECT(dtp_op_mesh_backproject_occluded((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr, 0, 3e38f, 3e38f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "does not fit fp32"));
+  EXPECT(dtp_op_mesh_backproject_occluded(nullptr, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr, 0, 1.f, 1.f, nullptr) == DTP_ERR_ARG && strstr(g_err, "NULL"));
+  EXPECT(dtp_op_mesh_backproject_occluded((dtp_mesh*)not_a_mesh, nullptr, 0, mask, face_idx, 1, tex, 1, 1, nullptr, 0, 1.f, 1.f, nullptr) == DTP_ERR_ARG &&
+         strstr(g_err, "not a live mesh"));
   printf("mesh_host_check: %d checks passed\n", g_checks);
   return 0;
 }

@@ -3,7 +3,9 @@
 2048^2 texture over the height field refined to about 100 k faces (`paint_mesh_stroke`), against `paint_stroke(max_group=1)` with the
 same number of stamps and the same seeds, in one process, alternating, warmed up, three repeats each.  Wall time from the call to the
 end of the device work, the host time of the call itself, and the two mesh kernels' groups on their own between events (render =
-reset + project + render; backproject = valid + backproject).  Prints one JSON line."""
+reset + project + render; backproject = valid + backproject).  A third arm, `paint_mesh_stroke(occlude=1.0)`, runs beside the plain one and is compared with it
+alone: the per-stamp difference next to the spread of the repeats of both arms, and the occluded backprojection between events on the
+same renders.  Prints one JSON line; --out also writes it to a file."""
 import argparse
 import json
 import os
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--ddim-steps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--grid", type=int, default=225, help="vertices per side of the height field (225: 100 352 faces)")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     from diffusiontexturepainting_amd import ops, synthetic, weights as W
     from diffusiontexturepainting_amd.inpainter import MI355ConditionalInpainter
@@ -49,6 +52,7 @@ def main():
 
     arms = {
         "paint_mesh_stroke": lambda tex: m.paint_mesh_stroke(mesh, tex, positions, normals, prevs, fov, seeds=seeds, **st),
+        "paint_mesh_stroke_occluded": lambda tex: m.paint_mesh_stroke(mesh, tex, positions, normals, prevs, fov, seeds=seeds, occlude=1.0, **st),
         "paint_stroke_serial": lambda tex: m.paint_stroke(tex, windows, seeds=seeds, max_group=1, margin=1, **st),
     }
     for fn in arms.values():  # build, capture, warm
@@ -89,6 +93,23 @@ def main():
             if rep == 1:
                 shown.append(int(face_idx.unique().numel()) - int((face_idx < 0).any()))
                 written.append(int((tex != before).any(dim=-1).sum()))
+    # valid + backproject, plain against occluded, on the same render's records into a texture each; the second of a pair is the slower
+    # whatever it is, so the arms take turns to go first
+    pair_ms, differ = {False: [], True: []}, []
+    for rep in range(2):
+        pair_ms = {False: [], True: []}
+        for i, cam in enumerate(cams):
+            _, face_idx = ops.mesh_render(mesh, cam, fov, tex0, R)
+            texs = {False: tex0.clone(), True: tex0.clone()}
+            for occluded in ((False, True) if (i + rep) % 2 == 0 else (True, False)):
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+                ops.mesh_backproject(mesh, dec, mask, face_idx, texs[occluded], fov=fov, occlude=1.0 if occluded else None)
+                ev[1].record()
+                torch.cuda.synchronize()
+                pair_ms[occluded].append(ev[0].elapsed_time(ev[1]))
+            if rep == 1:
+                differ.append(int((texs[False] != texs[True]).any(dim=-1).sum()))
     out = dict(res=R, texture=T, faces=int(faces.shape[0]), stamps=16, ddim_steps=a.ddim_steps, repeats=a.repeats)
     for name in arms:
         med = statistics.median(wall[name])
@@ -100,7 +121,21 @@ def main():
     out["kernels_alone"] = dict(render_ms_median=round(statistics.median(render_ms), 3), render_ms_max=round(max(render_ms), 3),
                                 backproject_ms_median=round(statistics.median(back_ms), 3), backproject_ms_max=round(max(back_ms), 3),
                                 faces_shown_median=int(statistics.median(shown)), texels_written_median=int(statistics.median(written)))
-    print(json.dumps(out))
+    plain, occl = wall["paint_mesh_stroke"], wall["paint_mesh_stroke_occluded"]
+    d = (statistics.median(occl) - statistics.median(plain)) / 16
+    out["occlude"] = dict(occlude=1.0, per_stamp_difference_ms_against_the_plain_arm=round(d, 3),
+                          per_stamp_difference_percent_of_a_stamp=round(100 * d / out["paint_mesh_stroke"]["per_stamp_ms"], 2),
+                          spread_of_the_repeats_ms_per_stamp=dict(plain=round((max(plain) - min(plain)) / 16, 3),
+                                                                  occluded=round((max(occl) - min(occl)) / 16, 3)),
+                          backproject_ms_median_with_the_arms_taking_turns=dict(plain=round(statistics.median(pair_ms[False]), 3),
+                                                                                occluded=round(statistics.median(pair_ms[True]), 3)),
+                          backproject_ms_max_with_the_arms_taking_turns=dict(plain=round(max(pair_ms[False]), 3), occluded=round(max(pair_ms[True]), 3)),
+                          texels_that_differ_from_the_plain_backprojection_median=int(statistics.median(differ)))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
