@@ -187,15 +187,7 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const FaceRec* __restr
     if (!blank) {
       const float* uv = uvs + (size_t)6 * best;
       const float u = interp(bw, uv[0], uv[2], uv[4]), v = interp(bw, uv[1], uv[3], uv[5]);
-      const Taps tp = taps(u * (float)W - 0.5f, (1.0f - v) * (float)H - 0.5f, H, W);
-      const unsigned int t00 = tex[(size_t)tp.y0 * W + tp.x0], t01 = tex[(size_t)tp.y0 * W + tp.x1];
-      const unsigned int t10 = tex[(size_t)tp.y1 * W + tp.x0], t11 = tex[(size_t)tp.y1 * W + tp.x1];
-#pragma unroll
-      for (int ch = 0; ch < 4; ++ch) {
-        const int sh = 8 * ch;
-        out[ch] = blend(tp, (float)((t00 >> sh) & 0xffu) / 255.0f, (float)((t01 >> sh) & 0xffu) / 255.0f,
-                        (float)((t10 >> sh) & 0xffu) / 255.0f, (float)((t11 >> sh) & 0xffu) / 255.0f);
-      }
+      sample_bilinear(tex, H, W, u, v, out);
     }
   }
 #pragma unroll

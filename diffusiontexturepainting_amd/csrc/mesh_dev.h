@@ -68,6 +68,19 @@ __device__ __forceinline__ Taps taps(float x, float y, int Hs, int Ws) {
 __device__ __forceinline__ float blend(const Taps& t, float v00, float v01, float v10, float v11) {
   return ((v00 * t.w00 + v01 * t.w01) + v10 * t.w10) + v11 * t.w11;
 }
+// the bilinear sample of an h x w RGBA8 image (a texture, or a level of its pyramid) at (u, v): the four taps of grid_sample, byte / 255
+// per channel
+__device__ __forceinline__ void sample_bilinear(const unsigned int* __restrict__ tex, int h, int w, float u, float v, float tc[4]) {
+  const Taps tp = taps(u * (float)w - 0.5f, (1.0f - v) * (float)h - 0.5f, h, w);
+  const unsigned int t00 = tex[(size_t)tp.y0 * w + tp.x0], t01 = tex[(size_t)tp.y0 * w + tp.x1];
+  const unsigned int t10 = tex[(size_t)tp.y1 * w + tp.x0], t11 = tex[(size_t)tp.y1 * w + tp.x1];
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) {
+    const int s8 = 8 * ch;
+    tc[ch] = blend(tp, (float)((t00 >> s8) & 0xffu) / 255.0f, (float)((t01 >> s8) & 0xffu) / 255.0f,
+                   (float)((t10 >> s8) & 0xffu) / 255.0f, (float)((t11 >> s8) & 0xffu) / 255.0f);
+  }
+}
 
 // the range [lo, hi] of pixel (texel) indices 0 .. n - 1 whose centres 256 i + 128 lie in [a, b]; empty: lo > hi
 __device__ __forceinline__ void centre_range(int a, int b, int n, int& lo, int& hi) {

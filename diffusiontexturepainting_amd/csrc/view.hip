@@ -8,15 +8,15 @@
 // segment alone -- plus the short list of faces too large to bin.  No capacity to choose, no overflow, no read-back.  The kernels read
 // the mesh's vertices, faces and UVs and write buffers of their own: nothing a stroke or a pick in flight uses.  Plain HIP: vector loads,
 // stores and atomics only.  dtp_mesh_view_mips is the same frame with a trilinear sample from the texture's mip pyramid
-// (mips.hip): the raster kernel is a template on the filter, and its unfiltered instantiation is dtp_mesh_view's code.  dtp_mesh_view_clip
-//  also draws the faces that CROSS the near plane, in homogeneous form: per face the cross products of its camera-space
-// vertices, per pixel their edge functions against the pixel's ray, which give the same q_k and d the rest of the raster kernel consumes.
-// It is a second template parameter; the instantiations without it are the code they were.  dtp_mesh_view_aa draws the
-// same frames with s x s samples per pixel: project, scan and fill run for the frame of s H x s W, and a raster kernel of its own
-// (view_raster_aa_kernel) keeps a winner per sample in registers and sums the samples' bytes in LDS: the larger frame is never stored.
-// dtp_mesh_view_aniso is a third value of the filter parameter of both raster kernels: the two footprint vectors are
-// kept apart, the level comes from the shorter one, and up to 16 trilinear taps along the longer one are averaged in a rolled loop.
-// The instantiations with filter 0 and 1 are the code they were.
+// (mips.hip): the raster kernel is a template on the filter.  dtp_mesh_view_clip also draws the faces that CROSS the
+// near plane, in homogeneous form: per face the cross products of its camera-space vertices, per pixel their edge functions against the
+// pixel's ray (cross_q), which give the same q_k and d the rest of the raster kernel consumes.  It is a second template parameter.
+// dtp_mesh_view_aa draws the same frames with s x s samples per pixel: project, scan and fill run for the frame of
+// s H x s W, and a raster kernel of its own (view_raster_aa_kernel) keeps a winner per sample in registers and sums the samples' bytes
+// in LDS: the larger frame is never stored.  dtp_mesh_view_aniso is a third value of the filter parameter of both
+// raster kernels: the two footprint vectors are kept apart, the level comes from the shorter one, and up to 16 trilinear taps along the
+// longer one are averaged in a rolled loop.  Both raster kernels shade their winner through view_shade, and a face across the near
+// plane is weighted through cross_q everywhere but in the plain kernel's face loop, which keeps its own text for a measured reason.
 #pragma clang fp contract(off)
 #include <math.h>
 #include <stddef.h>
@@ -88,6 +88,14 @@ __device__ __forceinline__ int bin_key(int e, int bx0, int bx1, int by0, int by1
   return (bx <= bx1 && by <= by1) ? by * nbx + bx : -1;
 }
 
+// the z of the unit normal of the camera-space triangle c, correctly rounded (a zero area: 0 / 0)
+__device__ __forceinline__ float unit_normal_z(const float c[3][3]) {
+  const float e1x = c[1][0] - c[0][0], e1y = c[1][1] - c[0][1], e1z = c[1][2] - c[0][2];
+  const float e2x = c[2][0] - c[0][0], e2y = c[2][1] - c[0][1], e2z = c[2][2] - c[0][2];
+  const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+  return nz / sqrtf((nx * nx + ny * ny) + nz * nz);
+}
+
 // One thread per face: camera space, the unit normal's z, the perspective division, the snapped screen position; a face that is drawn
 // (in front of the near plane, not culled, with an area and a pixel centre in its box) is counted into its bins or appended to `large`.
 // clip: a face with vertices on both sides of the near plane is drawn too: its record is the homogeneous form, its pixel range the box
@@ -126,10 +134,7 @@ __global__ __launch_bounds__(256) void view_project_kernel(const float* __restri
     int x0 = 0, x1 = W - 1, y0 = 0, y1 = H - 1;
     if (isfinite(D) && D != 0.f && (front || !cull) && (view_clip_box(c, cam.fx, cam.fy, cam.near, H, W, x0, x1, y0, y1) || !binned)) {
       if (!binned) { x0 = 0; x1 = W - 1; y0 = 0; y1 = H - 1; }
-      const float e1x = c[1][0] - c[0][0], e1y = c[1][1] - c[0][1], e1z = c[1][2] - c[0][2];
-      const float e2x = c[2][0] - c[0][0], e2y = c[2][1] - c[0][1], e2z = c[2][2] - c[0][2];
-      const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-      r.nzu = nz / sqrtf((nx * nx + ny * ny) + nz * nz);
+      r.nzu = unit_normal_z(c);
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         r.X[k] = __float_as_int(D < 0.f ? -n[0][k] : n[0][k]);
@@ -142,10 +147,7 @@ __global__ __launch_bounds__(256) void view_project_kernel(const float* __restri
     }
   }
   if (draw) {
-    const float e1x = c[1][0] - c[0][0], e1y = c[1][1] - c[0][1], e1z = c[1][2] - c[0][2];
-    const float e2x = c[2][0] - c[0][0], e2y = c[2][1] - c[0][1], e2z = c[2][2] - c[0][2];
-    const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
-    r.nzu = nz / sqrtf((nx * nx + ny * ny) + nz * nz);  // correctly rounded (a zero area: 0 / 0)
+    r.nzu = unit_normal_z(c);
     const float wx = 128.0f * (float)W, wy = 128.0f * (float)H;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -207,27 +209,30 @@ __global__ __launch_bounds__(256) void view_fill_kernel(const ViewRec* __restric
   }
 }
 
-// the bilinear sample of an h x w level at (u, v): the four taps of grid_sample, byte / 255 per channel
-__device__ __forceinline__ void view_sample(const unsigned int* __restrict__ tex, int h, int w, float u, float v, float tc[4]) {
-  const Taps tp = taps(u * (float)w - 0.5f, (1.0f - v) * (float)h - 0.5f, h, w);
-  const unsigned int t00 = tex[(size_t)tp.y0 * w + tp.x0], t01 = tex[(size_t)tp.y0 * w + tp.x1];
-  const unsigned int t10 = tex[(size_t)tp.y1 * w + tp.x0], t11 = tex[(size_t)tp.y1 * w + tp.x1];
-#pragma unroll
-  for (int ch = 0; ch < 4; ++ch) {
-    const int s8 = 8 * ch;
-    tc[ch] = blend(tp, (float)((t00 >> s8) & 0xffu) / 255.0f, (float)((t01 >> s8) & 0xffu) / 255.0f,
-                   (float)((t10 >> s8) & 0xffu) / 255.0f, (float)((t11 >> s8) & 0xffu) / 255.0f);
-  }
+// A face across the near plane (VF_CROSS) against the ray (gx, gy).  Its ten words -- X, Y: the float bits of n_0, n_1; iw: n_2; inv: the
+// bits of 1 / |D| -- come from a record or from a staged slot as they are, and this is the one place that unpacks them.
+// -> E_k = (n_k,x gx + n_k,y gy) - n_k,z; qk = E_k / |D|
+__device__ __forceinline__ float cross_edge(const int X[3], const int Y[3], const float iw[3], int inv, int k, float gx, float gy, float& qk) {
+  const float nx = k == 0 ? __int_as_float(X[0]) : k == 1 ? __int_as_float(Y[0]) : iw[0];
+  const float ny = k == 0 ? __int_as_float(X[1]) : k == 1 ? __int_as_float(Y[1]) : iw[1];
+  const float nz = k == 0 ? __int_as_float(X[2]) : k == 1 ? __int_as_float(Y[2]) : iw[2];
+  const float E = (nx * gx + ny * gy) - nz;
+  qk = E * __int_as_float(inv);
+  return E;
 }
+// the three q_k; -> the ray passes inside all three edges (E_k >= 0)
+__device__ __forceinline__ bool cross_q(const int X[3], const int Y[3], const float iw[3], int inv, float gx, float gy, float q[3]) {
+  const float E0 = cross_edge(X, Y, iw, inv, 0, gx, gy, q[0]), E1 = cross_edge(X, Y, iw, inv, 1, gx, gy, q[1]), E2 = cross_edge(X, Y, iw, inv, 2, gx, gy, q[2]);
+  return E0 >= 0.f && E1 >= 0.f && E2 >= 0.f;
+}
+// d = (q_0 + q_1) + q_2 of such a face lies on this side of its plane's horizon and not nearer than the near plane: the clip itself
+__device__ __forceinline__ bool cross_ahead(float d, float near) { return isfinite(d) && d > 0.f && 1.0f / d >= near; }
 
 // The texel of a covered centre: `best` won pixel (row, col) of an H x W frame, centre (px, py), ray (gx, gy) (CLIP alone), with q_k = bq
 // and their sum best_d.  The perspective-correct UV, the sample (FILTER 1: the footprint from the face at the two neighbouring centres,
 // the level walk, two levels blended; lod is written.  FILTER 2: the two footprint vectors kept apart, the level from the shorter one,
 // ntap trilinear taps along the longer one in a rolled loop, their plain mean; lod and ntap are written), the shade, the bytes with
-// alpha 255.  This is the text of view_raster_kernel's
-// own shading below, for the anti-aliased kernel alone: calling it from view_raster_kernel too changes that kernel's register
-// allocation and argument loads, and the instantiations of 3.24 - 3.27 are to stay the code they are.  A change to one is a change to
-// both; the anti-aliased tests compare the two byte for byte.
+// alpha 255.  Both raster kernels shade through it: a pixel of the plain frame and a sample of the anti-aliased one are the same code.
 template <int FILTER, int CLIP>
 __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ rec, const float* __restrict__ uvs, const unsigned int* __restrict__ tex,
                                                    int TH, int TW, int H, int W, ViewShade sh, ViewFilter<FILTER> fl,
@@ -237,22 +242,19 @@ __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ r
   const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
   float tc[4];
   if constexpr (FILTER == 0) {
-    view_sample(tex, TH, TW, u, v, tc);
+    sample_bilinear(tex, TH, TW, u, v, tc);
   } else {
     const ViewRec& r = rec[best];
     float qx[3], qy[3];
     bool crossing = false;
     if constexpr (CLIP != 0) crossing = (r.flags & VF_CROSS) != 0;
     if (crossing) {
-      if constexpr (CLIP != 0) {  // the same E_k, q_k at the two neighbouring centres, no inside test
-        const float gx1 = ray_x(col + 1, W, cl.fx), gy1 = ray_y(row + 1, H, cl.fy), inv = __int_as_float(r.pad[0]);
+      if constexpr (CLIP != 0) {  // the same q_k at the two neighbouring centres, no inside test
+        const float gx1 = ray_x(col + 1, W, cl.fx), gy1 = ray_y(row + 1, H, cl.fy);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          const float nx = k == 0 ? __int_as_float(r.X[0]) : k == 1 ? __int_as_float(r.Y[0]) : r.iw[0];
-          const float ny = k == 0 ? __int_as_float(r.X[1]) : k == 1 ? __int_as_float(r.Y[1]) : r.iw[1];
-          const float nz = k == 0 ? __int_as_float(r.X[2]) : k == 1 ? __int_as_float(r.Y[2]) : r.iw[2];
-          qx[k] = ((nx * gx1 + ny * gy) - nz) * inv;
-          qy[k] = ((nx * gx + ny * gy1) - nz) * inv;
+          cross_edge(r.X, r.Y, r.iw, r.pad[0], k, gx1, gy, qx[k]);
+          cross_edge(r.X, r.Y, r.iw, r.pad[0], k, gx, gy1, qy[k]);
         }
       }
     } else {
@@ -297,10 +299,10 @@ __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ r
     const float f = (l + 1 == fl.levels || rho2 <= p4) ? 0.f : ((rho2 / p4) - 1.0f) / 3.0f;
     lod = (float)l + f;
     if constexpr (FILTER == 1) {
-      view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
+      sample_bilinear(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
       if (f > 0.f) {
         float tn[4];
-        view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
+        sample_bilinear(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
       }
@@ -312,10 +314,10 @@ __device__ __forceinline__ unsigned int view_shade(const ViewRec* __restrict__ r
       for (int i = 0; i < n_taps; ++i) {
         const float o = (float)(2 * i + 1) / twice - 0.5f;
         const float ui = u + du * o, vi = v + dv * o;
-        view_sample(here, hl, wl, ui, vi, tc);
+        sample_bilinear(here, hl, wl, ui, vi, tc);
         if (f > 0.f) {
           float tn[4];
-          view_sample(fl.mips + next, mip_half(hl), mip_half(wl), ui, vi, tn);
+          sample_bilinear(fl.mips + next, mip_half(hl), mip_half(wl), ui, vi, tn);
 #pragma unroll
           for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
         }
@@ -353,7 +355,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
                                                           ViewFilter<FILTER> fl, ViewClip<CLIP> cl) {
   __shared__ int s_n, s_face[CHUNK], s_X[CHUNK][3], s_Y[CHUNK][3];
   __shared__ float s_iw[CHUNK][3];
-  __shared__ float s_inv[CLIP ? CHUNK : 1];  // (CLIP 0 never names it: no LDS)
+  __shared__ int s_inv[CLIP ? CHUNK : 1];  // (CLIP 0 never names it: no LDS)
   const int t = threadIdx.x, col0 = blockIdx.x * 16, row0 = blockIdx.y * 16;
   const int col = col0 + (t & 15), row = row0 + (t >> 4);
   const bool live = col < W && row < H;
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
           const int slot = atomicAdd(&s_n, 1);
           if constexpr (CLIP != 0) {
             s_face[slot] = (r.flags & VF_CROSS) ? f | CROSS_SLOT : f;
-            s_inv[slot] = __int_as_float(r.pad[0]);
+            s_inv[slot] = r.pad[0];
           } else {
             s_face[slot] = f;
           }
@@ -398,6 +400,8 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
           const int f = s_face[i];
           if (best < 0 || d > best_d || (d == best_d && f < best)) { best = f; best_d = d; bq[0] = q0; bq[1] = q1; bq[2] = q2; }
         } else {
+          // Own text, not cross_q / cross_ahead: through them height_field_225_far_trilinear_clip_on_samples_1 took 1.2010 ms against the
+          // parent's 1.1563 ms (spread 0.0445 ms; profiles/view_refactor_ab.json): three more moves in every round of this loop.
           float q0, q1, q2, d;
           int f = s_face[i];
           if (f & CROSS_SLOT) {
@@ -406,7 +410,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
             const float E1 = (__int_as_float(s_Y[i][0]) * gx + __int_as_float(s_Y[i][1]) * gy) - __int_as_float(s_Y[i][2]);
             const float E2 = (s_iw[i][0] * gx + s_iw[i][1] * gy) - s_iw[i][2];
             if (!(E0 >= 0.f && E1 >= 0.f && E2 >= 0.f)) continue;
-            const float inv = s_inv[i];
+            const float inv = __int_as_float(s_inv[i]);
             q0 = E0 * inv; q1 = E1 * inv; q2 = E2 * inv;
             d = (q0 + q1) + q2;
             if (!(isfinite(d) && d > 0.f && 1.0f / d >= cl.near)) continue;  // the plane's horizon, and the clip itself
@@ -427,108 +431,7 @@ __global__ __launch_bounds__(256) void view_raster_kernel(const ViewRec* __restr
   float dist = 0.f, lod = 0.f;
   [[maybe_unused]] int ntap = 0;
   if (best >= 0) {
-    const float* uv = uvs + (size_t)6 * best;
-    const float u = interp(bq, uv[0], uv[2], uv[4]) / best_d, v = interp(bq, uv[1], uv[3], uv[5]) / best_d;
-    float tc[4];
-    if constexpr (FILTER == 0) {
-      view_sample(tex, TH, TW, u, v, tc);
-    } else {
-      const ViewRec& r = rec[best];
-      float qx[3], qy[3];
-      bool crossing = false;
-      if constexpr (CLIP != 0) crossing = (r.flags & VF_CROSS) != 0;
-      if (crossing) {
-        if constexpr (CLIP != 0) {  // the same E_k, q_k at the two neighbouring centres, no inside test
-          const float gx1 = ray_x(col + 1, W, cl.fx), gy1 = ray_y(row + 1, H, cl.fy), inv = __int_as_float(r.pad[0]);
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const float nx = k == 0 ? __int_as_float(r.X[0]) : k == 1 ? __int_as_float(r.Y[0]) : r.iw[0];
-            const float ny = k == 0 ? __int_as_float(r.X[1]) : k == 1 ? __int_as_float(r.Y[1]) : r.iw[1];
-            const float nz = k == 0 ? __int_as_float(r.X[2]) : k == 1 ? __int_as_float(r.Y[2]) : r.iw[2];
-            qx[k] = ((nx * gx1 + ny * gy) - nz) * inv;
-            qy[k] = ((nx * gx + ny * gy1) - nz) * inv;
-          }
-        }
-      } else {
-        float wx[3], wy[3];
-        weights_at(r.X, r.Y, px + 256, py, wx);
-        weights_at(r.X, r.Y, px, py + 256, wy);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { qx[k] = wx[k] * r.iw[k]; qy[k] = wy[k] * r.iw[k]; }
-      }
-      const float dx = (qx[0] + qx[1]) + qx[2], dy = (qy[0] + qy[1]) + qy[2];
-      float rho2 = INFINITY;  // beyond the horizon, or a footprint that is not finite: the last level
-      [[maybe_unused]] float du = 0.f, dv = 0.f;  // FILTER 2: the longer axis of the footprint in UV, along which the taps lie
-      [[maybe_unused]] int n_taps = 1;
-      if (isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f) {
-        const float fw = (float)TW, fh = (float)TH;
-        if constexpr (FILTER == 1) {
-          const float ax = (interp(qx, uv[0], uv[2], uv[4]) / dx - u) * fw, ay = (interp(qx, uv[1], uv[3], uv[5]) / dx - v) * fh;
-          const float bx = (interp(qy, uv[0], uv[2], uv[4]) / dy - u) * fw, by = (interp(qy, uv[1], uv[3], uv[5]) / dy - v) * fh;
-          rho2 = fmaxf(ax * ax + ay * ay, bx * bx + by * by);
-          if (!isfinite(rho2)) rho2 = INFINITY;
-        } else {
-          const float dua = interp(qx, uv[0], uv[2], uv[4]) / dx - u, dva = interp(qx, uv[1], uv[3], uv[5]) / dx - v;
-          const float dub = interp(qy, uv[0], uv[2], uv[4]) / dy - u, dvb = interp(qy, uv[1], uv[3], uv[5]) / dy - v;
-          const float ax = dua * fw, ay = dva * fh, bx = dub * fw, by = dvb * fh;
-          const float la2 = ax * ax + ay * ay, lb2 = bx * bx + by * by;
-          if (isfinite(la2) && isfinite(lb2)) {
-            const float pmax2 = fmaxf(la2, lb2), pmin2 = fminf(la2, lb2), m = (float)(fl.max_aniso * fl.max_aniso);
-            du = la2 >= lb2 ? dua : dub; dv = la2 >= lb2 ? dva : dvb;
-            rho2 = fminf(pmax2, fmaxf(fmaxf(pmin2, 1.0f), pmax2 / m));  // the shorter axis; no finer than a texel, nor than max_aniso taps span
-            while (n_taps < fl.max_aniso && !(pmax2 <= (float)(n_taps * n_taps) * rho2)) ++n_taps;
-          }
-        }
-      }
-      // level l of hl x wl texels at `at` of the pyramid (l >= 1), level l + 1 at `next`; p4 = 4^l
-      int l = 0, hl = TH, wl = TW;
-      size_t at = 0, next = 0;
-      float p4 = 1.0f;
-      while (l + 1 < fl.levels && p4 * 4.0f <= rho2) {
-        at = next; hl = mip_half(hl); wl = mip_half(wl); next = at + (size_t)hl * wl;
-        p4 *= 4.0f; ++l;
-      }
-      const float f = (l + 1 == fl.levels || rho2 <= p4) ? 0.f : ((rho2 / p4) - 1.0f) / 3.0f;
-      lod = (float)l + f;
-      if constexpr (FILTER == 1) {
-        view_sample(l == 0 ? tex : fl.mips + at, hl, wl, u, v, tc);
-        if (f > 0.f) {
-          float tn[4];
-          view_sample(fl.mips + next, mip_half(hl), mip_half(wl), u, v, tn);
-#pragma unroll
-          for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
-        }
-      } else {  // n_taps trilinear samples of this l and f, spread along (du, dv) about (u, v); their plain average
-        const unsigned int* here = l == 0 ? tex : fl.mips + at;
-        const float twice = (float)(2 * n_taps);
-        float sum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int i = 0; i < n_taps; ++i) {
-          const float o = (float)(2 * i + 1) / twice - 0.5f;
-          const float ui = u + du * o, vi = v + dv * o;
-          view_sample(here, hl, wl, ui, vi, tc);
-          if (f > 0.f) {
-            float tn[4];
-            view_sample(fl.mips + next, mip_half(hl), mip_half(wl), ui, vi, tn);
-#pragma unroll
-            for (int ch = 0; ch < 4; ++ch) tc[ch] = tc[ch] + (tn[ch] - tc[ch]) * f;
-          }
-#pragma unroll
-          for (int ch = 0; ch < 4; ++ch) sum[ch] = sum[ch] + tc[ch];
-        }
-#pragma unroll
-        for (int ch = 0; ch < 4; ++ch) tc[ch] = sum[ch] / (float)n_taps;
-        ntap = n_taps;
-      }
-    }
-    const float s = sh.shade ? sh.ambient + (1.0f - sh.ambient) * fabsf(rec[best].nzu) : 1.0f;
-    const float rest = 1.0f - tc[3];
-    out = 0xff000000u;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const float cc = (tc[ch] * tc[3] + sh.unpainted[ch] * rest) * s;
-      out |= (unsigned int)(unsigned char)(fminf(cc, 1.0f) * 255.0f + 0.5f) << (8 * ch);
-    }
+    out = view_shade<FILTER, CLIP>(rec, uvs, tex, TH, TW, H, W, sh, fl, cl, best, bq, best_d, col, row, px, py, gx, gy, lod, ntap);
     dist = 1.0f / best_d;
   }
   image[pix] = out;
@@ -573,7 +476,7 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
   constexpr int CH = view_aa_chunk(S);
   __shared__ int s_n, s_cnt[N], s_face[CH], s_X[CH][3], s_Y[CH][3];
   __shared__ float s_iw[CH][3];
-  __shared__ float s_inv[CLIP ? CH : 1];
+  __shared__ int s_inv[CLIP ? CH : 1];
   __shared__ unsigned short s_list[N][CH];    // per sub-tile: the staged slots whose pixel range meets it
   __shared__ unsigned int s_sum[256][2];      // per output pixel: the sums of R | G << 16 and of B | A << 16 (at most 16 x 255 each)
   __shared__ int s_cov[256];                  // and the number of samples that a face covers
@@ -603,7 +506,7 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
           const int slot = atomicAdd(&s_n, 1);  // (below CH: at most one per staging thread)
           if constexpr (CLIP != 0) {
             s_face[slot] = (r.flags & VF_CROSS) ? f | CROSS_SLOT : f;
-            s_inv[slot] = __int_as_float(r.pad[0]);
+            s_inv[slot] = r.pad[0];
           } else {
             s_face[slot] = f;
           }
@@ -638,13 +541,10 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
         if constexpr (CLIP != 0) { crossing = (f & CROSS_SLOT) != 0; f &= ~CROSS_SLOT; }
         if (crossing) {
           if constexpr (CLIP != 0) {
-            const float E0 = (__int_as_float(s_X[i][0]) * gx + __int_as_float(s_X[i][1]) * gy) - __int_as_float(s_X[i][2]);
-            const float E1 = (__int_as_float(s_Y[i][0]) * gx + __int_as_float(s_Y[i][1]) * gy) - __int_as_float(s_Y[i][2]);
-            const float E2 = (s_iw[i][0] * gx + s_iw[i][1] * gy) - s_iw[i][2];
-            if (!(E0 >= 0.f && E1 >= 0.f && E2 >= 0.f)) continue;
-            const float inv = s_inv[i];
-            d = (E0 * inv + E1 * inv) + E2 * inv;
-            if (!(isfinite(d) && d > 0.f && 1.0f / d >= cl.near)) continue;  // the plane's horizon, and the clip itself
+            float q[3];
+            if (!cross_q(s_X[i], s_Y[i], s_iw[i], s_inv[i], gx, gy, q)) continue;
+            d = (q[0] + q[1]) + q[2];
+            if (!cross_ahead(d, cl.near)) continue;
           }
         } else {
           float w[3];
@@ -681,12 +581,7 @@ __global__ __launch_bounds__(view_aa_threads(S)) void view_raster_aa_kernel(cons
         gx = ray_x(col, FW, cl.fx); gy = ray_y(row, FH, cl.fy);
       }
       if (crossing) {
-        if constexpr (CLIP != 0) {
-          const float inv = __int_as_float(r.pad[0]);
-          q[0] = ((__int_as_float(r.X[0]) * gx + __int_as_float(r.X[1]) * gy) - __int_as_float(r.X[2])) * inv;
-          q[1] = ((__int_as_float(r.Y[0]) * gx + __int_as_float(r.Y[1]) * gy) - __int_as_float(r.Y[2])) * inv;
-          q[2] = ((r.iw[0] * gx + r.iw[1] * gy) - r.iw[2]) * inv;
-        }
+        if constexpr (CLIP != 0) cross_q(r.X, r.Y, r.iw, r.pad[0], gx, gy, q);
       } else {
         float w[3] = {0.f, 0.f, 0.f};
         weights_at(r.X, r.Y, px, py, w);
@@ -739,64 +634,95 @@ int view_reserve(const MeshGeom& g) {
   return DTP_OK;
 }
 
-// every check, then zero the counters -> project -> scan -> fill -> raster on s; nothing waits
-// filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null); 2 = up to max_aniso trilinear
-// taps along the footprint, with the maps of lod and of taps (or null); clip: the faces across the near plane are drawn too
-int view_run(const char* who, dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* o,
-             uint8_t* image, int* face_idx, float* depth, int binned, hipStream_t s, int filter = 0, const uint8_t* mips = nullptr, float* lod = nullptr,
-             int clip = 0, int samples = 0, uint8_t* coverage = nullptr, int max_aniso = 1, uint8_t* taps = nullptr) {
-  if (!mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
-  if (const char* why = view_check(texture, TH, TW, cam, H, W, o, image, face_idx, depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
-  if (samples)
-    if (const char* why = view_aa_check(samples, H, W)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
+// One view, as its entry point fills it in: the arguments every entry point has, then what only some have, with the values of a
+// dtp_mesh_view.  filter: 0 = one bilinear sample of level 0; 1 = trilinear from `mips`, with the map of lod (or null); 2 = up to max_aniso
+// trilinear taps along the footprint, with the maps of lod and of taps (or null); clip: the faces across the near plane are drawn too;
+// samples: 0 = the plain raster kernel, else the anti-aliased one with that many samples a side, and the map of coverage (or null)
+struct ViewCall {
+  const char* who; dtp_mesh* mesh; const uint8_t* texture; int TH, TW; const dtp_view_cam* cam; int H, W; const dtp_view_opts* o;
+  uint8_t* image; int* face_idx; float* depth; int binned; dtp_stream s;
+  int filter = 0; const uint8_t* mips = nullptr; float* lod = nullptr;
+  int clip = 0, samples = 0; uint8_t* coverage = nullptr;
+  int max_aniso = 1; uint8_t* taps = nullptr;
+};
+
+// what the _clip, _aa and _aniso entry points refuse of their own arguments before view_run sees them, in this order; `what`: which of them
+// the entry point has
+enum { OWN_FILTER = 1, OWN_CLIP = 2, OWN_SAMPLES = 4, OWN_ANISO = 8 };
+int view_refuse(const ViewCall& c, int what) {
+  const char* who = c.who;
+  if ((what & OWN_ANISO) && (c.max_aniso < 1 || c.max_aniso > VIEW_MAX_ANISO)) {
+    dtp_set_error("%s: max_aniso must lie in 1..%d", who, VIEW_MAX_ANISO);
+    return DTP_ERR_ARG;
+  }
+  if ((what & OWN_FILTER) && c.filter != 0 && c.filter != 1) { dtp_set_error("%s: filter is 0 (bilinear) or 1 (trilinear)", who); return DTP_ERR_ARG; }
+  if ((what & OWN_CLIP) && c.clip != 0 && c.clip != 1) { dtp_set_error("%s: clip is 0 or 1", who); return DTP_ERR_ARG; }
+  if ((what & OWN_FILTER) && !c.filter && (c.mips || c.lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
+  if ((what & OWN_SAMPLES) && c.samples != 1 && c.samples != 2 && c.samples != 4) {
+    dtp_set_error("%s: %s", who, view_aa_check(c.samples, 1, 1));
+    return DTP_ERR_ARG;
+  }
+  return DTP_OK;
+}
+
+// every check, then zero the counters -> project -> scan -> fill -> raster on the stream; nothing waits
+int view_run(const ViewCall& c) {
+  const char* who = c.who;
+  const int TH = c.TH, TW = c.TW, H = c.H, W = c.W;
+  const hipStream_t s = (hipStream_t)c.s;
+  if (!c.mesh) { dtp_set_error("%s: NULL argument (mesh, texture, cam, opts and image are required)", who); return DTP_ERR_ARG; }
+  if (const char* why = view_check(c.texture, TH, TW, c.cam, H, W, c.o, c.image, c.face_idx, c.depth)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
+  if (c.samples)
+    if (const char* why = view_aa_check(c.samples, H, W)) { dtp_set_error("%s: %s", who, why); return DTP_ERR_ARG; }
   dtp_mip_levels lay;
-  if (filter) {
+  if (c.filter) {
     (void)mip_layout(TH, TW, &lay);  // (the sides were checked above)
-    if (lay.levels > 1 && !mips) { dtp_set_error("%s: NULL argument (mips is required for a texture larger than 1 x 1)", who); return DTP_ERR_ARG; }
-    if (((uintptr_t)mips & 3) != 0 || ((uintptr_t)lod & 3) != 0) { dtp_set_error("%s: mips and lod must be 4-byte aligned", who); return DTP_ERR_ARG; }
+    if (lay.levels > 1 && !c.mips) { dtp_set_error("%s: NULL argument (mips is required for a texture larger than 1 x 1)", who); return DTP_ERR_ARG; }
+    if (((uintptr_t)c.mips & 3) != 0 || ((uintptr_t)c.lod & 3) != 0) { dtp_set_error("%s: mips and lod must be 4-byte aligned", who); return DTP_ERR_ARG; }
   }
   MeshGeom g;
-  if (!mesh_geom(mesh, &g)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
+  if (!mesh_geom(c.mesh, &g)) { dtp_set_error("%s: the mesh is not a live mesh (destroyed?)", who); return DTP_ERR_ARG; }
   HIP_CHECK(hipSetDevice(g.ctx->device));
   RC(view_reserve(g));
   const ViewBufs* b = (const ViewBufs*)*g.view;
+  const dtp_view_opts* o = c.o;
   ViewShade sh;
   sh.shade = o->shade; sh.ambient = o->ambient;
   for (int ch = 0; ch < 3; ++ch) sh.unpainted[ch] = (float)o->unpainted[ch] / 255.0f;
   sh.background = (unsigned int)o->background[0] | ((unsigned int)o->background[1] << 8) | ((unsigned int)o->background[2] << 16) |
                   ((unsigned int)o->background[3] << 24);
-  const int fine = samples ? samples : 1;  // project, scan and fill see the frame the samples are the pixels of
+  const int fine = c.samples ? c.samples : 1;  // project, scan and fill see the frame the samples are the pixels of
   const int nbx = view_bins_across(fine * W), blocks = (g.F + 255) / 256;
   HIP_CHECK(hipMemsetAsync(b->st, 0, offsetof(ViewState, offset), s));
-  hipLaunchKernelGGL(view_project_kernel, dim3(blocks), dim3(256), 0, s, g.verts, g.faces, g.F, *cam, fine * H, fine * W, o->cull, o->flip_normals,
-                     binned ? 1 : 0, nbx, b->rec, b->large, b->st, clip ? 1 : 0);
+  hipLaunchKernelGGL(view_project_kernel, dim3(blocks), dim3(256), 0, s, g.verts, g.faces, g.F, *c.cam, fine * H, fine * W, o->cull, o->flip_normals,
+                     c.binned ? 1 : 0, nbx, b->rec, b->large, b->st, c.clip ? 1 : 0);
   hipLaunchKernelGGL(view_scan_kernel, dim3(1), dim3(256), 0, s, b->st);
   hipLaunchKernelGGL(view_fill_kernel, dim3(blocks), dim3(256), 0, s, b->rec, g.F, nbx, b->items, b->st);
   const dim3 tiles((W + 15) / 16, (H + 15) / 16);
   ViewFilter<1> fl;
-  fl.mips = (const unsigned int*)mips; fl.lod = lod; fl.levels = filter ? lay.levels : 1;
+  fl.mips = (const unsigned int*)c.mips; fl.lod = c.lod; fl.levels = c.filter ? lay.levels : 1;
   ViewFilter<2> fa;
-  fa.mips = fl.mips; fa.lod = lod; fa.levels = fl.levels; fa.max_aniso = max_aniso; fa.taps = taps;
+  fa.mips = fl.mips; fa.lod = c.lod; fa.levels = fl.levels; fa.max_aniso = c.max_aniso; fa.taps = c.taps;
   ViewClip<1> cl;
-  cl.fx = cam->fx; cl.fy = cam->fy; cl.near = cam->near;
+  cl.fx = c.cam->fx; cl.fy = c.cam->fy; cl.near = c.cam->near;
 #define RASTER(FILTER, CLIP, fl, cl)                                                                                                   \
   hipLaunchKernelGGL((view_raster_kernel<FILTER, CLIP>), tiles, dim3(256), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs, \
-                     (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, fl, cl)
+                     (const unsigned int*)c.texture, TH, TW, H, W, sh, (unsigned int*)c.image, c.face_idx, c.depth, fl, cl)
 #define RASTER_AA(FILTER, CLIP, S, fl, cl)                                                                                                    \
   hipLaunchKernelGGL((view_raster_aa_kernel<FILTER, CLIP, S>), tiles, dim3(view_aa_threads(S)), 0, s, b->rec, b->items, b->large, b->st, g.F, nbx, g.uvs, \
-                     (const unsigned int*)texture, TH, TW, H, W, sh, (unsigned int*)image, face_idx, depth, coverage, fl, cl)
+                     (const unsigned int*)c.texture, TH, TW, H, W, sh, (unsigned int*)c.image, c.face_idx, c.depth, c.coverage, fl, cl)
 #define RASTER_S(FILTER, CLIP, fl, cl)                 \
   do {                                                 \
-    if (samples == 0) RASTER(FILTER, CLIP, fl, cl);    \
-    else if (samples == 1) RASTER_AA(FILTER, CLIP, 1, fl, cl); \
-    else if (samples == 2) RASTER_AA(FILTER, CLIP, 2, fl, cl); \
+    if (c.samples == 0) RASTER(FILTER, CLIP, fl, cl);  \
+    else if (c.samples == 1) RASTER_AA(FILTER, CLIP, 1, fl, cl); \
+    else if (c.samples == 2) RASTER_AA(FILTER, CLIP, 2, fl, cl); \
     else RASTER_AA(FILTER, CLIP, 4, fl, cl);           \
   } while (0)
-  if (filter == 2 && clip) RASTER_S(2, 1, fa, cl);
-  else if (filter == 2) RASTER_S(2, 0, fa, ViewClip<0>());
-  else if (filter && clip) RASTER_S(1, 1, fl, cl);
-  else if (filter) RASTER_S(1, 0, fl, ViewClip<0>());
-  else if (clip) RASTER_S(0, 1, ViewFilter<0>(), cl);
+  if (c.filter == 2 && c.clip) RASTER_S(2, 1, fa, cl);
+  else if (c.filter == 2) RASTER_S(2, 0, fa, ViewClip<0>());
+  else if (c.filter && c.clip) RASTER_S(1, 1, fl, cl);
+  else if (c.filter) RASTER_S(1, 0, fl, ViewClip<0>());
+  else if (c.clip) RASTER_S(0, 1, ViewFilter<0>(), cl);
   else RASTER_S(0, 0, ViewFilter<0>(), ViewClip<0>());
 #undef RASTER_S
 #undef RASTER_AA
@@ -835,17 +761,17 @@ int dtp_view_rays(const dtp_view_cam* cam, int H, int W, const float* pixels_xy,
 
 int dtp_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
                   uint8_t* image, int* face_idx, float* depth, dtp_stream s) {
-  return view_run("dtp_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, (hipStream_t)s);
+  return view_run(ViewCall{"dtp_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, s});
 }
 
 int dtp_mesh_view_mips(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                        const dtp_view_opts* opts, uint8_t* image, int* face_idx, float* depth, float* lod, dtp_stream s) {
-  return view_run("dtp_mesh_view_mips", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, (hipStream_t)s, 1, mips, lod);
+  return view_run(ViewCall{"dtp_mesh_view_mips", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, 1, s, 1, mips, lod});
 }
 
 int dtp_op_mesh_view(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const dtp_view_cam* cam, int H, int W, const dtp_view_opts* opts,
                      uint8_t* image, int* face_idx, float* depth, int binned, dtp_stream s) {
-  return view_run("dtp_op_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s);
+  return view_run(ViewCall{"dtp_op_mesh_view", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, s});
 }
 
 int dtp_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
@@ -855,10 +781,10 @@ int dtp_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, c
 
 int dtp_op_mesh_view_clip(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                           const dtp_view_opts* opts, int filter, uint8_t* image, int* face_idx, float* depth, float* lod, int binned, dtp_stream s) {
-  const char* who = binned == 1 ? "dtp_mesh_view_clip" : "dtp_op_mesh_view_clip";
-  if (filter != 0 && filter != 1) { dtp_set_error("%s: filter is 0 (bilinear) or 1 (trilinear)", who); return DTP_ERR_ARG; }
-  if (!filter && (mips || lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
-  return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, filter, mips, lod, 1);
+  const ViewCall c{binned == 1 ? "dtp_mesh_view_clip" : "dtp_op_mesh_view_clip", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, s,
+                   filter, mips, lod, 1};
+  RC(view_refuse(c, OWN_FILTER));
+  return view_run(c);
 }
 
 int dtp_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
@@ -870,12 +796,10 @@ int dtp_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, con
 int dtp_op_mesh_view_aa(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                         const dtp_view_opts* opts, int filter, int clip, int samples, uint8_t* image, int* face_idx, float* depth, float* lod,
                         uint8_t* coverage, int binned, dtp_stream s) {
-  const char* who = binned == 1 ? "dtp_mesh_view_aa" : "dtp_op_mesh_view_aa";
-  if (filter != 0 && filter != 1) { dtp_set_error("%s: filter is 0 (bilinear) or 1 (trilinear)", who); return DTP_ERR_ARG; }
-  if (clip != 0 && clip != 1) { dtp_set_error("%s: clip is 0 or 1", who); return DTP_ERR_ARG; }
-  if (!filter && (mips || lod)) { dtp_set_error("%s: mips and lod need filter 1", who); return DTP_ERR_ARG; }
-  if (samples != 1 && samples != 2 && samples != 4) { dtp_set_error("%s: %s", who, view_aa_check(samples, 1, 1)); return DTP_ERR_ARG; }
-  return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, filter, mips, lod, clip, samples, coverage);
+  const ViewCall c{binned == 1 ? "dtp_mesh_view_aa" : "dtp_op_mesh_view_aa", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, s,
+                   filter, mips, lod, clip, samples, coverage};
+  RC(view_refuse(c, OWN_FILTER | OWN_CLIP | OWN_SAMPLES));
+  return view_run(c);
 }
 
 int dtp_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
@@ -888,12 +812,11 @@ int dtp_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, 
 int dtp_op_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, const uint8_t* mips, const dtp_view_cam* cam, int H, int W,
                            const dtp_view_opts* opts, int clip, int samples, int max_aniso, uint8_t* image, int* face_idx, float* depth, float* lod,
                            uint8_t* taps, uint8_t* coverage, int binned, dtp_stream s) {
-  const char* who = binned == 1 ? "dtp_mesh_view_aniso" : "dtp_op_mesh_view_aniso";
-  if (max_aniso < 1 || max_aniso > VIEW_MAX_ANISO) { dtp_set_error("%s: max_aniso must lie in 1..%d", who, VIEW_MAX_ANISO); return DTP_ERR_ARG; }
-  if (clip != 0 && clip != 1) { dtp_set_error("%s: clip is 0 or 1", who); return DTP_ERR_ARG; }
-  if (samples != 1 && samples != 2 && samples != 4) { dtp_set_error("%s: %s", who, view_aa_check(samples, 1, 1)); return DTP_ERR_ARG; }
-  return view_run(who, mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, (hipStream_t)s, 2, mips, lod, clip,
-                  samples == 1 && !coverage ? 0 : samples, coverage, max_aniso, taps);
+  ViewCall c{binned == 1 ? "dtp_mesh_view_aniso" : "dtp_op_mesh_view_aniso", mesh, texture, TH, TW, cam, H, W, opts, image, face_idx, depth, binned, s,
+             2, mips, lod, clip, samples, coverage, max_aniso, taps};
+  RC(view_refuse(c, OWN_ANISO | OWN_CLIP | OWN_SAMPLES));
+  if (samples == 1 && !coverage) c.samples = 0;
+  return view_run(c);
 }
 
 }  // extern "C"

@@ -5,9 +5,10 @@ five repeats, medians with their spread, the device time between events with the
     floor of tests/view_aniso_ref.py), all at 1280 x 720: `anisotropy` 1 (the trilinear frame through dtp_mesh_view_mips /
     dtp_mesh_view_aa, as before), 2, 4, 8 and 16, each with samples 1 and 2, the arms alternating within a row; with each row the
     number of taps the frame took (mean, largest) and the frame's sha256;
-  - with --parent-lib: the bilinear and the trilinear frames of the same poses in fresh child processes bound in turn to a libdtp.so
-    of the parent commit ($DTP_LIB) and to this build's, alternating, before this process touches the GPU: one sha256 per frame, the
-    medians against the spread.
+  - with --parent-lib: the frames of the same poses that both builds draw -- bilinear, trilinear and anisotropy 16, each with clip_near
+    off and on and with samples 1 and 2 -- in fresh child processes bound in turn to a libdtp.so of the parent commit ($DTP_LIB) and to
+    this build's, alternating, before this process touches the GPU: one sha256 per frame, the medians against the spread;
+  - with --stroke as well: the 16-stamp bleed = 0 stroke of tools/mesh_pick_timing.py --child once per library: its texture's sha256.
 Prints one JSON line; --out writes it to a file as well (profiles/mesh_view_aniso_timing.json; no other tool's file)."""
 import argparse
 import hashlib
@@ -82,14 +83,17 @@ def aniso_frames(m, tex, repeats):
 
 
 def old_frames(m, tex, repeats):
-    """The paths this build does not change: the bilinear and the trilinear frame of every scene -> {scene_filter: median, min, max, sha256}."""
+    """The paths both builds have: every scene with each filter (bilinear, trilinear, anisotropy 16), clip_near off and on, samples 1 and 2
+    -> {scene_filter_clip_samples: median, min, max, sha256}."""
     blocker = torch.randn(4096, 4096, dtype=torch.float16, device="cuda:0")
     mips = m.build_mips(tex)
+    filters = (("bilinear", {}), ("trilinear", dict(filter="trilinear", mips=mips)), ("anisotropy_16", dict(filter="trilinear", mips=mips, anisotropy=16)))
     out = {}
     for name, data, (eye, at, up, fov, near) in scenes():
         mesh = m.load_mesh(*data)
         cam = mesh.view_camera(eye, at, up, fov, SIZE, near)
-        calls = {"bilinear": lambda: m.render_view(mesh, tex, cam), "trilinear": lambda: m.render_view(mesh, tex, cam, filter="trilinear", mips=mips)}
+        calls = {f"{filt}_clip_{'on' if clip else 'off'}_samples_{s}": (lambda kw=kw, clip=clip, s=s: m.render_view(mesh, tex, cam, clip_near=clip, samples=s, **kw))
+                 for filt, kw in filters for clip in (False, True) for s in SAMPLES}
         times = {k: [] for k in calls}
         for _ in range(repeats):
             for k, call in calls.items():
@@ -106,6 +110,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--parent-lib", default=None, help="a libdtp.so of the parent commit for the comparison of the unchanged paths")
     ap.add_argument("--processes", type=int, default=2, help="fresh processes per library, alternating")
+    ap.add_argument("--stroke", action="store_true", help="with --parent-lib: also the 16-stamp stroke's sha256, once per library")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -131,6 +136,11 @@ def main():
             rows[frame] = dict(parent_ms=meds["parent"], this_build_ms=meds["this_build"], difference_ms=round(diff, 4), spread_ms=round(spread, 4),
                                within_the_spread=abs(diff) <= spread, sha256=sorted(shas), frames_byte_identical=len(shas) == 1)
         out["unchanged_frames_against_the_parent_build"] = dict(processes_per_library=a.processes, frames=rows)
+        if a.stroke:
+            cmd = [sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "mesh_pick_timing.py"), "--child", "--res", "512", "--texture", "2048",
+                   "--ddim-steps", "20", "--repeats", "1", "--grid", "225"]
+            strokes = {arm: run_child(cmd, lib) for arm, lib in (("parent", os.path.abspath(a.parent_lib)), ("this_build", ""))}
+            out["stroke_16_stamps"] = dict(strokes, texture_byte_identical=strokes["parent"]["sha256"] == strokes["this_build"]["sha256"])
     m, tex = setup(a.texture)
     out["anisotropic_frames"] = aniso_frames(m, tex, a.repeats)
     line = json.dumps(out)
