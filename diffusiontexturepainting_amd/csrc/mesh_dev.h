@@ -1,7 +1,7 @@
-// The device arithmetic that the mesh strokes (mesh.hip) and the view of a mesh (view.hip) share, so that there is ONE coverage rule:
-// vertices snapped to 1/256 pixel, edge functions in int64 with the top-left fill rule and both windings, interpolation and the bilinear
-// taps in fp32 one rounded operation at a time.  Every file that includes this is compiled with contraction off; the pragma below holds
-// for the rest of the including file as well.  Below it: what view.hip needs of a mesh, which lives in mesh.hip.
+// The device arithmetic that the mesh strokes (mesh.hip, mesh_bleed.hip, mesh_pick.hip) and the view of a mesh (view.hip) share, so that
+// there is ONE coverage rule: vertices snapped to 1/256 pixel, edge functions in int64 with the top-left fill rule and both windings,
+// interpolation and the bilinear taps in fp32 one rounded operation at a time.  Every file that includes this is compiled with contraction
+// off; the pragma below holds for the rest of the including file as well.  Below it: what view.hip needs of a mesh, which lives in mesh.hip.
 #pragma once
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
@@ -91,6 +91,48 @@ __device__ __forceinline__ int min3(int a, int b, int c) { return min(a, min(b, 
 __device__ __forceinline__ int max3(int a, int b, int c) { return max(a, max(b, c)); }
 // a range packed as lo | hi << 16 against [lo, hi]
 __device__ __forceinline__ bool ranges_meet(int packed, int lo, int hi) { return (packed & 0xffff) <= hi && (packed >> 16) >= lo; }
+
+// an entry of a face list: the face and its pixel (texel) ranges, 16 bits a bound
+__device__ __forceinline__ int4 pack_box(int f, int x0, int x1, int y0, int y1) { return make_int4(f, x0 | (x1 << 16), y0 | (y1 << 16), 0); }
+
+// texture-space position of a face's three UVs, snapped to 1/256 texel
+__device__ __forceinline__ void snap_uvs(const float* __restrict__ uv, int H, int W, int X[3], int Y[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    X[k] = snap((uv[2 * k] * (float)W) * 256.0f);
+    Y[k] = snap(((1.0f - uv[2 * k + 1]) * (float)H) * 256.0f);
+  }
+}
+// a face in texture space: false for a zero area or a texel box without a centre
+__device__ __forceinline__ bool face_texels(const float* __restrict__ uv, int H, int W, int X[3], int Y[3], int& x0, int& x1, int& y0, int& y1) {
+  snap_uvs(uv, H, W, X, Y);
+  if (orient(X[0], Y[0], X[1], Y[1], X[2], Y[2]) == 0) return false;
+  centre_range(min3(X[0], X[1], X[2]), max3(X[0], X[1], X[2]), W, x0, x1);
+  centre_range(min3(Y[0], Y[1], Y[2]), max3(Y[0], Y[1], Y[2]), H, y0, y1);
+  return x0 <= x1 && y0 <= y1;
+}
+
+// A 16 x 16 tile at (col0, row0), one thread per pixel (texel), against a list of n_list pack_box entries: the list streams through LDS
+// CHUNK entries at a time; an entry whose ranges miss the tile is dropped on the way in, any other takes a slot, which stage(slot, entry)
+// fills in the caller's own shared arrays; then every `live` thread calls visit(i) for the slots in turn.  s_n: the caller's shared
+// counter.  Every thread of the workgroup must call this (three barriers a round).
+template <typename Stage, typename Visit>
+__device__ __forceinline__ void stream_faces(const int4* __restrict__ list, int n_list, int col0, int row0, bool live, int& s_n, Stage stage, Visit visit) {
+  const int t = threadIdx.x;
+  for (int base = 0; base < n_list; base += CHUNK) {
+    if (t == 0) s_n = 0;
+    __syncthreads();
+    if (base + t < n_list) {
+      const int4 e = list[base + t];
+      if (ranges_meet(e.y, col0, col0 + 15) && ranges_meet(e.z, row0, row0 + 15)) stage(atomicAdd(&s_n, 1), e);
+    }
+    __syncthreads();
+    const int n = s_n;
+    if (live)
+      for (int i = 0; i < n; ++i) visit(i);
+    __syncthreads();
+  }
+}
 
 // ---------------------------------------------------------------- a mesh, as the view sees it
 struct Ctx;

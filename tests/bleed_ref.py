@@ -1,4 +1,4 @@
-"""Numpy restatement of the bleed pass of the mesh strokes (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_op_mesh_coverage; csrc/mesh.hip,
+"""Numpy restatement of the bleed pass of the mesh strokes (dtp_mesh_stroke_bleed, dtp_mesh_bleed, dtp_op_mesh_coverage; csrc/mesh_bleed.hip,
 DESIGN.md 3.21) for the tests, written from the contract in include/dtp.h: coverage of a texture by ALL faces of a mesh through
 mesh_ref.snap / mesh_ref.rasterize, the texel rectangle of a stamp, the order of the candidate offsets, and the pass by brute force.
 Everything is integer arithmetic and runs on the CPU."""

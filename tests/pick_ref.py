@@ -1,4 +1,4 @@
-"""Numpy restatement of picking on a mesh (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan; csrc/mesh.hip, csrc/mesh_host.h) for
+"""Numpy restatement of picking on a mesh (dtp_mesh_pick, dtp_mesh_ray_frame, dtp_mesh_path_plan; csrc/mesh_pick.hip, csrc/mesh_host.h) for
 the tests, written from the contract in include/dtp.h ("picking on a mesh") operation for operation: the ray frame and the grid's
 exponent in double, rounded to fp32 once; the per-face test in fp32 with every operation rounded once, on the render's snap, coverage and
 interpolation (mesh_ref.snap / cover / interp); the winner the largest (z, -face index); the record; the stamp spacing of a pointer path

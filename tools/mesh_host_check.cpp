@@ -1,9 +1,10 @@
-// Stand-alone host check of csrc/mesh.hip for a sanitizer build: the part of it that needs no device -- dtp_mesh_camera, the argument
+// Stand-alone host check of csrc/mesh.hip and csrc/mesh_bleed.hip for a sanitizer build: the part of it that needs no device -- dtp_mesh_camera, the argument
 // checks of dtp_mesh_create, dtp_mesh_destroy, dtp_mesh_stroke and the two ops, all of which return before their first HIP call, and
 // the host side of the bleed pass (the offset table, the rectangle clipping of csrc/mesh_host.h, the argument checks), and of the
 // occlusion test (the setting, the rounding of its tolerance, the refusals of the two occluded entry points) -- driven from its own main().  The rest of the library is replaced by the stubs below; none of them may be reached.  Build and run:
 //   hipcc --offload-arch=gfx950 -std=c++17 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         -I include -I diffusiontexturepainting_amd/csrc diffusiontexturepainting_amd/csrc/mesh.hip tools/mesh_host_check.cpp -o mesh_host_check
+//         -I include -I diffusiontexturepainting_amd/csrc diffusiontexturepainting_amd/csrc/mesh.hip \
+//         diffusiontexturepainting_amd/csrc/mesh_bleed.hip tools/mesh_host_check.cpp -o mesh_host_check
 //   ./mesh_host_check
 #include <math.h>
 #include <stdarg.h>
