@@ -106,6 +106,7 @@ def view_anisotropy_check(anisotropy, filter, want_taps, least=1):
 
 
 SELECT_OPS = {"replace": 0, "add": 1, "subtract": 2}  # DTP_SELECT_*
+EXTEND_HOWS = {"rings": 0, "shrink": 1, "linked": 2, "charts": 3}  # DTP_EXTEND_*
 
 
 class MipLevels(C.Structure):  # dtp_mip_levels
@@ -274,6 +275,10 @@ SYMBOLS = {
                                     _vp]),
     "dtp_view_tint": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, C.POINTER(C.c_uint8 * 3), _i, _vp]),
     "dtp_op_mesh_backproject_masked": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
+    "dtp_topology_build": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i * 3)]),
+    "dtp_mesh_topology": (_i, [_vp, C.POINTER(_i * 3), _vp]),
+    "dtp_mesh_topology_labels": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "dtp_mesh_select_extend": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "dtp_mesh_stroke_occluded": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(MeshStamp), _i, C.POINTER(Settings), C.POINTER(MeshStrokeOpts), _vp, _i, _vp, _i,
                                       _f, _vp]),
     "dtp_op_mesh_backproject_occluded": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _f, _f, _vp]),

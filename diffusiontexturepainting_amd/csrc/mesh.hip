@@ -343,6 +343,7 @@ void mesh_free(Mesh* m) {
   (void)hipFree(m->pick_rays); (void)hipFree(m->pick_slots); (void)hipFree(m->pick_out);
   if (m->pick_host) (void)hipHostFree(m->pick_host);
   view_free(m->view);
+  topo_free(m->topo);
   delete m;
 }
 

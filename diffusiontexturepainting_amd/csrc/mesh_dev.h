@@ -149,3 +149,4 @@ struct MeshGeom {
 };
 bool mesh_geom(dtp_mesh* mesh, MeshGeom* out);  // mesh.hip: false = not a live mesh (nothing is followed)
 void view_free(void* view);                     // view.hip: frees what *MeshGeom::view holds (null: nothing); called when the mesh is freed
+void topo_free(void* topo);                     // topology.hip: the same for the mesh's topology

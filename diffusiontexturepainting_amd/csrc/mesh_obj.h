@@ -1,5 +1,6 @@
-// The mesh object, as the three files that work on it see it: mesh.hip (the object itself and the strokes), mesh_bleed.hip (coverage and
-// the bleed pass) and mesh_pick.hip (picking).  Private to them: every other file reaches a mesh through mesh_geom (mesh_dev.h).
+// The mesh object, as the four files that work on it see it: mesh.hip (the object itself and the strokes), mesh_bleed.hip (coverage and
+// the bleed pass), mesh_pick.hip (picking) and topology.hip (growing a face set).  Private to them: every other file reaches a mesh
+// through mesh_geom (mesh_dev.h).
 #pragma once
 #include "mesh_dev.h"
 #include "mesh_host.h"
@@ -38,6 +39,7 @@ struct Mesh {
   int pick_cap = 0;
   int* sel_poly = nullptr;  // [2 * 1024]: the snapped polygon of the lasso in flight (select.hip); no stroke, pick or view touches it
   void* view = nullptr;  // the buffers of dtp_mesh_view (view.hip): allocated at the first view; no stroke or pick touches them
+  void* topo = nullptr;  // the topology and the scratch of dtp_mesh_select_extend (topology.hip): built at the first use
 };
 
 bool mesh_alive(const Mesh* m);  // mesh.hip, as the next two: a destroyed handle is refused, not followed

@@ -103,6 +103,16 @@ def _stroke_stamps(positions, seeds=None, modes=None, slots=None):
     return arr
 
 
+def _extend_args(how, rings):
+    """(how, rings as an int) of extend_selection; ValueError for a how that is not in the table or rings that is no integer (its range
+    is the library's to refuse)."""
+    if how not in _lib.EXTEND_HOWS:
+        raise ValueError(f"how {how!r}: choose one of {', '.join(_lib.EXTEND_HOWS)}")
+    if isinstance(rings, bool) or not isinstance(rings, int):
+        raise ValueError(f"rings = {rings!r}: an integer in 1..64")
+    return how, int(rings)
+
+
 def _tint_args(color, opacity):
     """(the 3 bytes of a tint as a ctypes array, the opacity as an int); ValueError outside 0..255."""
     if len(color) != 3 or not all(0 <= int(v) <= 255 for v in color) or isinstance(opacity, bool) or not 0 <= int(opacity) <= 255:
@@ -689,7 +699,7 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         extra = tuple(t for t in (face_idx if want_face_idx else None, depth, lod, taps, coverage) if t is not None)
         return (out,) + extra if extra else out
 
-    def select_faces(self, mesh, face_idx, polygon, op="replace", out=None):
+    def select_faces(self, mesh, face_idx, polygon, op="replace", out=None, extend=None, rings=1):
         """Lasso selection (dtp_mesh_select): the faces of `mesh` that a frame shows inside a polygon, as a face set --
         int32 [(F + 31) // 32] on the model's device, bit f % 32 of word f // 32 = face f (mesh.faceset_to_bool unpacks it; |, & and ~
         are union, intersection and complement).  face_idx: int32 [H, W] on the device, as render_view(want_face_idx=True) returns it
@@ -700,11 +710,15 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         pixels: what the user sees, not hidden, back-facing or sub-pixel faces.  op: "replace" (out is zeroed first), "add" or
         "subtract" (out is the set to edit).  out: default a fresh zeroed set.  The call only enqueues, on self.view_stream, behind
         the frame it reads and behind the caller's current stream, which then waits for the set (on the device).  One select of a
-        mesh at a time."""
+        mesh at a time.  extend: None, or a `how` of extend_selection ("rings", "shrink", "linked", "charts") with its `rings`: the
+        set the call leaves in `out` -- after the op, so with "add" the edited set -- is grown in place on the same stream
+        (DESIGN.md 3.33)."""
         if not isinstance(mesh, _mesh.Mesh):
             raise ValueError("mesh must come from load_mesh()")
         if op not in _lib.SELECT_OPS:
             raise ValueError(f"op {op!r}: choose one of {', '.join(_lib.SELECT_OPS)}")
+        if extend is not None:
+            extend, rings = _extend_args(extend, rings)
         if not (isinstance(face_idx, torch.Tensor) and face_idx.dtype == torch.int32 and face_idx.dim() == 2 and face_idx.device == self._device
                 and face_idx.is_contiguous()):
             raise ValueError(f"face_idx must be a contiguous int32 [H, W] tensor on {self._device}")
@@ -720,8 +734,46 @@ class MI355ConditionalInpainter(ConditionalInpainterBase):
         src = poly if n else torch.zeros(1, 2, dtype=torch.float32)  # (an empty tensor has no address; n = 0 is the library's to refuse)
         check(self._lib.dtp_mesh_select(mesh.handle, ptr(face_idx), face_idx.shape[0], face_idx.shape[1], ptr(src), n,
                                         _lib.SELECT_OPS[op], ptr(out), out.shape[0], C.c_void_p(self.view_stream.cuda_stream)), "dtp_mesh_select")
-        cur.wait_stream(self.view_stream)
+        try:
+            if extend is not None:
+                check(self._lib.dtp_mesh_select_extend(mesh.handle, ptr(out), ptr(out), out.shape[0], _lib.EXTEND_HOWS[extend], rings,
+                                                       C.c_void_p(self.view_stream.cuda_stream)), "dtp_mesh_select_extend")
+        finally:
+            cur.wait_stream(self.view_stream)  # (also when the growth is refused: the lasso is enqueued by then)
         for t in (face_idx, given):
+            if t is not None:
+                t.record_stream(self.view_stream)
+        if given is None:
+            out.record_stream(cur)
+        return out
+
+    def extend_selection(self, mesh, sel, how="rings", rings=1, out=None):
+        """Grow a face set on the device (dtp_mesh_select_extend; Blender's select more / less, linked, UV island).  how:
+        "rings": `rings` times, add every face that shares a point with a face of the set; "shrink": `rings` times, drop every face of the
+        set that shares a point with a face outside it (an open border is no outside face: the full set stays full); "linked": every face
+        of every part the set touches (the fixed point of "rings"); "charts": every face of every UV chart it touches.  A point is a
+        position: vertices with the same coordinates are one, so a mesh whose vertices are split along UV seams is still linked across
+        them (Mesh.topology() has the labels).  rings: 1..64, ignored by "linked" and "charts".  sel: a face set of `mesh` on the model's
+        device; its bits at positions >= F are ignored and those of the result are 0.  out: default a fresh set; out=sel works in place.
+        The call only enqueues, on self.view_stream with the waits select_faces makes, so lasso -> extend -> paint_mesh_stroke(face_mask=)
+        needs no synchronise; only the mesh's first use waits for that stream (it builds the topology).  One extend of a mesh at a
+        time."""
+        if not isinstance(mesh, _mesh.Mesh):
+            raise ValueError("mesh must come from load_mesh()")
+        how, rings = _extend_args(how, rings)
+        _mesh.faceset_check(sel, mesh.num_faces, self._device, what="sel")
+        if out is not None:
+            _mesh.faceset_check(out, mesh.num_faces, self._device, what="out")
+        cur = torch.cuda.current_stream(self._device)
+        given = out
+        with torch.cuda.stream(self.view_stream):
+            if out is None:
+                out = torch.empty_like(sel)
+        self.view_stream.wait_stream(cur)
+        check(self._lib.dtp_mesh_select_extend(mesh.handle, ptr(sel), ptr(out), sel.shape[0], _lib.EXTEND_HOWS[how], rings,
+                                               C.c_void_p(self.view_stream.cuda_stream)), "dtp_mesh_select_extend")
+        cur.wait_stream(self.view_stream)
+        for t in (sel, given):
             if t is not None:
                 t.record_stream(self.view_stream)
         if given is None:

@@ -7,7 +7,9 @@ pointer-to-paint call paint_mesh_path.  The view: the host-only
 the frame itself is MI355ConditionalInpainter.render_view (ops.mesh_view at op level).  Face sets: the packing of a
 set of faces into int32 words and its checks live here; the lasso is MI355ConditionalInpainter.select_faces, the stroke that respects a
 set paint_mesh_stroke(face_mask=), the tint tint_selection.  The occlusion test of the backprojection: the reading of
-the `occlude` keyword lives here; the test itself is paint_mesh_stroke(occlude=) and ops.mesh_backproject(fov=, occlude=)."""
+the `occlude` keyword lives here; the test itself is paint_mesh_stroke(occlude=) and ops.mesh_backproject(fov=, occlude=).  Growing a
+face set: Mesh.topology() and the host-only topology_build live here; the growth itself is
+MI355ConditionalInpainter.extend_selection and select_faces(extend=) (ops.faceset_extend at op level)."""
 import ctypes as C
 
 import torch
@@ -195,6 +197,24 @@ def faceset_check(sel, F, device, what="face_mask"):
     return sel
 
 
+def topology_build(vertices, faces, face_uvs):
+    """The topology of a mesh on the host (dtp_topology_build: host only, needs no GPU), from vertices [V, 3], faces [F, 3] and face_uvs
+    [F, 3, 2] -> the dict of Mesh.topology().  DtpError for what load_mesh refuses of the data."""
+    v = torch.as_tensor(vertices).detach().to("cpu", torch.float32).contiguous()
+    f = torch.as_tensor(faces).detach().to("cpu", torch.int32).contiguous()
+    uv = torch.as_tensor(face_uvs).detach().to("cpu", torch.float32).contiguous()
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3 or tuple(uv.shape) != (f.shape[0], 3, 2):
+        raise ValueError(f"vertices [V, 3], faces [F, 3] and face_uvs [F, 3, 2] expected, got {tuple(v.shape)}, {tuple(f.shape)}, {tuple(uv.shape)}")
+    F, n = f.shape[0], max(f.shape[0], 1)  # (an empty tensor has no address; F = 0 is the library's to refuse)
+    point, part, chart = torch.zeros(n, 3, dtype=torch.int32), torch.zeros(n, dtype=torch.int32), torch.zeros(n, dtype=torch.int32)
+    counts = (C.c_int * 3)()
+    src = [t if t.numel() else torch.zeros(1, dtype=t.dtype) for t in (v, f, uv)]
+    check(_lib.load().dtp_topology_build(_lib.ptr(src[0]), v.shape[0], _lib.ptr(src[1]), F, _lib.ptr(src[2]), _lib.ptr(point), _lib.ptr(part),
+                                         _lib.ptr(chart), C.byref(counts)), "dtp_topology_build")
+    return dict(point=point.numpy(), part=part.numpy(), chart=chart.numpy(), num_points=counts[0], num_parts=counts[1], num_charts=counts[2],
+                num_faces=F)
+
+
 OCCLUDE_DEFAULT = 1.0  # stamp pixels: what occlude=True means (DESIGN.md 3.32)
 
 
@@ -250,6 +270,26 @@ class Mesh:
     plan_path = staticmethod(plan_path)
     view_camera = staticmethod(view_camera)
     view_rays = staticmethod(view_rays)
+
+    def topology(self):
+        """The topology that extend_selection grows a face set by (dtp_mesh_topology, dtp_mesh_topology_labels), as numpy
+        on the host: point int32 [F, 3] (the lowest vertex index with the coordinates of that corner, -0.0 taken as +0.0: vertices split
+        along a UV seam weld), part int32 [F] (the lowest face of the faces linked to it through shared points), chart int32 [F] (the
+        lowest face of its UV chart: linked through edges on which the UVs agree), num_points, num_parts, num_charts and num_faces.  Built
+        on the first call, on the current stream, which it waits for; cached on the object."""
+        if getattr(self, "_topology", None) is None:
+            if not self._h:
+                raise ValueError("the mesh is closed")
+            F = self.num_faces
+            point, part, chart = torch.zeros(F, 3, dtype=torch.int32), torch.zeros(F, dtype=torch.int32), torch.zeros(F, dtype=torch.int32)
+            counts = (C.c_int * 3)()
+            dev = self._keep._device if self._keep is not None else torch.device("cuda", torch.cuda.current_device())
+            s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            check(self._lib.dtp_mesh_topology(self._h, C.byref(counts), s), "dtp_mesh_topology")
+            check(self._lib.dtp_mesh_topology_labels(self._h, _lib.ptr(point), _lib.ptr(part), _lib.ptr(chart), s), "dtp_mesh_topology_labels")
+            self._topology = dict(point=point.numpy(), part=part.numpy(), chart=chart.numpy(), num_points=counts[0], num_parts=counts[1],
+                                  num_charts=counts[2], num_faces=F)
+        return self._topology
 
     def close(self):
         if getattr(self, "_h", None):

@@ -671,6 +671,23 @@ def mesh_pick(mesh, origins, directions):
     return _mesh.hits_dict(rec)
 
 
+def faceset_extend(mesh, sel, how, rings=1, out=None):
+    """dtp_mesh_select_extend, the bare call on the current stream: the face set `sel` of `mesh` (a mesh.Mesh) grown by how = "rings",
+    "shrink", "linked" or "charts" (MI355ConditionalInpainter.extend_selection has the rules) -> out, default a fresh set; out=sel works in
+    place.  Only the mesh's first use waits (it builds the topology)."""
+    from . import mesh as _mesh
+    if how not in _lib.EXTEND_HOWS:
+        raise ValueError(f"how {how!r}: choose one of {', '.join(_lib.EXTEND_HOWS)}")
+    _mesh.faceset_check(sel, mesh.num_faces, sel.device if isinstance(sel, torch.Tensor) else "cpu", what="sel")
+    if out is None:
+        out = torch.empty_like(sel)
+    else:
+        _mesh.faceset_check(out, mesh.num_faces, sel.device, what="out")
+    check(_lib.load().dtp_mesh_select_extend(mesh.handle, ptr(sel), ptr(out), sel.shape[0], _lib.EXTEND_HOWS[how], int(rings), _stream()),
+          "dtp_mesh_select_extend")
+    return out
+
+
 def mesh_view(mesh, texture, camera, size=None, binned=True, want_face_idx=True, want_depth=True, clip_near=False, filter="bilinear", mips=None,
               want_lod=False, samples=1, want_coverage=False, anisotropy=None, want_taps=False, **opts):
     """dtp_op_mesh_view: the frame of MI355ConditionalInpainter.render_view on the current stream -> (image u8 [H,W,4], face_idx i32

@@ -29,7 +29,8 @@ extern "C" {
  * mip pyramid with its filtered view (dtp_mip_layout, dtp_texture_mips, dtp_mesh_view_mips) and the changed tiles of an image (dtp_delta_*, dtp_op_delta_state)
  * and the view clipped at the near plane (dtp_mesh_view_clip, dtp_op_mesh_view_clip) and the anti-aliased view (dtp_mesh_view_aa,
  * dtp_op_mesh_view_aa) and the anisotropic view (dtp_mesh_view_aniso, dtp_op_mesh_view_aniso) and the occlusion test of the
- * backprojection (dtp_mesh_stroke_occluded, dtp_op_mesh_backproject_occluded) are additions; nothing that existed at
+ * backprojection (dtp_mesh_stroke_occluded, dtp_op_mesh_backproject_occluded) and the growth of a face set (dtp_topology_build,
+ * dtp_mesh_topology, dtp_mesh_topology_labels, dtp_mesh_select_extend) are additions; nothing that existed at
  * version 3 changed its signature or behaviour, so a caller built against the earlier header keeps working. */
 #define DTP_ABI_VERSION 3
 
@@ -677,8 +678,8 @@ int dtp_mesh_view_aniso(dtp_mesh* mesh, const uint8_t* texture, int TH, int TW, 
  * (c (255 - opacity) + color[ch] opacity + 127) / 255 in integers, 0 <= opacity <= 255; alpha is untouched, and every other pixel is
  * neither read nor written.  One thread per pixel, one launch on `s`.  A pass of its own, so that no raster kernel changes.
  *
- * Not here: selecting through the mesh (hidden faces), growing a set to whole UV charts or by connectivity, texel-space stencils and the
- * 2D dtp_stroke, an outline instead of a tint, a wire message. */
+ * Not here: selecting through the mesh (hidden faces), texel-space stencils and the 2D dtp_stroke, an outline instead of a tint, a wire
+ * message.  (Growing a set to whole UV charts or by connectivity: the next section.) */
 #define DTP_SELECT_REPLACE 0
 #define DTP_SELECT_ADD 1
 #define DTP_SELECT_SUBTRACT 2
@@ -689,6 +690,62 @@ int dtp_mesh_stroke_masked(dtp_ctx* ctx, dtp_mesh* mesh, uint8_t* texture, int H
                            const uint32_t* face_mask, int mask_words, dtp_stream s);
 int dtp_view_tint(dtp_ctx* ctx, uint8_t* frame, const int* face_idx, int H, int W, const uint32_t* set, int words, int F,
                   const uint8_t color[3], int opacity, dtp_stream s);
+
+/* ---------------------------------------------------------------- growing a face set
+ * The lasso selects what a frame shows; what a painter means is "this chart", "this piece" or "what I circled plus a border" (DESIGN.md
+ * 3.33; Blender's select more / less, select linked, select UV island).  The growth runs on the device, in stream order, so that lasso ->
+ * extend -> masked stroke needs no synchronise.
+ *
+ * THE TOPOLOGY of a mesh is exact; no step uses a tolerance.
+ *  - Points.  The key of a vertex is the bit pattern of its three fp32 coordinates with -0.0 taken as +0.0; vertices with equal keys are
+ *    one point, named by the LOWEST vertex index that carries the key.  point[f][k] is the point of faces[f][k], a value in 0 .. V - 1.
+ *    (This welds meshes whose vertices are split along UV seams.)
+ *  - Parts.  Two faces are neighbours when they share a point; a part is a class of the transitive closure, and part[f] is the LOWEST
+ *    face index of the class of f.
+ *  - Charts.  Two faces are chart-neighbours when they share an edge -- the same unordered pair of two DIFFERENT points -- and at both
+ *    points of it the UV each face carries there is equal (fp32, component-wise, -0.0 == +0.0).  An edge shared by more than two faces
+ *    unites every pair whose UVs agree; a side of zero length is no edge.  chart[f] is the lowest face index of the class of f.  A chart
+ *    never spans two parts.
+ * dtp_topology_build (host only, like dtp_mesh_path_plan: no device, no handle): point i32 [F][3], part i32 [F], chart i32 [F];
+ * counts = {distinct points the faces use, parts, charts}.  The argument checks are dtp_mesh_create's (DTP_ERR_ARG: a NULL pointer,
+ * V < 1, F outside 1..2^20, a vertex or UV that is not finite, an index outside 0 .. V - 1).
+ * dtp_mesh_topology: the first call for a mesh copies its vertices, faces and UVs back on `s`, runs dtp_topology_build, allocates, uploads
+ * the three label arrays and allocates the scratch of dtp_mesh_select_extend (a mark bitset of (max(V, F) + 31) / 32 words and two face
+ * sets); it waits for `s` only, never for the null stream, so it does not sit behind a stroke queued elsewhere.  Later calls only return
+ * the counts (counts may be NULL).  The buffers are freed with the mesh.
+ * dtp_mesh_topology_labels: builds the topology if need be, copies the labels to the host on `s` and waits for `s` (for a UI's "select
+ * chart k" and for tests); a NULL array is skipped.
+ *
+ * dtp_mesh_select_extend: out = `in` grown by `how`, both face sets of the mesh on its device.
+ *  - DTP_EXTEND_RINGS, `rings` times: add every face that shares a point with a face of the set.
+ *  - DTP_EXTEND_SHRINK, `rings` times: drop every face of the set that shares a point with a face (< F) outside it.  An open border is
+ *    no outside face: the full set stays full.
+ *  - DTP_EXTEND_LINKED: every face of every part the set touches (the fixed point of RINGS).
+ *  - DTP_EXTEND_CHARTS: every face of every chart the set touches.
+ * Bits of `in` at positions >= F are ignored and bits of `out` there are written as 0; the empty set stays empty in every mode.
+ * in == out is allowed, otherwise the two must not overlap.  rings is 1..64 for RINGS and SHRINK and ignored for the others.  One step
+ * is three launches on `s` -- clear the mesh's mark bitset, mark (one thread per face: a face of the source, for SHRINK a face outside
+ * it, ORs the bits of its three points, its part or its chart), gather (one thread per face tests its labels' marks; the 64 bits of a
+ * wave leave as two word stores, each thread having read the source word of its own face before) -- so a call enqueues at most 3 x 64
+ * launches, the steps before the last writing the mesh's two scratch sets in turn.  The result is an OR of single bits and does not
+ * depend on the order of the atomics.  The call checks everything and then only enqueues: no host round trip and no allocation, except
+ * at the mesh's first use, which builds the topology as dtp_mesh_topology does.  It reads only the topology and the two sets, so it runs
+ * beside a stroke, a pick, a view or a lasso of the same mesh; one extend of a mesh at a time, because the scratch is the mesh's.
+ * Refusals, DTP_ERR_ARG before anything is enqueued: an unknown how, rings outside 1..64 with RINGS or SHRINK (these two before the mesh
+ * is looked at), a NULL pointer, a mesh that is not alive, words != (F + 31) / 32, a pointer that is not 4-byte aligned, `in` and `out`
+ * that overlap without being equal.
+ *
+ * Not here: a flood by dihedral angle ("select flat": a loop whose length the host cannot know), rings by edge adjacency, selecting
+ * through the mesh, an outline, a wire message. */
+#define DTP_EXTEND_RINGS 0
+#define DTP_EXTEND_SHRINK 1
+#define DTP_EXTEND_LINKED 2
+#define DTP_EXTEND_CHARTS 3
+int dtp_topology_build(const float* vertices, int V, const int* faces, int F, const float* face_uvs, int* point, int* part, int* chart,
+                       int counts[3]);
+int dtp_mesh_topology(dtp_mesh* mesh, int counts[3], dtp_stream s);
+int dtp_mesh_topology_labels(dtp_mesh* mesh, int* point, int* part, int* chart, dtp_stream s);
+int dtp_mesh_select_extend(dtp_mesh* mesh, const uint32_t* in, uint32_t* out, int words, int how, int rings, dtp_stream s);
 
 /* ---------------------------------------------------------------- occlusion in the backprojection
  * The render of a stamp decides visibility per pixel, the backprojection per face: a valid face (front, not steep, the winner of at
